@@ -9,12 +9,19 @@ CUDA graph, demo/lightglue_trt.cpp:347-366) and replayed once between barriers, 
 in HBM. value = calls/s over all ranks (replicas: each GPU runs its own stream of calls, no
 collective on the data path; the only collective is the max-over-ranks of the timer).
 
-Extra fields: roofline of the dominant kernel (main attention kernel; duration from HIP events
-on the launch stream), isolated single-call latency, the batched-launch throughput (several
-calls stacked in one launch) and the CPU baseline (the reference's PyTorch attention restated in
-oracle/oracle.py, timed on this host's cores on a bounded sample).
+A plain run sets up, runs the W warm-up steps, times the K steps and prints the line (metric, value,
+unit, ms_per_step, ...). `--dump-outputs DIR` also writes the O of the last timed step as DIR/out.npy
+(float32; the inputs are seeded, so two builds can be compared output for output).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+`--full` adds everything else the benchmark measures or checks, each in runs of its own after the
+headline: the same calls in 2000-step graphs, the cross-rank output digest, the roofline of the
+dominant kernel (main attention kernel; duration from HIP events on the launch stream), isolated
+single-call latency, the batched-launch throughput (several calls stacked in one launch), the
+variants, concurrent streams, the matcher figures and the CPU baseline (the reference's PyTorch
+attention restated in oracle/oracle.py, timed on this host's cores on a bounded sample). `--full
+--quick` keeps only the first two of those.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -206,13 +213,7 @@ def timed_replays(torch, replay, stream, barrier, reduce_max, replays, local=Non
     # untimed rehearsal: host submission time, and the sleep kernel's rate on this device
     host_s = submit()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    with torch.cuda.stream(stream):
-        e0.record(stream)
-        torch.cuda._sleep(int(1e7))
-        e1.record(stream)
-    torch.cuda.synchronize()
-    cycles_per_s = 1e7 / max(1e-6, e0.elapsed_time(e1) * 1e-3)
+    cycles_per_s = sleep_cycles_per_s(torch, stream)
 
     barrier()
     torch.cuda.synchronize()
@@ -225,6 +226,64 @@ def timed_replays(torch, replay, stream, barrier, reduce_max, replays, local=Non
     if local is not None:
         local["median_s"] = med
     return reduce_max(med), reduce_max(host)
+
+
+def sleep_cycles_per_s(torch, stream):
+    """The sleep kernel's rate on this device (cycles per second), from one 1e7-cycle sleep between events."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(stream):
+        e0.record(stream)
+        torch.cuda._sleep(int(1e7))
+        e1.record(stream)
+    torch.cuda.synchronize()
+    return 1e7 / max(1e-6, e0.elapsed_time(e1) * 1e-3)
+
+
+def split_steps(steps, chunk=2000):
+    """`steps` as chunks of at most `chunk` steps (the last one takes the remainder)."""
+    return [chunk] * (steps // chunk) + ([steps % chunk] if steps % chunk else [])
+
+
+def timed_chunks(torch, run_chunk, chunks, stream, barrier, reduce_max, round_steps=6000, local=None):
+    """The timed region for more steps than one backlog holds: the K steps are issued ONCE, as
+    `chunks` (split_steps) with a HIP event pair around each chunk (`run_chunk(n)` issues n steps),
+    and the chunk times are summed. The chunks go out in rounds of at most `round_steps` steps, each
+    round queued behind a sleep kernel sized from an untimed rehearsal of the first chunk, as
+    timed_replays does for its replays, so the host's submission stays out of the events; the stream
+    is drained between rounds. The cost of the run grows with K alone (no repetitions of the K
+    steps). Returns (max over ranks of the summed chunk times, max over ranks of the host's
+    submission time), in seconds; `local`, if given, receives this rank's own sum under "median_s"."""
+    t = time.perf_counter()
+    with torch.cuda.stream(stream):
+        run_chunk(chunks[0])
+    host_per_step = (time.perf_counter() - t) / chunks[0]
+    torch.cuda.synchronize()
+    cycles_per_s = sleep_cycles_per_s(torch, stream)
+
+    barrier()
+    torch.cuda.synchronize()
+    total_ms, host, i = 0.0, 0.0, 0
+    while i < len(chunks):
+        group = [chunks[i]]
+        i += 1
+        while i < len(chunks) and sum(group) + chunks[i] <= round_steps:
+            group.append(chunks[i])
+            i += 1
+        events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in group]
+        with torch.cuda.stream(stream):
+            torch.cuda._sleep(int(cycles_per_s * (1.25 * host_per_step * sum(group) + 2e-3)))
+            t = time.perf_counter()
+            for (s, e), n in zip(events, group):
+                s.record(stream)
+                run_chunk(n)
+                e.record(stream)
+            host += time.perf_counter() - t
+        torch.cuda.synchronize()
+        total_ms += sum(s.elapsed_time(e) for s, e in events)
+    barrier()
+    if local is not None:
+        local["median_s"] = total_ms * 1e-3
+    return reduce_max(total_ms * 1e-3), reduce_max(host)
 
 
 def claim_stdout(ws):
@@ -841,7 +900,13 @@ def main():
     ap.add_argument("--matcher-separate", action="store_true",
                     help="also time the 36 matcher calls as separate enqueues (adds other sizes of the headline "
                          "kernel to a profile of this command)")
-    ap.add_argument("--quick", action="store_true", help="skip the secondary measurements (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement and check (2000-step graphs, "
+                         "cross-rank digest, roofline, batched, variants, streams, matcher, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the O of the last timed step as DIR/out.npy (float32; ranks > 0: out_rank<r>.npy)")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: skip the secondary measurements (keep the 2000-step graphs and the digest)")
     ap.add_argument("--sweep", action="store_true", help="time every workgroup shape x KV split (stderr table)")
     ap.add_argument("--only", choices=["call", "batched"], default=None,
                     help="profiling driver: launch just this workload --steps times (eager), print nothing else")
@@ -908,19 +973,40 @@ def main():
         for _ in range(args.steps):
             enqueue()
 
-    if args.launch == "graph":                       # ... or one replay of a graph captured from them
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=stream):
-            enqueue_steps()
-        graph.replay()                               # upload / first-replay cost outside the timer
+    def graph_of(n):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=stream):
+            for _ in range(n):
+                enqueue()
+        g.replay()                                   # upload / first-replay cost outside the timer
         stream.synchronize()
-        run_steps = graph.replay
-    else:
-        run_steps = enqueue_steps
+        return g
 
-    replays = args.replays if args.replays > 0 else max(10, min(250, -(-5000 // args.steps)))
-    mine = {}
-    elapsed, wall = timed_replays(torch, run_steps, stream, barrier, reduce_max, replays, local=mine)
+    mine, chunks = {}, None
+    if args.replays == 0 and args.steps > 5000:
+        # more steps than one backlog holds: the K steps issued once, in chunks (timed_chunks)
+        chunks, replays = split_steps(args.steps), 1
+        if args.launch == "graph":
+            graphs = {n: graph_of(n) for n in set(chunks)}
+            run_chunk = lambda n: graphs[n].replay()
+        else:
+            def run_chunk(n):
+                for _ in range(n):
+                    enqueue()
+        elapsed, wall = timed_chunks(torch, run_chunk, chunks, stream, barrier, reduce_max, local=mine)
+    else:
+        # ... K enqueues, or one replay of a graph captured from them
+        run_steps = graph_of(args.steps).replay if args.launch == "graph" else enqueue_steps
+        replays = args.replays if args.replays > 0 else max(10, min(250, -(-5000 // args.steps)))
+        elapsed, wall = timed_replays(torch, run_steps, stream, barrier, reduce_max, replays, local=mine)
+    if args.dump_outputs:
+        # the timed path's result: O as its last timed step left it (before any --full measurement
+        # writes to the same buffer)
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "out.npy" if rank == 0 else f"out_rank{rank}.npy"),
+                out.float().cpu().numpy())
     total_calls = args.steps * ws
     value = total_calls / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
@@ -930,7 +1016,7 @@ def main():
     # driver's K = 20 the enqueue form runs 5.0 us per call, the graph form 5.35
     # (profiles/r06/headline_launch_ab.txt). The same calls in 2000-step graphs, for comparison:
     long_rate = None
-    if args.steps < 2000:
+    if args.full and args.steps < 2000:
         g2 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g2, stream=stream):
             for _ in range(2000):
@@ -942,14 +1028,16 @@ def main():
         del g2
 
     # Bit-identity across devices: every rank runs the same seeded pair-call and hashes its output.
-    import hashlib
+    digests = None
+    if args.full:
+        import hashlib
 
-    cq, ck, cv = (torch.from_numpy(x).to(device).half().contiguous() for x in synth.qkv(4242, nq, nkv))
-    co = torch.empty_like(cq)
-    with torch.cuda.stream(stream):
-        lightglue_amd.mha_hd64(cq, ck, cv, out=co)
-    stream.synchronize()
-    digests = gather(dist, hashlib.sha256(co.cpu().numpy().tobytes()).hexdigest()[:16])
+        cq, ck, cv = (torch.from_numpy(x).to(device).half().contiguous() for x in synth.qkv(4242, nq, nkv))
+        co = torch.empty_like(cq)
+        with torch.cuda.stream(stream):
+            lightglue_amd.mha_hd64(cq, ck, cv, out=co)
+        stream.synchronize()
+        digests = gather(dist, hashlib.sha256(co.cpu().numpy().tobytes()).hexdigest()[:16])
 
     import ctypes
 
@@ -976,12 +1064,16 @@ def main():
         "timing": {"replays": replays, "launch": args.launch,
                    "per_replay": "HIP events on the launch stream around the K steps (K enqueues or one K-step "
                                  "graph replay); median over replays, max over ranks; replays "
-                                                     "queued behind a sleep kernel so host submission does not gap "
-                                                     "the GPU",
+                                 "queued behind a sleep kernel so host submission does not gap "
+                                 "the GPU" if chunks is None else
+                                 f"the K steps issued once as {len(chunks)} chunks of <= {max(chunks)} steps, HIP events "
+                                 "on the launch stream around each chunk, chunk times summed, max over ranks; "
+                                 "each round of chunks queued behind a sleep kernel so host submission does not "
+                                 "gap the GPU",
                    "host_submit_ms_per_replay": round(wall * 1e3, 4),
                    "calls_per_s_in_2000_step_graphs": long_rate},
         "per_rank_calls_per_s": rank_values,
-        "outputs_bitwise_identical_across_ranks": len(set(digests)) == 1,
+        "outputs_bitwise_identical_across_ranks": None if digests is None else len(set(digests)) == 1,
         "config": {"workload": "MHAHeadDim64 plugin enqueue, Q/K/V [1,4,1024,64] fp16 -> O fp16 "
                                "(BASELINE configs[1]); K independent plugin enqueues per timed repetition",
                    "batch": 1, "heads": 4, "nq": nq, "nkv": nkv, "head_dim": 64,
@@ -989,7 +1081,7 @@ def main():
                    "plan": {"q_waves": q_waves, "kv_waves": kv_waves, "kv_splits": splits}},
     }
 
-    if not args.quick:
+    if args.full and not args.quick:
         ws_buf = torch.empty(max(ws_need, 16), dtype=torch.uint8, device=device)
 
         def forced(mask):
@@ -1184,7 +1276,7 @@ def main():
 
     if args.sweep and rank == 0:
         sweep(torch, lib, device, stream, nq, nkv)
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline and not args.quick:  # CPU baseline: N=1 only
+    if rank == 0 and ws == 1 and args.full and not args.no_cpu_baseline and not args.quick:  # CPU baseline: N=1 only
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds, nq, nkv)
     if rank == 0:
         print(json.dumps(result), file=result_out, flush=True)

@@ -213,7 +213,7 @@ def test_claim_stdout_keeps_only_the_json_line():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_on_hardware():
-    """The N>1 path on the GPU box: `BENCH_SHARE_DEVICE=1 bench.py --gpus 2 --quick` (two rank
+    """The N>1 path on the GPU box: `BENCH_SHARE_DEVICE=1 bench.py --gpus 2 --full --quick` (two rank
     processes sharing the one GPU, gloo group, per-rank rates, cross-rank output digest). Exactly one
     JSON line on stdout."""
     import json
@@ -222,8 +222,8 @@ def test_bench_two_ranks_on_hardware():
         pytest.skip("no GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["BENCH_SHARE_DEVICE"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--quick", "--steps", "200",
-                        "--warmup", "20"], env=env, capture_output=True, text=True, timeout=110)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--quick", "--steps",
+                        "200", "--warmup", "20"], env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -231,3 +231,45 @@ def test_bench_two_ranks_on_hardware():
     assert d["n_gpus"] == 2 and d["value"] > 0
     assert len(d["per_rank_calls_per_s"]) == 2 and all(v > 0 for v in d["per_rank_calls_per_s"])
     assert d["outputs_bitwise_identical_across_ranks"] is True
+
+
+def test_split_steps_covers_every_step_once():
+    import bench
+
+    for n in (1, 1999, 2000, 2001, 5001, 20000, 123457):
+        chunks = bench.split_steps(n)
+        assert sum(chunks) == n and all(0 < c <= 2000 for c in chunks)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_timed_output(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times its K steps and nothing else (what moved
+    behind --full is absent from the line), and --dump-outputs writes the O of the last timed step:
+    float32, the bits mha_hd64 gives on the same seeded inputs."""
+    import json
+
+    import numpy as np
+
+    import lightglue_amd
+    from lightglue_amd import synth
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["unit"] == "calls/s" and d["dtype"] == "fp16" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1e3) < 1.0  # ms_per_step = 1e3 / (calls/s)
+    assert d["timing"]["calls_per_s_in_2000_step_graphs"] is None
+    for moved in ("roofline", "batched", "variants", "matcher_e2e_fp16", "cpu_baseline"):
+        assert moved not in d
+    assert sorted(os.listdir(tmp_path)) == ["out.npy"]
+    got = np.load(tmp_path / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 4, 1024, 64)
+    q, k, v = (torch.from_numpy(x).cuda().half().contiguous() for x in synth.qkv(100, 1024, 1024))
+    want = lightglue_amd.mha_hd64(q, k, v).float().cpu().numpy()
+    assert np.array_equal(got, want)

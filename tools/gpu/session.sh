@@ -6,7 +6,7 @@
 #        pmc_ffn:<P>:<n>:<mode>  "tool:<tools/NAME.py> [args...]" (one quoted word)
 #        "frstamps:<P> <n> <kind>" (FFN segment stamps; build lib/ab/libmha_hd64_frstamps.so first with
 #        tools/build_linear_variant.sh frstamps -DLG_FR_STAMPS)
-# (the round-start check: gpu smoke "bench:--steps 20 --warmup 5"; round 5's 50 tools/gpu/r05_*.sh
+# (the round-start check: gpu smoke "bench:--full --steps 20 --warmup 5"; round 5's 50 tools/gpu/r05_*.sh
 # sessions were each one such list of steps, folded into this script in round 6)
 set -o pipefail
 tag=$1; shift

@@ -9,7 +9,7 @@ REPO=$PWD
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- \
-    python3 "$REPO/bench.py" --steps 20 --warmup 5 > "$OUT/bench_stdout.json" 2> "$OUT/bench_stderr.log"
+    python3 "$REPO/bench.py" --full --steps 20 --warmup 5 >"$OUT/bench_stdout.json" 2> "$OUT/bench_stderr.log"
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o call -- \
       python3 "$REPO/bench.py" --only call --steps 50 --warmup 5 > /dev/null 2> "$OUT/pmc_$C.log"
