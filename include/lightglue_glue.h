@@ -19,7 +19,9 @@
  * lg_glue_abi_version() == LG_GLUE_ABI_VERSION once at load.
  * ABI version 3 (round 6): lg_linear_cat_ffn takes the packed weight stream of its one-launch form
  * (w_packed, after b2; lg_ffn_pack). ABI version 4: lg_ffn_pack writes two layouts (the 16-row
- * kernel's after the 32-row kernel's; lg_ffn_packed_bytes doubled).
+ * kernel's after the 32-row kernel's; lg_ffn_packed_bytes doubled). Still version 4 with
+ * lg_assign_matches and its workspace query: new symbols change no existing argument list, and a
+ * library without them fails the loader's symbol check (reported as stale).
  */
 #ifndef LIGHTGLUE_GLUE_H_
 #define LIGHTGLUE_GLUE_H_
@@ -183,6 +185,31 @@ int32_t lg_log_double_softmax_f16(const void* sim, const void* z0, const void* z
 size_t lg_assign_scores_workspace(int32_t m, int32_t n, int32_t batch);
 int32_t lg_assign_scores(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
                          float* scores, void* workspace, hipStream_t stream);
+
+/* The match head: filter_matches (lightglue.py:235-258, with the dense outputs it keeps commented out)
+ * applied to the scores lg_assign_scores would write for the same v, without that tensor: at most
+ * three launches (the similarity + logsumexp launch of lg_assign_scores, a "best" pass in the
+ * combine's place that keeps each row's and column's (max, index) per block, and one workgroup per
+ * pair that closes them and writes the outputs), no atomics, bitwise reproducible.
+ *   s[i][j] = (2 sim[i][j] + rterm[i]) + cterm[j]   (each with the bits lg_assign_scores writes)
+ *   j*(i) = argmax_j s[i][j], i*(j) = argmax_i s[i][j], ties to the lowest index
+ *   mscores0[i] = i*(j*(i)) == i ? expf(s[i][j*(i)]) : 0;  valid0[i] = mscores0[i] > threshold
+ *   matches0[i] = valid0[i] ? j*(i) : -1
+ *   mutual1[j] = j*(i*(j)) == j;  mscores1[j] = mutual1 ? mscores0[i*(j)] : 0
+ *   matches1[j] = mutual1 && valid0[i*(j)] ? i*(j) : -1
+ *   matches / mscores: the valid rows (i, j*(i)) / mscores0[i] in ascending i; counts[p] their number
+ *   (<= min(m, n)); list rows past it hold -1 / 0.
+ * v, pair_stride, ld, zc, m, n, batch as for lg_assign_scores (m, n <= 2048, n % 8 == 0, ld % 8 == 0,
+ * 256 <= zc < ld); threshold >= 0; v and workspace 16-B aligned, the outputs 4-B aligned; workspace >=
+ * lg_assign_matches_workspace(m, n, batch) bytes (lg_assign_scores' layout, then the per-block bests).
+ * batch == 0 is a no-op; m == 0 or n == 0 writes only counts (zeros; it may then be null). Inputs are
+ * assumed finite; otherwise values are unspecified but every index written is in range or -1.
+ * (Additions leave every earlier argument list as it was, so LG_GLUE_ABI_VERSION stays 4; a library
+ * built before them lacks the symbols, which the Python loader reports as a stale library.) */
+size_t lg_assign_matches_workspace(int32_t m, int32_t n, int32_t batch);
+int32_t lg_assign_matches(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
+                          float threshold, int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1,
+                          int32_t* matches, float* mscores, int32_t* counts, void* workspace, hipStream_t stream);
 
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]

@@ -1922,16 +1922,12 @@ __device__ __forceinline__ float lse_close(const float2* part, size_t stride, in
     return mx + __logf(s);
 }
 
-// scores = 2 sim + rterm[i] + cterm[j] (fp32), the terms logsig(z) - logsumexp closed here from the S
-// partials (round 6: a separate close launch cost ~4.7 us at a single pair): the block's 8 W rows'
-// and 512 columns' terms into LDS (256 threads; every partial and z load in flight at once), then each
-// of the W combine waves writes 8 rows, a lane 8 columns (16-B loads, 2 x 16-B stores)
+// The closed terms logsig(z) - logsumexp of a block's 8 W rows (rts) and 512 columns (cts) from the S
+// partials, by 256 threads (every partial and z load in flight at once); ends in the block's barrier.
+// Shared by the combine and the match head's best kernel, so both see the same bits.
 template <int W>
-__global__ __launch_bounds__(256) void assign_combine_kernel(AsArgs a) {
-    __shared__ float rts[8 * W], cts[512];
-    const int p = blockIdx.z, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int ib = blockIdx.x * 8 * W, jb = blockIdx.y * 512;
+__device__ __forceinline__ void assign_close_terms(const AsArgs& a, int p, int ib, int jb, float* rts, float* cts) {
+    const int tid = threadIdx.x;
     const f16* const vp = a.v + (size_t)p * a.ps;
     if (tid < 8 * W && ib + tid < a.m) {
         const float z = (float)vp[(size_t)(ib + tid) * a.ld + a.zc];
@@ -1945,6 +1941,19 @@ __global__ __launch_bounds__(256) void assign_combine_kernel(AsArgs a) {
         }
     }
     __syncthreads();
+}
+
+// scores = 2 sim + rterm[i] + cterm[j] (fp32), the terms logsig(z) - logsumexp closed here from the S
+// partials (round 6: a separate close launch cost ~4.7 us at a single pair): the block's 8 W rows'
+// and 512 columns' terms into LDS (256 threads; every partial and z load in flight at once), then each
+// of the W combine waves writes 8 rows, a lane 8 columns (16-B loads, 2 x 16-B stores)
+template <int W>
+__global__ __launch_bounds__(256) void assign_combine_kernel(AsArgs a) {
+    __shared__ float rts[8 * W], cts[512];
+    const int p = blockIdx.z, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int ib = blockIdx.x * 8 * W, jb = blockIdx.y * 512;
+    assign_close_terms<W>(a, p, ib, jb, rts, cts);
     const int i0 = ib + wave * 8, j = jb + lane * 8;
     if (wave >= W || i0 >= a.m || j >= a.n) return;
     const int i1 = min(i0 + 8, a.m);
@@ -1969,6 +1978,180 @@ __global__ __launch_bounds__(256) void assign_combine_kernel(AsArgs a) {
         *reinterpret_cast<f32x4*>(out + (size_t)(i0 + b) * a.n + j) = o0;
         *reinterpret_cast<f32x4*>(out + (size_t)(i0 + b) * a.n + j + 4) = o1;
     }
+}
+
+// ---- the match head: mutual nearest neighbours without the scores tensor (lg_assign_matches) ----
+// filter_matches (lightglue.py:235-258, its commented-out dense outputs included) on the scores the
+// combine would write, in two launches after assign_lse_kernel:
+//  * assign_best_kernel takes the combine's place (blocks of 32 rows x 512 columns, the same closes and
+//    16-B loads of sim, each score evaluated as the combine evaluates it) and keeps, instead of the
+//    scores, each row's (max, column) over the block's columns (rbest, one slab per column block) and
+//    each column's (max, row) over the block's rows (cbest, one slab per 32-row strip).
+//  * assign_finish_kernel, one workgroup per pair: closes the slabs in ascending order, the mutual and
+//    threshold logic of both sides, and the compact list by a prefix sum over the pair's rows.
+// Ties go to the lowest index everywhere (strict > in ascending order; the wave reduction compares
+// (value, index)); no atomics and no exchange between workgroups inside a launch, so a call is
+// bitwise reproducible.
+struct AmArgs {
+    AsArgs a;
+    int RB, CB, K;      // 32-row strips, 512-column blocks, list rows per pair = min(m, n)
+    float thr;
+    float2* rbest;      // workspace [batch][CB][m]: (max, column as int bits) of row i over column block c
+    float2* cbest;      // workspace [batch][RB][n]: (max, row as int bits) of column j over row strip r
+    int *m0, *m1, *mt, *cnt;
+    float *s0, *s1, *ms;
+};
+
+__global__ __launch_bounds__(256) void assign_best_kernel(AmArgs q) {
+    const AsArgs& a = q.a;
+    __shared__ float rts[32], cts[512];
+    __shared__ __attribute__((aligned(16))) float cbv[4][512];
+    __shared__ __attribute__((aligned(16))) int cbi[4][512];
+    const int p = blockIdx.z, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int ib = blockIdx.x * 32, jb = blockIdx.y * 512;
+    assign_close_terms<4>(a, p, ib, jb, rts, cts);
+    const int i0 = ib + wave * 8, j = jb + lane * 8;
+    const int i1 = min(i0 + 8, a.m);          // (<= i0: a wave past the last row)
+    const bool act = j < a.n && i0 < i1;      // this lane holds 8 columns of >= 1 row
+    const f16* sim = a.sim + (size_t)p * a.m * a.n;
+    f16x8 x[8] = {};
+    float cl[8] = {};
+    if (act) {
+#pragma unroll
+        for (int b = 0; b < 8; ++b) x[b] = *reinterpret_cast<const f16x8*>(sim + (size_t)min(i0 + b, i1 - 1) * a.n + j);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) cl[e] = cts[lane * 8 + e];
+    }
+    float cv[8];
+    int ci[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) cv[e] = -INFINITY, ci[e] = ib;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const int i = i0 + b;
+        if (i >= i1) break;  // (wave-uniform)
+        float bv = -INFINITY;
+        int bj = j < a.n ? j : 0x7fffffff;
+        if (act) {
+            const float rt = rts[wave * 8 + b];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float s = 2.f * (float)x[b][e] + rt + cl[e];
+                if (s > bv) bv = s, bj = j + e;
+                if (s > cv[e]) cv[e] = s, ci[e] = i;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float ov = __shfl_xor(bv, off, 64);
+            const int oj = __shfl_xor(bj, off, 64);
+            if (ov > bv || (ov == bv && oj < bj)) bv = ov, bj = oj;
+        }
+        if (lane == 0) q.rbest[((size_t)p * q.CB + blockIdx.y) * a.m + i] = make_float2(bv, __int_as_float(bj));
+    }
+    // the block's columns over its 4 waves' rows, in wave (= row) order
+#pragma unroll
+    for (int e = 0; e < 8; ++e) cbv[wave][lane * 8 + e] = cv[e], cbi[wave][lane * 8 + e] = ci[e];
+    __syncthreads();
+#pragma unroll
+    for (int c = tid; c < 512; c += 256) {
+        if (jb + c >= a.n) continue;
+        float v = cbv[0][c];
+        int i = cbi[0][c];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (cbv[w][c] > v) v = cbv[w][c], i = cbi[w][c];
+        q.cbest[((size_t)p * q.RB + blockIdx.x) * a.n + jb + c] = make_float2(v, __int_as_float(i));
+    }
+}
+
+__global__ __launch_bounds__(1024) void assign_finish_kernel(AmArgs q) {
+    const AsArgs& a = q.a;
+    __shared__ int js[2048], is[2048];   // j*(i), i*(j)
+    __shared__ float sc[2048];           // row i's best score, then mscores0[i]
+    __shared__ unsigned char vld[2048];  // valid0[i]
+    __shared__ int wsum[16];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = a.m, n = a.n;
+    for (int i = tid; i < m; i += 1024) {
+        float2 r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = k < q.CB ? q.rbest[((size_t)p * q.CB + k) * m + i] : make_float2(-INFINITY, 0.f);
+        float bv = r[0].x;
+        int bj = __float_as_int(r[0].y);
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            if (k < q.CB && r[k].x > bv) bv = r[k].x, bj = __float_as_int(r[k].y);
+        js[i] = min(max(bj, 0), n - 1);
+        sc[i] = bv;
+    }
+    for (int j = tid; j < n; j += 1024) {
+        float bv = -INFINITY;
+        int bi = 0;
+        for (int k0 = 0; k0 < q.RB; k0 += 8) {
+            float2 c[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                c[k] = k0 + k < q.RB ? q.cbest[((size_t)p * q.RB + k0 + k) * n + j] : make_float2(-INFINITY, 0.f);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k0 + k < q.RB && c[k].x > bv) bv = c[k].x, bi = __float_as_int(c[k].y);
+        }
+        is[j] = min(max(bi, 0), m - 1);
+    }
+    __syncthreads();
+    // the row side; a thread owns rows 2 tid and 2 tid + 1, so the list keeps ascending i
+    bool val[2] = {false, false};
+    float ms[2] = {0.f, 0.f};
+    int jj[2] = {0, 0};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int i = 2 * tid + k;
+        if (i >= m) continue;
+        jj[k] = js[i];
+        const bool mutual = is[jj[k]] == i;
+        ms[k] = mutual ? expf(sc[i]) : 0.f;
+        val[k] = ms[k] > q.thr;
+        sc[i] = ms[k];
+        vld[i] = val[k];
+        q.m0[(size_t)p * m + i] = val[k] ? jj[k] : -1;
+        q.s0[(size_t)p * m + i] = ms[k];
+    }
+    const int cnt = (int)val[0] + (int)val[1];
+    int inc = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();  // (also: sc and vld of every row written)
+    for (int j = tid; j < n; j += 1024) {
+        const int i = is[j];
+        const bool mutual = js[i] == j;
+        q.s1[(size_t)p * n + j] = mutual ? sc[i] : 0.f;
+        q.m1[(size_t)p * n + j] = (mutual && vld[i]) ? i : -1;
+    }
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+        if (w < wave) base += wsum[w];
+        total += wsum[w];
+    }
+    int pos = base + inc - cnt;
+    int* const mt = q.mt + (size_t)p * q.K * 2;
+    float* const mso = q.ms + (size_t)p * q.K;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!val[k] || pos >= q.K) continue;  // (pos < K always: valid rows map to distinct columns)
+        mt[2 * pos] = 2 * tid + k, mt[2 * pos + 1] = jj[k];
+        mso[pos] = ms[k];
+        ++pos;
+    }
+    total = min(total, q.K);
+    for (int r = total + tid; r < q.K; r += 1024) mt[2 * r] = -1, mt[2 * r + 1] = -1, mso[r] = 0.f;
+    if (tid == 0) q.cnt[p] = total;
 }
 
 constexpr int kTileGrid = 256;  // the 256-row forms: one workgroup per CU
@@ -2302,13 +2485,74 @@ int assign_splits(int32_t m, int32_t n, int32_t batch) {
     while (S < 8 && base * S * 2 <= 256) S *= 2;
     return S;
 }
+size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+// the workspace both heads share (sim, the lse partials, the terms' slots) and assign_lse_kernel's launch
+void assign_layout(AsArgs& a, char* ws, int32_t batch) {
+    const size_t b = (size_t)batch, S = (size_t)a.S, m = (size_t)a.m, n = (size_t)a.n;
+    a.sim = (f16*)ws;
+    a.rpart = (float2*)(ws + up256(b * m * n * 2));
+    a.cpart = (float2*)((char*)a.rpart + up256(b * S * m * 8));
+    a.rterm = (float*)((char*)a.cpart + up256(b * S * n * 8));
+    a.cterm = (float*)((char*)a.rterm + up256(b * m * 4));
+}
+void launch_assign_lse(const AsArgs& a, int32_t batch, hipStream_t stream) {
+    const int m = a.m, n = a.n;
+    const dim3 g1(a.rb0 + (n + 31) / 32, batch, a.S);
+    const int oth = m > n ? m : n;  // other-image blocks per wave: ceil(blocks / (8 S))
+    const int bpw = ((oth + 31) / 32 + 8 * a.S - 1) / (8 * a.S);
+    if (bpw <= 1) hipLaunchKernelGGL(assign_lse_kernel<1>, g1, dim3(512), 0, stream, a);
+    else if (bpw <= 2) hipLaunchKernelGGL(assign_lse_kernel<2>, g1, dim3(512), 0, stream, a);
+    else if (bpw <= 4) hipLaunchKernelGGL(assign_lse_kernel<4>, g1, dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL(assign_lse_kernel<8>, g1, dim3(512), 0, stream, a);
+}
 }  // namespace
 
 size_t lg_assign_scores_workspace(int32_t m, int32_t n, int32_t batch) {
     if (m <= 0 || n <= 0 || batch <= 0) return 0;
     const size_t b = (size_t)batch, S = (size_t)assign_splits(m, n, batch);
-    return (b * m * n * 2 + 255) / 256 * 256 + (b * S * m * 8 + 255) / 256 * 256 + (b * S * n * 8 + 255) / 256 * 256 +
-           (b * m * 4 + 255) / 256 * 256 + (b * n * 4 + 255) / 256 * 256;
+    return up256(b * m * n * 2) + up256(b * S * m * 8) + up256(b * S * n * 8) + up256(b * m * 4) + up256(b * n * 4);
+}
+
+// lg_assign_scores' layout, then rbest [batch][CB][m] and cbest [batch][RB][n] (8 B each)
+size_t lg_assign_matches_workspace(int32_t m, int32_t n, int32_t batch) {
+    if (m <= 0 || n <= 0 || batch <= 0) return 0;
+    const size_t b = (size_t)batch, cb = (size_t)(n + 511) / 512, rb = (size_t)(m + 31) / 32;
+    return lg_assign_scores_workspace(m, n, batch) + up256(b * cb * m * 8) + up256(b * rb * n * 8);
+}
+
+int32_t lg_assign_matches(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
+                          float threshold, int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1,
+                          int32_t* matches, float* mscores, int32_t* counts, void* workspace, hipStream_t stream) {
+    auto aligned4 = [](const void* p) { return ((uintptr_t)p & 3) == 0; };
+    const bool work = m > 0 && n > 0 && batch > 0;
+    if (m < 0 || n < 0 || batch < 0 || m > 2048 || n > 2048 || n % 8 != 0 || ld < 256 || ld % 8 != 0 || zc < 256 ||
+        zc >= ld || pair_stride < (int64_t)(m + n) * ld || !(threshold >= 0.f) || !aligned4(counts) ||
+        (work && (!v || !workspace || !aligned16(v) || !aligned16(workspace) || !matches0 || !matches1 || !mscores0 ||
+                  !mscores1 || !matches || !mscores || !counts || !aligned4(matches0) || !aligned4(matches1) ||
+                  !aligned4(mscores0) || !aligned4(mscores1) || !aligned4(matches) || !aligned4(mscores))))
+        return bad("lg_assign_matches");
+    if (batch == 0) return MHA_HD64_STATUS_SUCCESS;
+    if (m == 0 || n == 0) {  // no rows or no columns: no match in any pair
+        if (!counts) return MHA_HD64_STATUS_SUCCESS;
+        const hipError_t e = hipMemsetAsync(counts, 0, (size_t)batch * 4, stream);
+        return e == hipSuccess ? MHA_HD64_STATUS_SUCCESS
+                               : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, "lg_assign_matches", hipGetErrorString(e));
+    }
+    AmArgs q{};
+    AsArgs& a = q.a;
+    a.v = (const f16*)v, a.ps = (long)pair_stride, a.ld = ld, a.zc = zc, a.m = m, a.n = n, a.rb0 = (m + 31) / 32;
+    a.S = assign_splits(m, n, batch);
+    assign_layout(a, (char*)workspace, batch);
+    q.RB = (m + 31) / 32, q.CB = (n + 511) / 512, q.K = m < n ? m : n, q.thr = threshold;
+    q.rbest = (float2*)((char*)workspace + lg_assign_scores_workspace(m, n, batch));
+    q.cbest = (float2*)((char*)q.rbest + up256((size_t)batch * q.CB * m * 8));
+    q.m0 = matches0, q.m1 = matches1, q.mt = matches, q.cnt = counts, q.s0 = mscores0, q.s1 = mscores1, q.ms = mscores;
+    launch_assign_lse(a, batch, stream);
+    hipLaunchKernelGGL(assign_best_kernel, dim3(q.RB, q.CB, batch), dim3(256), 0, stream, q);
+    hipLaunchKernelGGL(assign_finish_kernel, dim3(batch), dim3(1024), 0, stream, q);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MHA_HD64_STATUS_SUCCESS
+                           : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, "lg_assign_matches", hipGetErrorString(e));
 }
 
 int32_t lg_assign_scores(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
@@ -2322,21 +2566,9 @@ int32_t lg_assign_scores(const void* v, int64_t pair_stride, int32_t ld, int32_t
     AsArgs a{};
     a.v = (const f16*)v, a.ps = (long)pair_stride, a.ld = ld, a.zc = zc, a.m = m, a.n = n, a.rb0 = (m + 31) / 32;
     a.S = assign_splits(m, n, batch);
-    char* ws = (char*)workspace;
-    const size_t b = (size_t)batch, S = (size_t)a.S;
-    a.sim = (f16*)ws;
-    a.rpart = (float2*)(ws + (b * m * n * 2 + 255) / 256 * 256);
-    a.cpart = (float2*)((char*)a.rpart + (b * S * m * 8 + 255) / 256 * 256);
-    a.rterm = (float*)((char*)a.cpart + (b * S * n * 8 + 255) / 256 * 256);
-    a.cterm = (float*)((char*)a.rterm + (b * m * 4 + 255) / 256 * 256);
+    assign_layout(a, (char*)workspace, batch);
     a.scores = scores;
-    const dim3 g1(a.rb0 + (n + 31) / 32, batch, a.S);
-    const int oth = m > n ? m : n;  // other-image blocks per wave: ceil(blocks / (8 S))
-    const int bpw = ((oth + 31) / 32 + 8 * a.S - 1) / (8 * a.S);
-    if (bpw <= 1) hipLaunchKernelGGL(assign_lse_kernel<1>, g1, dim3(512), 0, stream, a);
-    else if (bpw <= 2) hipLaunchKernelGGL(assign_lse_kernel<2>, g1, dim3(512), 0, stream, a);
-    else if (bpw <= 4) hipLaunchKernelGGL(assign_lse_kernel<4>, g1, dim3(512), 0, stream, a);
-    else hipLaunchKernelGGL(assign_lse_kernel<8>, g1, dim3(512), 0, stream, a);
+    launch_assign_lse(a, batch, stream);
     // combine (with the row / column closes): blocks of 8 W rows x 512 columns (W = 4: 32 rows; 1 where
     // that leaves the chip idle)
     const int cb = (n + 511) / 512;

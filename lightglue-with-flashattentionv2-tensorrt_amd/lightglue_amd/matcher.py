@@ -20,6 +20,10 @@ What is different, and why:
   kernels (include/lightglue_glue.h: q/k/v split + rotary + per-image head-major layout in one
   pass, head split/merge, LayerNorm+GELU, the dual log-softmax); ``glue="torch"`` is the same
   math in framework ops (the restatement the CPU tests pin to the reference);
+* ``match_batch`` returns the matches of all pairs of a forward as one ``MatchResult`` (the dense
+  outputs ``filter_matches`` keeps commented out, :241-252, and the compacted list): on the fp16 hip
+  path from ``lg_assign_matches``, which never writes the scores tensor; elsewhere from
+  ``filter_matches_dense``, the same semantics in framework ops;
 * ``attention=`` lets tests substitute the oracle for the kernel on CPU; the default path
   requires GPU tensors and fails loudly otherwise (no CPU fallback).
 """
@@ -28,7 +32,7 @@ from __future__ import annotations
 import ctypes
 import os
 import zlib
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -265,6 +269,25 @@ class _Hip:
         _Hip._last_assign_ws = ws
         st = lib.lg_assign_scores(v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, out.data_ptr(), ws.data_ptr(), stream)
         _check(st, "lg_assign_scores")
+        return out
+
+    @staticmethod
+    def assign_matches(v, m, zc, threshold):
+        """v as for assign_scores -> MatchResult for all P pairs (lg_assign_matches: at most three
+        launches, no fp32 scores tensor, no framework op, no host synchronisation)."""
+        pr, n, ch = v.shape[0], v.shape[1] - m, v.shape[2]
+        k = min(m, n)
+        lib = _lib.load()
+        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=v.device)    # noqa: E731
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=v.device)  # noqa: E731
+        out = MatchResult(i32(pr, m), i32(pr, n), f32(pr, m), f32(pr, n), i32(pr, k, 2), f32(pr, k), i32(pr))
+        stream = _Hip._stream(v)
+        ws = _workspace(v.device, stream, lib.lg_assign_matches_workspace(m, n, pr))
+        st = lib.lg_assign_matches(v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, float(threshold), out.matches0.data_ptr(),
+                                   out.matches1.data_ptr(), out.scores0.data_ptr(), out.scores1.data_ptr(),
+                                   out.matches.data_ptr(), out.match_scores.data_ptr(), out.counts.data_ptr(),
+                                   ws.data_ptr(), stream)
+        _check(st, "lg_assign_matches")
         return out
 
     @staticmethod
@@ -571,6 +594,14 @@ class MatchAssignment(nn.Module):
         v = _Hip.linear(x, w, b).view(pr, m + n, 384)
         return _Hip.assign_scores(v, m, d)   # sim (fp16) and the dual log-softmax: two launches
 
+    def matches_rows(self, x: torch.Tensor, pr: int, m: int, n: int, threshold: float) -> "MatchResult":
+        """forward_rows' projection, then lg_assign_matches: the matches of all P pairs without the
+        scores tensor (filter_matches_dense's semantics on the scores forward_rows would return)."""
+        d = x.shape[-1]
+        w, b = self.aug_weights(x.dtype, 384)
+        v = _Hip.linear(x, w, b).view(pr, m + n, 384)
+        return _Hip.assign_matches(v, m, d, threshold)
+
     def forward(self, d0: torch.Tensor, d1: torch.Tensor, hip: bool = False) -> torch.Tensor:
         m0 = self.final_proj(d0) / self.scale
         m1 = self.final_proj(d1) / self.scale
@@ -592,6 +623,72 @@ def filter_matches(scores: torch.Tensor, th: float):
     keep = ms > th
     idx0 = rows[keep]
     return torch.stack([idx0, m0[0][idx0]], -1), ms[idx0]
+
+
+class MatchResult(NamedTuple):
+    """Matches of P image pairs (filter_matches with the reference's commented-out dense outputs,
+    lightglue.py:235-258). Indices are int32, as lg_assign_matches writes them (filter_matches returns
+    int64); scores are fp32.
+
+    matches0 [P, M]: the column matched to row i, or -1; matches1 [P, N]: the row matched to column j,
+    or -1; scores0 [P, M] / scores1 [P, N]: exp(score) of the mutual nearest neighbour, else 0 (also
+    below the threshold, where matches* is -1); matches [P, min(M, N), 2] / match_scores [P, min(M, N)]:
+    the matched (i, j) in ascending i, rows past counts[p] holding -1 / 0; counts [P]."""
+    matches0: torch.Tensor
+    matches1: torch.Tensor
+    scores0: torch.Tensor
+    scores1: torch.Tensor
+    matches: torch.Tensor
+    match_scores: torch.Tensor
+    counts: torch.Tensor
+
+
+def _argmax_lowest(scores: torch.Tensor, dim: int):
+    """(max, argmax) along dim with ties to the lowest index (numpy's rule; torch.max promises none on
+    the GPU): the minimum over the indices that hold the maximum."""
+    size = scores.shape[dim]
+    mx = scores.amax(dim, keepdim=True)
+    shape = [1] * scores.dim()
+    shape[dim] = size
+    idx = torch.arange(size, device=scores.device).view(shape)
+    first = torch.where(scores == mx, idx, idx.new_full((), size)).amin(dim)
+    return mx.squeeze(dim), first.clamp_(max=size - 1)  # (a row of NaNs holds its maximum nowhere)
+
+
+def filter_matches_dense(scores: torch.Tensor, th: float) -> MatchResult:
+    """filter_matches for all P pairs of a log assignment [P, M, N] at once, with the dense outputs
+    (lightglue.py:235-258 with its commented-out lines): framework ops only, no loop over pairs and no
+    host synchronisation. Ties go to the lowest index. th >= 0. The restatement lg_assign_matches is
+    checked against; LightGlueMatcher.match_batch runs it for the shapes that kernel does not take."""
+    if th < 0:
+        raise ValueError("filter_matches_dense: th must be >= 0")
+    pr, m, n = scores.shape
+    k, dev = min(m, n), scores.device
+    i32 = torch.int32
+    if k == 0:
+        z = lambda *s: torch.zeros(s, dtype=scores.dtype, device=dev)       # noqa: E731
+        e = lambda *s: torch.full(s, -1, dtype=i32, device=dev)             # noqa: E731
+        return MatchResult(e(pr, m), e(pr, n), z(pr, m), z(pr, n), e(pr, 0, 2), z(pr, 0),
+                           torch.zeros((pr,), dtype=i32, device=dev))
+    v0, j0 = _argmax_lowest(scores, 2)       # best column per row
+    _, i1 = _argmax_lowest(scores, 1)        # best row per column
+    rows = torch.arange(m, device=dev)[None]
+    cols = torch.arange(n, device=dev)[None]
+    zero = torch.zeros((), dtype=v0.dtype, device=dev)
+    mutual0 = i1.gather(1, j0) == rows
+    ms0 = torch.where(mutual0, v0.exp(), zero)
+    valid0 = ms0 > th
+    mutual1 = j0.gather(1, i1) == cols
+    ms1 = torch.where(mutual1, ms0.gather(1, i1), zero)
+    valid1 = mutual1 & valid0.gather(1, i1)
+    counts = valid0.sum(1)
+    # the valid rows first, in ascending i (stable); valid rows are mutual, so there are <= min(M, N)
+    order = torch.argsort((~valid0).to(torch.uint8), dim=1, stable=True)[:, :k]
+    keep = torch.arange(k, device=dev)[None] < counts[:, None]
+    lst = torch.stack([order, j0.gather(1, order)], -1)
+    return MatchResult(torch.where(valid0, j0, -1).to(i32), torch.where(valid1, i1, -1).to(i32), ms0, ms1,
+                       torch.where(keep[..., None], lst, -1).to(i32), torch.where(keep, ms0.gather(1, order), zero),
+                       counts.to(i32))
 
 
 class LightGlueMatcher(nn.Module):
@@ -629,8 +726,14 @@ class LightGlueMatcher(nn.Module):
                 and kpts0.shape[-1] == 2 and kpts1.shape[-1] == 2 and tuple(self.posenc.Wr.weight.shape) == (32, 2))
 
     def forward(self, kpts0, kpts1, desc0, desc1):
+        return self._forward(kpts0, kpts1, desc0, desc1)
+
+    def _forward(self, kpts0, kpts1, desc0, desc1, threshold: Optional[float] = None):
+        """forward; with `threshold` (match_batch) the fp16 hip head returns a MatchResult from
+        lg_assign_matches in the scores' place. Every other path returns scores as ever."""
         pr, m, n = desc0.shape[0], desc0.shape[1], desc1.shape[1]
         hip = self.glue == "hip"
+        rows_out = threshold is not None and self.attention is _kernel_attention
         if not hip and pr > 1:  # the framework-op restatement: one pair at a time
             outs = [self.forward(kpts0[i:i + 1], kpts1[i:i + 1], desc0[i:i + 1], desc1[i:i + 1]) for i in range(pr)]
             return tuple(torch.cat(t, 0) for t in zip(*outs))
@@ -649,11 +752,16 @@ class LightGlueMatcher(nn.Module):
                 cos, sin = cos.contiguous(), sin.contiguous()
         head = self.log_assignment[self.n_layers - 1]
         if hip and self.chain_ok(x, m, n):
-            x, scores = self._forward_chain(x, cos, sin, splits)
+            x, scores = self._forward_chain(x, cos, sin, splits, rows=rows_out)
+            if rows_out:  # the head's projected rows v: the matches without the scores tensor
+                scores = _Hip.assign_matches(scores, m, x.shape[-1], threshold)
         else:
             for layer in self.transformers:
                 x = layer(x, cos, sin, splits, self.attention, hip)
-            scores = head.forward_rows(x, pr, m, n) if hip and head.hip16_ok(x, m, n) else None
+            if hip and head.hip16_ok(x, m, n):
+                scores = head.matches_rows(x, pr, m, n, threshold) if rows_out else head.forward_rows(x, pr, m, n)
+            else:
+                scores = None
         x = x.view(pr, m + n, x.shape[-1])
         d0, d1 = x[:, :m], x[:, m:]
         return d0, d1, scores if scores is not None else head(d0, d1, hip)
@@ -682,7 +790,7 @@ class LightGlueMatcher(nn.Module):
         return (self.n_layers > 0 and all(_fused_ok(x, layer.self_attn) for layer in self.transformers) and
                 self.log_assignment[self.n_layers - 1].hip16_ok(x, m, n))
 
-    def _forward_chain(self, x, cos, sin, splits):
+    def _forward_chain(self, x, cos, sin, splits, rows: bool = False):
         """fp16 hip path with the layers chained (round 6): FFN launches also project their output for
         the attention that follows (lg_linear_cat_ffn_proj) — by default the self block's FFN the cross
         block's to_qk | to_v, the cross block's FFN the next layer's Wqkv (+ rotary) and the last FFN
@@ -730,7 +838,10 @@ class LightGlueMatcher(nn.Module):
         if v is None:
             w, b = head.aug_weights(dt, 384)
             v = _Hip.linear(x, w, b)
-        return x, _Hip.assign_scores(v.view(pr, m + n, 384), m, x.shape[-1])
+        v = v.view(pr, m + n, 384)
+        if rows:  # (match_batch: the head's projected rows instead of the scores)
+            return x, v
+        return x, _Hip.assign_scores(v, m, x.shape[-1])
 
     def match(self, kpts0, kpts1, desc0, desc1):
         """forward + filter_matches (the demo's post-processing); for P > 1 pairs a list of
@@ -739,6 +850,16 @@ class LightGlueMatcher(nn.Module):
         if scores.shape[0] == 1:
             return filter_matches(scores, self.filter_threshold)
         return [filter_matches(scores[i:i + 1], self.filter_threshold) for i in range(scores.shape[0])]
+
+    def match_batch(self, kpts0, kpts1, desc0, desc1) -> MatchResult:
+        """The matches of all P pairs as one MatchResult (dense matches and scores of both images and
+        the compacted list), without a loop over pairs or a host synchronisation. On the fp16 hip path
+        the forward stops at the head's projection and lg_assign_matches takes its rows (the forward's
+        launches through the last FFN, then at most three; the fp32 scores tensor is never written).
+        Every other case (fp32 model, glue='torch', n % 8 != 0, more than 2048 keypoints, a substituted
+        attention=) computes the scores as forward does and runs filter_matches_dense on them."""
+        out = self._forward(kpts0, kpts1, desc0, desc1, threshold=self.filter_threshold)[2]
+        return out if isinstance(out, MatchResult) else filter_matches_dense(out, self.filter_threshold)
 
 
 # --------------------------------------------------------------------------------------------
