@@ -211,6 +211,29 @@ int32_t lg_assign_matches(const void* v, int64_t pair_stride, int32_t ld, int32_
                           float threshold, int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1,
                           int32_t* matches, float* mscores, int32_t* counts, void* workspace, hipStream_t stream);
 
+/* Both heads on ragged batches: the layout is the padded one (m and n stay the strides and limits:
+ * <= 2048, n % 8 == 0), and pair p's leading m_len[p] rows of image 0 and n_len[p] rows of image 1 are
+ * real. m_len, n_len: DEVICE int32 [batch], 4-B aligned, clamped into [1, m] / [1, n] by the kernels,
+ * multiples of nothing; a null table means every pair has all m (n) rows, and with both null the
+ * results equal lg_assign_scores / lg_assign_matches bit for bit. The counts are read when the kernels
+ * run (a captured call replays with what the tables hold then).
+ * Everything said above for lg_assign_scores / lg_assign_matches holds on the pair's [m_len, n_len]
+ * sub-matrix: both logsumexps run over its entries only, and
+ *   scores[p][i][j] = -inf exactly for i >= m_len[p] or j >= n_len[p];
+ *   matches0 = -1 and mscores0 = 0 on padded rows, matches1 = -1 and mscores1 = 0 on padded columns;
+ *   the list keeps min(m, n) rows per pair, counts[p] <= min(m_len[p], n_len[p]).
+ * (So filter_matches on the padded scores gives the pair's matches unchanged.) No padded row of v is
+ * ever read: it may hold anything, NaN and Inf included. Workspaces: lg_assign_scores_workspace /
+ * lg_assign_matches_workspace of (m, n, batch), the same layout. New symbols only:
+ * LG_GLUE_ABI_VERSION stays 4. */
+int32_t lg_assign_scores_lens(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
+                              const int32_t* m_len, const int32_t* n_len, float* scores, void* workspace,
+                              hipStream_t stream);
+int32_t lg_assign_matches_lens(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n,
+                               int32_t batch, const int32_t* m_len, const int32_t* n_len, float threshold,
+                               int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1, int32_t* matches,
+                               float* mscores, int32_t* counts, void* workspace, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

@@ -208,6 +208,35 @@ size_t mha_hd64_grouped_workspace_bytes(const mha_hd64_call_t* calls, int32_t n_
  * (chunks reuse the workspace in stream order). 0 for an invalid in_type. */
 size_t mha_hd64_grouped_workspace_bytes_typed(const mha_hd64_call_t* calls, int32_t n_calls, int32_t in_type);
 
+/* ---- grouped launcher with per-item key counts (ragged batches; no reference counterpart: the
+ * reference runs one pair per enqueue) ----
+ * As mha_hd64_launch_grouped for fp16 inputs (in_type HALF; out_type HALF or FLOAT), but item b of
+ * call i attends to keys 0 .. len - 1 of its [heads, nkv, 64] K/V slab only, len = kv_lens[i][b]:
+ * kv_lens[i] is a DEVICE pointer to calls[i].batch int32 values, or NULL for "every item of call i
+ * uses nkv". The layout is the padded one: strides stay nkv. The kernel clamps len into [1, nkv]
+ * (a bad value can neither read out of bounds nor divide by zero) and never reads a key at or past
+ * len: its K/V buffer descriptors end there, so those rows may hold anything, NaN and Inf included.
+ * Query rows are not masked: every row of O is written, from that item's valid keys. The counts are
+ * read on the device when the kernel runs (one scalar load per item): a captured launch replays with
+ * whatever the tables hold then. Always the persistent streaming kernel, the wave form as the
+ * planner chooses it; no key split, so workspace is unused and may be NULL. BAD_PARAM (before any
+ * device call) for FLOAT in_type, null calls or a null kv_lens array with n_calls > 0, misaligned
+ * pointers. More than 4 calls are chunked. Returns a status. */
+int32_t mha_hd64_launch_grouped_lens(const mha_hd64_call_t* calls, const int32_t* const* kv_lens, int32_t n_calls,
+                                     int32_t in_type, int32_t out_type, void* workspace, size_t ws_bytes,
+                                     hipStream_t stream);
+/* The same with query-row counts as well: q_lens[i] is a device table of calls[i].batch int32 values
+ * (or NULL: all nq rows; q_lens itself may be NULL), and rows at or past q_lens[i][b] of item b are
+ * padding. A wave of the kernel decides for its 32 query rows together when to move their running
+ * maxima (the lazy rescale), so a row's rounding depends on what its 31 neighbours hold; padded rows
+ * are therefore taken out of those decisions (their Q is zeroed on load by select, like a non-finite
+ * query row's) and written as NaN. With both tables a real row's output bits depend on no padded row
+ * of Q, K or V, NaN and Inf included. (The matcher passes both: self attention of image i counts_i
+ * twice, cross attention i -> j counts_i for the rows and counts_j for the keys.) */
+int32_t mha_hd64_launch_grouped_qkv_lens(const mha_hd64_call_t* calls, const int32_t* const* q_lens,
+                                         const int32_t* const* kv_lens, int32_t n_calls, int32_t in_type,
+                                         int32_t out_type, void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* ---- concurrency hint (no reference counterpart: TensorRT gives a plugin no view of its
  * other streams) ----
  * How many independent enqueue streams the host keeps busy on this process's GPUs at once
@@ -251,6 +280,11 @@ int32_t mha_hd64_launch_forced(const void* q, const void* k, const void* v, void
                                int32_t nq, int32_t nkv, int32_t in_f32, int32_t out_f32, int32_t q_waves,
                                int32_t kv_waves, int32_t splits, void* workspace, size_t ws_bytes,
                                hipStream_t stream, int32_t phase_mask);
+/* One call through mha_hd64_launch_grouped_lens' kernel with a pinned wave form: kv_len is a device
+ * table of `batch` int32 key counts (or NULL), waves 4 / 8 its 4- / 8-wave form, 0 the planner's. */
+int32_t mha_hd64_launch_stream_lens(const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t heads,
+                                    int32_t nq, int32_t nkv, const int32_t* kv_len, int32_t out_f32, int32_t waves,
+                                    hipStream_t stream);
 /* The planner's choice for a fp16 call: out4 = {q_waves (or 21/22/23), kv_waves, splits,
  * tiles_per_split} (streaming plan: {23, 4 or 8 waves, 1, ...}); returns the workspace bytes that
  * plan uses. */

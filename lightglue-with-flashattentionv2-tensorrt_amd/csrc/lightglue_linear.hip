@@ -1779,8 +1779,18 @@ struct AsArgs {
     float* rterm;     // workspace [batch][m] (round 6's separate close; kept in the workspace layout)
     float* cterm;     // workspace [batch][n]
     float* scores;    // [batch][m][n]
+    // Ragged batches (lg_assign_scores_lens / lg_assign_matches_lens): pair p's leading mlen[p] rows and
+    // nlen[p] columns are real, the rest padding (null: all m / n). m and n stay the strides and the
+    // launch bounds. No kernel reads a padded row of v, and every use of a padded slot of the workspace
+    // is a select, never arithmetic.
+    const int* mlen;
+    const int* nlen;
 };
 __device__ __forceinline__ float log_sigmoid_f(float z) { return fminf(z, 0.f) - log1pf(__expf(-fabsf(z))); }
+// pair p's valid count, clamped into [1, full] (null table: full)
+__device__ __forceinline__ int assign_len(const int* lens, int p, int full) {
+    return lens ? min(max(lens[p], 1), full) : full;
+}
 
 template <int BPW>  // 32-row blocks of the other image per wave
 __global__ __launch_bounds__(512, 1) void assign_lse_kernel(AsArgs a) {
@@ -1795,7 +1805,11 @@ __global__ __launch_bounds__(512, 1) void assign_lse_kernel(AsArgs a) {
     const int p = blockIdx.y, sp = blockIdx.z;
     const bool side = (int)blockIdx.x >= a.rb0;
     const int o0 = (side ? (int)blockIdx.x - a.rb0 : (int)blockIdx.x) * 32;
-    const int nown = side ? a.n : a.m, noth = side ? a.m : a.n;
+    // the pair's valid rows of both images: every bound below (loads, the other image's descriptor, the
+    // key mask, the partials' store) is the valid count, so padded rows are never read
+    const int nown = assign_len(side ? a.nlen : a.mlen, p, side ? a.n : a.m);
+    const int noth = assign_len(side ? a.mlen : a.nlen, p, side ? a.m : a.n);
+    if (o0 >= nown) return;  // (ragged only) a workgroup wholly in padding: its partials are never read
     const f16* const vp = a.v + (size_t)p * a.ps;
     const f16* const own = vp + (size_t)(side ? a.m : 0) * a.ld;
     const f16* const oth = vp + (size_t)(side ? 0 : a.m) * a.ld;
@@ -1929,13 +1943,15 @@ template <int W>
 __device__ __forceinline__ void assign_close_terms(const AsArgs& a, int p, int ib, int jb, float* rts, float* cts) {
     const int tid = threadIdx.x;
     const f16* const vp = a.v + (size_t)p * a.ps;
-    if (tid < 8 * W && ib + tid < a.m) {
+    // (ragged: the terms of valid rows and columns only; the other slots of rts / cts stay unwritten)
+    const int ml = assign_len(a.mlen, p, a.m), nl = assign_len(a.nlen, p, a.n);
+    if (tid < 8 * W && ib + tid < ml) {
         const float z = (float)vp[(size_t)(ib + tid) * a.ld + a.zc];
         rts[tid] = log_sigmoid_f(z) - lse_close(a.rpart + (size_t)p * a.S * a.m + ib + tid, a.m, a.S);
     }
 #pragma unroll
     for (int c = tid; c < 512; c += 256) {
-        if (jb + c < a.n) {
+        if (jb + c < nl) {
             const float z = (float)vp[(size_t)(a.m + jb + c) * a.ld + a.zc];
             cts[c] = log_sigmoid_f(z) - lse_close(a.cpart + (size_t)p * a.S * a.n + jb + c, a.n, a.S);
         }
@@ -1957,6 +1973,9 @@ __global__ __launch_bounds__(256) void assign_combine_kernel(AsArgs a) {
     const int i0 = ib + wave * 8, j = jb + lane * 8;
     if (wave >= W || i0 >= a.m || j >= a.n) return;
     const int i1 = min(i0 + 8, a.m);
+    // (ragged) padded rows and columns are written too, as -inf, by select: what sim, rts and cts hold
+    // there (unwritten workspace and LDS) never enters a written value
+    const int ml = assign_len(a.mlen, p, a.m), nl = assign_len(a.nlen, p, a.n);
     const f16* sim = a.sim + (size_t)p * a.m * a.n;
     float* out = a.scores + (size_t)p * a.m * a.n;
     f16x8 x[8];
@@ -1969,11 +1988,12 @@ __global__ __launch_bounds__(256) void assign_combine_kernel(AsArgs a) {
     for (int b = 0; b < 8; ++b) {
         if (i0 + b >= i1) break;
         const float rt = rts[wave * 8 + b];
+        const int nv = i0 + b < ml ? nl - j : 0;  // this lane's valid columns of the row (<= 0: none)
         f32x4 o0, o1;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            o0[e] = 2.f * (float)x[b][e] + rt + cl[e];
-            o1[e] = 2.f * (float)x[b][e + 4] + rt + cl[e + 4];
+            o0[e] = e < nv ? 2.f * (float)x[b][e] + rt + cl[e] : -INFINITY;
+            o1[e] = e + 4 < nv ? 2.f * (float)x[b][e + 4] + rt + cl[e + 4] : -INFINITY;
         }
         *reinterpret_cast<f32x4*>(out + (size_t)(i0 + b) * a.n + j) = o0;
         *reinterpret_cast<f32x4*>(out + (size_t)(i0 + b) * a.n + j + 4) = o1;
@@ -2010,10 +2030,14 @@ __global__ __launch_bounds__(256) void assign_best_kernel(AmArgs q) {
     const int p = blockIdx.z, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int ib = blockIdx.x * 32, jb = blockIdx.y * 512;
+    // (ragged) the pair's valid rows and columns bound everything; a block wholly in padding leaves its
+    // slabs unwritten, and the finish kernel reads the slabs of blocks with a valid row and column only
+    const int ml = assign_len(a.mlen, p, a.m), nl = assign_len(a.nlen, p, a.n);
+    if (ib >= ml || jb >= nl) return;
     assign_close_terms<4>(a, p, ib, jb, rts, cts);
     const int i0 = ib + wave * 8, j = jb + lane * 8;
-    const int i1 = min(i0 + 8, a.m);          // (<= i0: a wave past the last row)
-    const bool act = j < a.n && i0 < i1;      // this lane holds 8 columns of >= 1 row
+    const int i1 = min(i0 + 8, ml);           // (<= i0: a wave past the last row)
+    const bool act = j < nl && i0 < i1;       // this lane holds >= 1 column of >= 1 row
     const f16* sim = a.sim + (size_t)p * a.m * a.n;
     f16x8 x[8] = {};
     float cl[8] = {};
@@ -2032,12 +2056,13 @@ __global__ __launch_bounds__(256) void assign_best_kernel(AmArgs q) {
         const int i = i0 + b;
         if (i >= i1) break;  // (wave-uniform)
         float bv = -INFINITY;
-        int bj = j < a.n ? j : 0x7fffffff;
+        int bj = j < nl ? j : 0x7fffffff;
         if (act) {
             const float rt = rts[wave * 8 + b];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float s = 2.f * (float)x[b][e] + rt + cl[e];
+                // (a padded column of a ragged pair: -inf by select, never above any best)
+                const float s = j + e < nl ? 2.f * (float)x[b][e] + rt + cl[e] : -INFINITY;
                 if (s > bv) bv = s, bj = j + e;
                 if (s > cv[e]) cv[e] = s, ci[e] = i;
             }
@@ -2056,7 +2081,7 @@ __global__ __launch_bounds__(256) void assign_best_kernel(AmArgs q) {
     __syncthreads();
 #pragma unroll
     for (int c = tid; c < 512; c += 256) {
-        if (jb + c >= a.n) continue;
+        if (jb + c >= nl) continue;
         float v = cbv[0][c];
         int i = cbi[0][c];
 #pragma unroll
@@ -2074,31 +2099,36 @@ __global__ __launch_bounds__(1024) void assign_finish_kernel(AmArgs q) {
     __shared__ int wsum[16];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int m = a.m, n = a.n;
-    for (int i = tid; i < m; i += 1024) {
+    // (ragged) ml x nl is the pair's valid sub-matrix: the slabs of its blocks only (cbn column blocks, rbn
+    // strips: the ones assign_best_kernel wrote), its rows and columns only; the padded rows and
+    // columns get -1 / 0 below. The slabs' strides stay q.CB, q.RB, m, n.
+    const int ml = assign_len(a.mlen, p, m), nl = assign_len(a.nlen, p, n);
+    const int cbn = (nl + 511) / 512, rbn = (ml + 31) / 32;
+    for (int i = tid; i < ml; i += 1024) {
         float2 r[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = k < q.CB ? q.rbest[((size_t)p * q.CB + k) * m + i] : make_float2(-INFINITY, 0.f);
+        for (int k = 0; k < 4; ++k) r[k] = k < cbn ? q.rbest[((size_t)p * q.CB + k) * m + i] : make_float2(-INFINITY, 0.f);
         float bv = r[0].x;
         int bj = __float_as_int(r[0].y);
 #pragma unroll
         for (int k = 1; k < 4; ++k)
-            if (k < q.CB && r[k].x > bv) bv = r[k].x, bj = __float_as_int(r[k].y);
-        js[i] = min(max(bj, 0), n - 1);
+            if (k < cbn && r[k].x > bv) bv = r[k].x, bj = __float_as_int(r[k].y);
+        js[i] = min(max(bj, 0), nl - 1);
         sc[i] = bv;
     }
-    for (int j = tid; j < n; j += 1024) {
+    for (int j = tid; j < nl; j += 1024) {
         float bv = -INFINITY;
         int bi = 0;
-        for (int k0 = 0; k0 < q.RB; k0 += 8) {
+        for (int k0 = 0; k0 < rbn; k0 += 8) {
             float2 c[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                c[k] = k0 + k < q.RB ? q.cbest[((size_t)p * q.RB + k0 + k) * n + j] : make_float2(-INFINITY, 0.f);
+                c[k] = k0 + k < rbn ? q.cbest[((size_t)p * q.RB + k0 + k) * n + j] : make_float2(-INFINITY, 0.f);
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                if (k0 + k < q.RB && c[k].x > bv) bv = c[k].x, bi = __float_as_int(c[k].y);
+                if (k0 + k < rbn && c[k].x > bv) bv = c[k].x, bi = __float_as_int(c[k].y);
         }
-        is[j] = min(max(bi, 0), m - 1);
+        is[j] = min(max(bi, 0), ml - 1);
     }
     __syncthreads();
     // the row side; a thread owns rows 2 tid and 2 tid + 1, so the list keeps ascending i
@@ -2109,6 +2139,11 @@ __global__ __launch_bounds__(1024) void assign_finish_kernel(AmArgs q) {
     for (int k = 0; k < 2; ++k) {
         const int i = 2 * tid + k;
         if (i >= m) continue;
+        if (i >= ml) {  // (ragged) a padded row: no match
+            q.m0[(size_t)p * m + i] = -1;
+            q.s0[(size_t)p * m + i] = 0.f;
+            continue;
+        }
         jj[k] = js[i];
         const bool mutual = is[jj[k]] == i;
         ms[k] = mutual ? expf(sc[i]) : 0.f;
@@ -2128,6 +2163,11 @@ __global__ __launch_bounds__(1024) void assign_finish_kernel(AmArgs q) {
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();  // (also: sc and vld of every row written)
     for (int j = tid; j < n; j += 1024) {
+        if (j >= nl) {  // (ragged) a padded column: no match
+            q.s1[(size_t)p * n + j] = 0.f;
+            q.m1[(size_t)p * n + j] = -1;
+            continue;
+        }
         const int i = is[j];
         const bool mutual = js[i] == j;
         q.s1[(size_t)p * n + j] = mutual ? sc[i] : 0.f;
@@ -2520,28 +2560,34 @@ size_t lg_assign_matches_workspace(int32_t m, int32_t n, int32_t batch) {
     return lg_assign_scores_workspace(m, n, batch) + up256(b * cb * m * 8) + up256(b * rb * n * 8);
 }
 
-int32_t lg_assign_matches(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
-                          float threshold, int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1,
-                          int32_t* matches, float* mscores, int32_t* counts, void* workspace, hipStream_t stream) {
+namespace {
+// lg_assign_matches and lg_assign_matches_lens (m_len / n_len: device tables of per-pair valid counts, or
+// null = all m / n; `who` names the entry point in errors)
+int32_t assign_matches_run(const char* who, const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n,
+                           int32_t batch, const int32_t* m_len, const int32_t* n_len, float threshold, int32_t* matches0,
+                           int32_t* matches1, float* mscores0, float* mscores1, int32_t* matches, float* mscores,
+                           int32_t* counts, void* workspace, hipStream_t stream) {
     auto aligned4 = [](const void* p) { return ((uintptr_t)p & 3) == 0; };
     const bool work = m > 0 && n > 0 && batch > 0;
     if (m < 0 || n < 0 || batch < 0 || m > 2048 || n > 2048 || n % 8 != 0 || ld < 256 || ld % 8 != 0 || zc < 256 ||
-        zc >= ld || pair_stride < (int64_t)(m + n) * ld || !(threshold >= 0.f) || !aligned4(counts) ||
+        zc >= ld || pair_stride < (int64_t)(m + n) * ld || !(threshold >= 0.f) || !aligned4(counts) || !aligned4(m_len) ||
+        !aligned4(n_len) ||
         (work && (!v || !workspace || !aligned16(v) || !aligned16(workspace) || !matches0 || !matches1 || !mscores0 ||
                   !mscores1 || !matches || !mscores || !counts || !aligned4(matches0) || !aligned4(matches1) ||
                   !aligned4(mscores0) || !aligned4(mscores1) || !aligned4(matches) || !aligned4(mscores))))
-        return bad("lg_assign_matches");
+        return bad(who);
     if (batch == 0) return MHA_HD64_STATUS_SUCCESS;
     if (m == 0 || n == 0) {  // no rows or no columns: no match in any pair
         if (!counts) return MHA_HD64_STATUS_SUCCESS;
         const hipError_t e = hipMemsetAsync(counts, 0, (size_t)batch * 4, stream);
         return e == hipSuccess ? MHA_HD64_STATUS_SUCCESS
-                               : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, "lg_assign_matches", hipGetErrorString(e));
+                               : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, who, hipGetErrorString(e));
     }
     AmArgs q{};
     AsArgs& a = q.a;
     a.v = (const f16*)v, a.ps = (long)pair_stride, a.ld = ld, a.zc = zc, a.m = m, a.n = n, a.rb0 = (m + 31) / 32;
     a.S = assign_splits(m, n, batch);
+    a.mlen = m_len, a.nlen = n_len;
     assign_layout(a, (char*)workspace, batch);
     q.RB = (m + 31) / 32, q.CB = (n + 511) / 512, q.K = m < n ? m : n, q.thr = threshold;
     q.rbest = (float2*)((char*)workspace + lg_assign_scores_workspace(m, n, batch));
@@ -2552,20 +2598,40 @@ int32_t lg_assign_matches(const void* v, int64_t pair_stride, int32_t ld, int32_
     hipLaunchKernelGGL(assign_finish_kernel, dim3(batch), dim3(1024), 0, stream, q);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MHA_HD64_STATUS_SUCCESS
-                           : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, "lg_assign_matches", hipGetErrorString(e));
+                           : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, who, hipGetErrorString(e));
+}
+}  // namespace
+
+int32_t lg_assign_matches(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
+                          float threshold, int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1,
+                          int32_t* matches, float* mscores, int32_t* counts, void* workspace, hipStream_t stream) {
+    return assign_matches_run("lg_assign_matches", v, pair_stride, ld, zc, m, n, batch, nullptr, nullptr, threshold, matches0,
+                              matches1, mscores0, mscores1, matches, mscores, counts, workspace, stream);
 }
 
-int32_t lg_assign_scores(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
-                         float* scores, void* workspace, hipStream_t stream) {
-    if (m < 0 || n < 0 || batch < 0 || m > 2048 || n > 2048 || n % 8 != 0 || ld < 256 || ld % 8 != 0 || zc < 256 ||
+int32_t lg_assign_matches_lens(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n,
+                               int32_t batch, const int32_t* m_len, const int32_t* n_len, float threshold,
+                               int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1, int32_t* matches,
+                               float* mscores, int32_t* counts, void* workspace, hipStream_t stream) {
+    return assign_matches_run("lg_assign_matches_lens", v, pair_stride, ld, zc, m, n, batch, m_len, n_len, threshold,
+                              matches0, matches1, mscores0, mscores1, matches, mscores, counts, workspace, stream);
+}
+
+namespace {
+int32_t assign_scores_run(const char* who, const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n,
+                          int32_t batch, const int32_t* m_len, const int32_t* n_len, float* scores, void* workspace,
+                          hipStream_t stream) {
+    if (((uintptr_t)m_len & 3) || ((uintptr_t)n_len & 3) ||
+        m < 0 || n < 0 || batch < 0 || m > 2048 || n > 2048 || n % 8 != 0 || ld < 256 || ld % 8 != 0 || zc < 256 ||
         zc >= ld || pair_stride < (int64_t)(m + n) * ld ||
         ((m > 0 && n > 0 && batch > 0) && (!v || !scores || !workspace || !aligned16(v) || !aligned16(scores) ||
                                           !aligned16(workspace))))
-        return bad("lg_assign_scores");
+        return bad(who);
     if (m == 0 || n == 0 || batch == 0) return MHA_HD64_STATUS_SUCCESS;
     AsArgs a{};
     a.v = (const f16*)v, a.ps = (long)pair_stride, a.ld = ld, a.zc = zc, a.m = m, a.n = n, a.rb0 = (m + 31) / 32;
     a.S = assign_splits(m, n, batch);
+    a.mlen = m_len, a.nlen = n_len;
     assign_layout(a, (char*)workspace, batch);
     a.scores = scores;
     launch_assign_lse(a, batch, stream);
@@ -2578,7 +2644,21 @@ int32_t lg_assign_scores(const void* v, int64_t pair_stride, int32_t ld, int32_t
         hipLaunchKernelGGL(assign_combine_kernel<1>, dim3((m + 7) / 8, cb, batch), dim3(256), 0, stream, a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MHA_HD64_STATUS_SUCCESS
-                           : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, "lg_assign_scores", hipGetErrorString(e));
+                           : mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, who, hipGetErrorString(e));
+}
+}  // namespace
+
+int32_t lg_assign_scores(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
+                         float* scores, void* workspace, hipStream_t stream) {
+    return assign_scores_run("lg_assign_scores", v, pair_stride, ld, zc, m, n, batch, nullptr, nullptr, scores, workspace,
+                             stream);
+}
+
+int32_t lg_assign_scores_lens(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
+                              const int32_t* m_len, const int32_t* n_len, float* scores, void* workspace,
+                              hipStream_t stream) {
+    return assign_scores_run("lg_assign_scores_lens", v, pair_stride, ld, zc, m, n, batch, m_len, n_len, scores, workspace,
+                             stream);
 }
 
 int32_t lg_linear_qkv_rotary(const void* x, const void* w_perm, const void* b_perm, const void* cosv,

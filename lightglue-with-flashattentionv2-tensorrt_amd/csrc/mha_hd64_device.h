@@ -43,7 +43,7 @@ struct CallArgs {
     int qtiles;       // query blocks per (batch, head)
     int bh;           // batch * heads
     int block_begin;  // first block (in XCD-remapped order j) of this call
-    int pad_;
+    int heads;        // (read by the streaming kernel's per-item key counts only: item -> batch index)
 };
 struct FwdArgs {
     CallArgs c[kMaxCalls];
@@ -53,6 +53,13 @@ struct FwdArgs {
     // In-launch combine (non-null): one arrival ticket per query group, indexed by the group's
     // first block j; zero between launches (the last arriver resets its ticket).
     unsigned* tickets;
+    // Per-item key counts (the streaming kernel's lens form only; last, so every other kernel's
+    // kernarg offsets stay): lens[i] = call i's [batch] int32 table, or null = every item nkv keys.
+    const int* lens[kMaxCalls];
+    // The same for query rows: qlens[i] = call i's [batch] int32 table of real query rows, or null =
+    // all nq. Rows at or past it are padding: zeroed on load and written as NaN, so that no decision
+    // a wave takes for its 32 queries together (the lazy rescale) can depend on what they hold.
+    const int* qlens[kMaxCalls];
 };
 
 // Single-pass kernel (mha_hd64_direct.hip): 8 waves x tiles_per_wave 64-key tiles per 32-row block.
@@ -64,7 +71,8 @@ hipError_t launch_direct16(const FwdArgs& a, int grid, int tiles_per_wave, bool 
 // Persistent streaming kernel (mha_hd64_stream.hip): 128-row items, all keys, fp16 Q/K/V;
 // a.total_blocks = items (128-row blocks of every call, qtiles per call of 128 rows).
 // waves = 4 (128-row items, two workgroups per CU) or 8 (256-row items, one per CU).
-hipError_t launch_stream(const FwdArgs& a, int waves, bool out_f32, hipStream_t stream);
+// lens: the form that takes each item's key count from a.lens (mha_hd64_launch_grouped_lens).
+hipError_t launch_stream(const FwdArgs& a, int waves, bool out_f32, hipStream_t stream, bool lens = false);
 int stream_grid(int items, int waves);
 
 namespace {

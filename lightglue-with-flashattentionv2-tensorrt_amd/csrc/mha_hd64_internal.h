@@ -64,9 +64,13 @@ constexpr int kForceDirect16 = 22;
 constexpr int kForceStream = 23;
 GroupPlan plan_group(const Call* calls, int n, size_t ws_bytes, int force_q_waves = 0, int force_kv_waves = 0,
                      int force_splits = 0, InType in = InType::F16);
+// lens (non-null only with force_q_waves = kForceStream and fp16 inputs): lens[i] is a device table of
+// calls[i].batch int32 key counts, or null; item b of call i attends to its first lens[i][b] keys
+// (clamped into [1, nkv] in the kernel). qlens (with lens only; may be null): the same for query rows
+// (qlens[i][b] real rows of item b; the rows past it are written as NaN and influence no other row).
 hipError_t launch_group(const Call* calls, int n, InType in, OutType out, void* workspace, size_t ws_bytes,
                         hipStream_t stream, int force_q_waves = 0, int force_kv_waves = 0, int force_splits = 0,
-                        int phase_mask = 3);
+                        int phase_mask = 3, const int* const* lens = nullptr, const int* const* qlens = nullptr);
 // Workspace bytes launch_group can use for these calls with inputs of type `in`: the largest
 // chunk's need (chunks of kGroupCalls reuse the workspace in stream order) -- split partials, or
 // for fp32 inputs the fp16 copies the convert launch writes when a single-pass kernel runs them.

@@ -1315,7 +1315,8 @@ int set_stream_mode(int mode) {
 
 static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutType out, void* workspace,
                                      size_t ws_bytes, hipStream_t stream, int force_q_waves, int force_kv_waves,
-                                     int force_splits, int phase_mask);
+                                     int force_splits, int phase_mask, const int* const* lens = nullptr,
+                                     const int* const* qlens = nullptr);
 
 // Whether an fp32-input launch whose fp16 plan is p16 takes the convert launch + that fp16 kernel
 // (true) or the ring kernel rounding fp32 on load (false). The 32-row single-pass kernel after a
@@ -1376,9 +1377,10 @@ static hipError_t launch_f32_via_f16(const Call* calls, int n, OutType out, void
     return launch_group_chunk(c16, n, InType::F16, out, nullptr, 0, stream, 0, 0, 0, phase_mask);
 }
 
+// lens (the streaming kernel's per-item key counts, launch_group's comment): lens[i] belongs to calls[i]
 static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutType out, void* workspace,
                                      size_t ws_bytes, hipStream_t stream, int force_q_waves, int force_kv_waves,
-                                     int force_splits, int phase_mask) {
+                                     int force_splits, int phase_mask, const int* const* lens, const int* const* qlens) {
     bool in32_direct = false;  // fp32 inputs into the 16-row kernel's one-pass forms
     GroupPlan p{};
     if (in == InType::F32 && force_q_waves == 0 && force_kv_waves == 0 && force_splits == 0) {
@@ -1415,6 +1417,9 @@ static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutTyp
         ca.splits = p.splits[i];
         ca.tiles_per_split = p.tiles_per_split[i];
         ca.bh = c.batch * c.heads;
+        ca.heads = c.heads;
+        a.lens[n_live] = lens ? lens[i] : nullptr;
+        a.qlens[n_live] = lens && qlens ? qlens[i] : nullptr;
         const int block_m = p.rows_per_wave == 16 ? 16 : 32 * p.q_waves * (p.rows_per_wave / 32);
         ca.qtiles = (c.nq + block_m - 1) / block_m;
         ca.block_begin = blocks;
@@ -1442,8 +1447,9 @@ static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutTyp
     if (p.stream) {  // persistent streaming kernel: no split, no workspace
         g_last_combine = 0;
         if (!(phase_mask & 1)) return hipSuccess;
-        return launch_stream(a, p.q_waves, out == OutType::F32, stream);
+        return launch_stream(a, p.q_waves, out == OutType::F32, stream, lens != nullptr);
     }
+    if (lens) return hipErrorInvalidValue;  // (only the streaming kernel takes key counts)
     if (p.direct_tiles > 0) {  // single-pass kernel: no split, no workspace
         g_last_combine = 0;
         if (!(phase_mask & 1)) return hipSuccess;
@@ -1503,11 +1509,12 @@ static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutTyp
 
 hipError_t launch_group(const Call* calls, int n, InType in, OutType out, void* workspace, size_t ws_bytes,
                         hipStream_t stream, int force_q_waves, int force_kv_waves, int force_splits,
-                        int phase_mask) {
+                        int phase_mask, const int* const* lens, const int* const* qlens) {
     // Chunks of kMaxCalls calls share one launch; each chunk reuses the workspace (stream order).
     for (int i = 0; i < n; i += kMaxCalls) {
         const hipError_t e = launch_group_chunk(calls + i, std::min(kMaxCalls, n - i), in, out, workspace, ws_bytes,
-                                                stream, force_q_waves, force_kv_waves, force_splits, phase_mask);
+                                                stream, force_q_waves, force_kv_waves, force_splits, phase_mask,
+                                                lens ? lens + i : nullptr, qlens ? qlens + i : nullptr);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

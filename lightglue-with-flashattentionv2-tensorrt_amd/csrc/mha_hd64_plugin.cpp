@@ -352,6 +352,58 @@ int32_t mha_hd64_launch_grouped(const mha_hd64_call_t* calls, int32_t n_calls, i
         __FILE__, __LINE__);
 }
 
+// Per-item key counts (and, optionally, query-row counts): always the streaming kernel (its lens form),
+// the wave form as the planner chooses it (waves 0) or forced (the test hook: 4 / 8); splits are 1, so no
+// workspace is used. q_lens may be null (no query row is padding), and so may any entry of either array.
+static int32_t launch_lens(const mha_hd64_call_t* calls, const int32_t* const* q_lens, const int32_t* const* kv_lens,
+                           int32_t n_calls, int32_t in_type, int32_t out_type, int32_t waves, hipStream_t stream) {
+    MHA_CHECK(in_type == MHA_HD64_DT_HALF);  // fp16 inputs only
+    MHA_CHECK(out_type == MHA_HD64_DT_HALF || out_type == MHA_HD64_DT_FLOAT);
+    MHA_CHECK(waves == 0 || waves == 4 || waves == 8);
+    MHA_CHECK(n_calls >= 0 && (n_calls == 0 || (calls != nullptr && kv_lens != nullptr)));
+    for (int32_t i = 0; i < n_calls; ++i) {
+        MHA_CHECK((uintptr_t)kv_lens[i] % 4 == 0);
+        MHA_CHECK(q_lens == nullptr || (uintptr_t)q_lens[i] % 4 == 0);
+    }
+    std::vector<mha_hd64::Call> v;
+    const int32_t st = to_calls(calls, n_calls, v);
+    if (st != MHA_HD64_STATUS_SUCCESS || v.empty()) return st;
+    std::vector<const int32_t*> kl, ql;  // (to_calls drops the calls with nothing to compute)
+    for (int32_t i = 0; i < n_calls; ++i)
+        if (calls[i].batch != 0 && calls[i].heads != 0 && calls[i].nq != 0) {
+            kl.push_back(kv_lens[i]);
+            ql.push_back(q_lens ? q_lens[i] : nullptr);
+        }
+    return launch_status(
+        mha_hd64::launch_group(v.data(), (int)v.size(), mha_hd64::InType::F16,
+                               out_type == MHA_HD64_DT_HALF ? mha_hd64::OutType::F16 : mha_hd64::OutType::F32, nullptr, 0,
+                               stream, mha_hd64::kForceStream, waves, 0, 3, kl.data(), ql.data()),
+        __FILE__, __LINE__);
+}
+
+int32_t mha_hd64_launch_grouped_lens(const mha_hd64_call_t* calls, const int32_t* const* kv_lens, int32_t n_calls,
+                                     int32_t in_type, int32_t out_type, void* workspace, size_t ws_bytes,
+                                     hipStream_t stream) {
+    (void)workspace, (void)ws_bytes;  // (no split: unused, may be NULL)
+    return launch_lens(calls, nullptr, kv_lens, n_calls, in_type, out_type, 0, stream);
+}
+
+int32_t mha_hd64_launch_grouped_qkv_lens(const mha_hd64_call_t* calls, const int32_t* const* q_lens,
+                                         const int32_t* const* kv_lens, int32_t n_calls, int32_t in_type,
+                                         int32_t out_type, void* workspace, size_t ws_bytes, hipStream_t stream) {
+    (void)workspace, (void)ws_bytes;
+    return launch_lens(calls, q_lens, kv_lens, n_calls, in_type, out_type, 0, stream);
+}
+
+// Test hook: one call through the lens form with a pinned wave form.
+int32_t mha_hd64_launch_stream_lens(const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t heads,
+                                    int32_t nq, int32_t nkv, const int32_t* kv_len, int32_t out_f32, int32_t waves,
+                                    hipStream_t stream) {
+    const mha_hd64_call_t c{q, k, v, o, batch, heads, nq, nkv};
+    return launch_lens(&c, nullptr, &kv_len, 1, MHA_HD64_DT_HALF, out_f32 ? MHA_HD64_DT_FLOAT : MHA_HD64_DT_HALF, waves,
+                       stream);
+}
+
 size_t mha_hd64_grouped_workspace_bytes(const mha_hd64_call_t* calls, int32_t n_calls) {
     return mha_hd64_grouped_workspace_bytes_typed(calls, n_calls, MHA_HD64_DT_HALF);
 }

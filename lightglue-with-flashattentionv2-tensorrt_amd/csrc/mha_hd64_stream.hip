@@ -148,6 +148,14 @@ struct StreamItem {
     int q0;  // first query row of the block
     int nt;  // 64-key tiles, rounded up to an even count (the padding tile reads zeros, masked)
 };
+// lens form: an item's counts as the tables hold them (raw: clamped where they are first used, an item
+// after the scalar loads). Kept beside StreamItem, not in it, so that the form without counts has the
+// state, and the instruction stream, it had before this form existed.
+struct StreamLens {
+    int len;   // keys (raw)
+    int cap;   // the call's nkv
+    int qlen;  // real query rows (raw; rows at or past it are padding; a null table: all)
+};
 // The loader's cursor: K/V descriptors of the item whose tiles it issues, its next local tile, its
 // tile count and its index. It runs `lead` tiles ahead of the compute side, across item seams
 // (over several short items if need be).
@@ -157,6 +165,28 @@ struct StreamLoader {
 };
 
 __device__ __forceinline__ int stream_tiles(int nkv) { return ((nkv + 2 * kTileKV - 1) / (2 * kTileKV)) * 2; }
+
+// The lens form (mha_hd64_launch_grouped_lens): item (call ci, batch·head bh) attends to the first
+// lens[ci][bh / heads] keys of its [nkv, 64] K/V slab. The count is one scalar load (the table is
+// read through the constant address space: a uniform address there is always a scalar load), issued
+// an item ahead by the compute side (nxt) and by the loader (its next item's count): the raw value
+// is clamped into [1, nkv] only where it is first used (stream_clamp), so the load's latency lies
+// under an item's steps. A null table: every item of the call has nkv keys.
+typedef const __attribute__((address_space(4))) int* stream_lens_t;
+// (tab: a.lens, or a.qlens for the query rows' counts; dflt: the value of a null table)
+template <bool MULTI>
+__device__ __forceinline__ int stream_len_raw(const FwdArgs& a, const int* const (&tab)[kMaxCalls], int ci, int bh, int dflt) {
+    const int* lp = tab[0];
+    if constexpr (MULTI) {
+#pragma unroll
+        for (int i = 1; i < kMaxCalls; ++i)
+            if (ci == i) lp = tab[i];
+    }
+    int len = dflt;
+    if (lp) len = ((stream_lens_t)(uintptr_t)lp)[__builtin_amdgcn_readfirstlane(bh / MHA_SEL(heads))];
+    return len;
+}
+__device__ __forceinline__ int stream_clamp(int len, int nkv) { return min(max(len, 1), nkv); }
 
 template <bool MULTI, int OSZ, int NW>
 __device__ __forceinline__ StreamItem stream_item(const FwdArgs& a, int j, bool live) {
@@ -184,12 +214,39 @@ __device__ __forceinline__ StreamItem stream_item(const FwdArgs& a, int j, bool 
     it.nt = stream_tiles(nkv);
     return it;
 }
-
+// lens form: item j's counts (two scalar loads, issued here, waited for at stream_settle)
 template <bool MULTI>
-__device__ __forceinline__ StreamLoader stream_kv(const FwdArgs& a, int j, bool live) {
+__device__ __forceinline__ StreamLens stream_lens(const FwdArgs& a, int j) {
+    const int ci = stream_call<MULTI>(a, j);
+    const int nkv = MHA_SEL(nkv);
+    const int bh = (j - MHA_SEL(block_begin)) / MHA_SEL(qtiles);
+    StreamLens ln;
+    ln.len = stream_len_raw<MULTI>(a, a.lens, ci, bh, nkv);
+    ln.cap = nkv;
+    ln.qlen = stream_len_raw<MULTI>(a, a.qlens, ci, bh, 0x7fffffff);
+    return ln;
+}
+// lens form: the item's key count and tile count from the raw table value, at its first use
+__device__ __forceinline__ void stream_settle(StreamItem& it, const StreamLens& ln) {
+    it.nkv = stream_clamp(ln.len, ln.cap);
+    it.nt = stream_tiles(it.nkv);
+}
+
+// Item j's key count for the loader, raw (lens form)
+template <bool MULTI>
+__device__ __forceinline__ int stream_kv_len(const FwdArgs& a, int j) {
+    const int ci = stream_call<MULTI>(a, j);
+    return stream_len_raw<MULTI>(a, a.lens, ci, (j - MHA_SEL(block_begin)) / MHA_SEL(qtiles), MHA_SEL(nkv));
+}
+
+// len_raw (lens form only): the item's raw key count; its K/V descriptors end at that key, so no
+// key at or past it is ever read (the strides stay nkv)
+template <bool MULTI, bool LENS>
+__device__ __forceinline__ StreamLoader stream_kv(const FwdArgs& a, int j, bool live, int len_raw) {
     const int ci = stream_call<MULTI>(a, j);
     const int nkv = MHA_SEL(nkv), qtiles = MHA_SEL(qtiles);
     const int bh = (j - MHA_SEL(block_begin)) / qtiles;
+    const int len = LENS ? stream_clamp(len_raw, nkv) : nkv;
 #ifdef MHA_STREAM_L2KV  // diagnostic: every item streams the first head's K/V (L2-resident)
     const int bhk = 0;
 #else
@@ -199,11 +256,11 @@ __device__ __forceinline__ StreamLoader stream_kv(const FwdArgs& a, int j, bool 
     const char* v = reinterpret_cast<const char*>(MHA_SEL(v)) + (size_t)bhk * nkv * (kHeadDim * 2);
     StreamLoader ld;
     // (past the workgroup's last item: empty descriptors, zeros into the ring, forever)
-    const unsigned kvb = live ? (unsigned)nkv * kHeadDim * 2 : 0u;
+    const unsigned kvb = live ? (unsigned)len * kHeadDim * 2 : 0u;
     ld.k = stream_rsrc(k, kvb);
     ld.v = stream_rsrc(v, kvb);
     ld.lt = 0;
-    ld.nt = live ? stream_tiles(nkv) : (1 << 30);
+    ld.nt = live ? stream_tiles(len) : (1 << 30);
     ld.j = j;
     return ld;
 }
@@ -221,6 +278,24 @@ __device__ __forceinline__ f16x8 stream_scale_q(f16x8 raw) {
             : "=&v"(outv[w])
             : "v"(in[w]), "v"(sc));
     return __builtin_bit_cast(f16x8, outv);
+}
+
+// lens form: the wave's query rows nv .. 31 are padding (nv: wave-uniform, the item's real rows left
+// at this wave's first; >= 32: none). They are handled as non-finite query rows are (q_nonfinite_fix):
+// Q fragments zeroed, so their scores are 0 whatever they held and they move no running max and take
+// no part in the wave's rescale decisions; their bits join the mask qm, so their output rows are NaN.
+template <bool LENS>
+__device__ __forceinline__ unsigned stream_pad_q(f16x8 (&q)[4], unsigned qm, int nv) {
+    if constexpr (LENS) {
+        if (nv < 32) {  // (wave-uniform)
+            const unsigned pm = nv <= 0 ? ~0u : (~0u << nv);
+            const bool pad = (pm >> (__lane_id() & 31)) & 1u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) q[i] = pad ? f16x8{} : q[i];
+            qm |= pm;
+        }
+    }
+    return qm;
 }
 
 typedef f16 f16x2 __attribute__((ext_vector_type(2)));
@@ -251,7 +326,9 @@ struct StreamScores {
 #define MHA_STREAM_SPEC 0
 #endif
 
-template <typename TOut, bool MULTI, int NW>
+// LENS: per-item key counts from a.lens (a form of its own: the instantiations without it compile
+// to the instruction streams they had before it existed).
+template <typename TOut, bool MULTI, int NW, bool LENS = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kernel(FwdArgs a) {
     constexpr int OSZ = (int)sizeof(TOut);
     constexpr int kPW = 8 / NW;  // DMA pieces (1 KiB, 8 rows) per wave of each 8 KiB K or V image
@@ -319,7 +396,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
     // The loader's K and V pieces of its current tile into ring slot `slot` (pieces wave + NW·h of
     // each image, 8 KiB apart per image), then its cursor moves on (past an item's last tile: the
     // workgroup's next item, or an empty one past the last)
-    StreamLoader ld = stream_kv<MULTI>(a, j, true);
+    // (lens form: ld_len is the raw count of the loader's NEXT item, loaded when it took its
+    // current one; an index past the workgroup's last item stays on that item)
+    StreamLoader ld = stream_kv<MULTI, LENS>(a, j, true, LENS ? stream_kv_len<MULTI>(a, j) : 0);
+    int ld_len = 0;
+    if constexpr (LENS) ld_len = stream_kv_len<MULTI>(a, j + G < je ? j + G : j);
     auto issue_tile = [&](unsigned slot) {
         const unsigned m = m0w + slot * (unsigned)kSSlot;
         const unsigned so = (unsigned)ld.lt * (unsigned)kTileBytes + sow;
@@ -333,8 +414,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
     auto ld_advance = [&]() {
         if (++ld.lt >= ld.nt) {  // (wave-uniform, once per item)
             const int jn = ld.j + G;
-            ld = stream_kv<MULTI>(a, jn < je ? jn : ld.j, jn < je);
+            const int jc = jn < je ? jn : ld.j;
+            ld = stream_kv<MULTI, LENS>(a, jc, jn < je, ld_len);
             ld.j = jn;
+            if constexpr (LENS) ld_len = stream_kv_len<MULTI>(a, jn + G < je ? jn + G : jc);
         }
     };
     // this wave's 32 Q rows of an item into its part of the Q region
@@ -348,6 +431,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
     // ---- state ----
     StreamItem cur = stream_item<MULTI, OSZ, NW>(a, j, true);
     StreamItem nxt = stream_item<MULTI, OSZ, NW>(a, j + G < je ? j + G : j, j + G < je);
+    StreamLens curL = {}, nxtL = {};  // (lens form only)
+    if constexpr (LENS) {
+        curL = stream_lens<MULTI>(a, j);
+        stream_settle(cur, curL);
+        nxtL = stream_lens<MULTI>(a, j + G < je ? j + G : j);
+    }
     unsigned gb = 0;  // global tile index of the current item's tile 0 (ring slot = index & kSM)
     f16x8 qf[4];
     f32x16 cm;                  // −m (the QKᵀ chains' C operand)
@@ -637,7 +726,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         asm volatile("" : "+v"(pn[0][0]), "+v"(pn[0][1]), "+v"(pn[1][0]), "+v"(pn[1][1]));
         SEG(SB + 1);
         if constexpr (MASK) {  // LAST: the next item's tile 0 (keys past its nkv)
-            const int lim = LAST ? nxt.nkv : cur.nkv - kTileKV * (t + 1);  // keys of tile t + 1 (<= 0: none)
+            // keys of tile t + 1 (<= 0: none); (lens form: nxt still holds its raw count)
+            const int lim = LAST ? (LENS ? stream_clamp(nxtL.len, nxtL.cap) : nxt.nkv) : cur.nkv - kTileKV * (t + 1);
             if (lim < kTileKV) {  // (wave-uniform, rare: a partial or padding tile)
                 asm volatile("" ::: "memory");
                 mask_tile(n, lim);
@@ -690,6 +780,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
     using K5 = std::integral_constant<int, 5>;
     // Q fragments of an item's rows from the Q region (this wave's own rows: its own DMA, waited at
     // a step's end), scaled; the mask of non-finite query rows
+    // (lens form: the item's padded query rows join that mask, stream_pad_q)
     auto read_q = [&]() -> unsigned {
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = stream_scale_q(lds_read16(lds, q_base + k_addr[s]));
@@ -697,6 +788,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
     };
     // the first item's tile 0 (C = 0) and its exact row max, as a LAST step does for the others
     unsigned qbad = read_q();
+    if constexpr (LENS) qbad = stream_pad_q<LENS>(qf, qbad, curL.qlen - (cur.q0 + 32 * wave));
     {
         f16x8 k0[8];
 #pragma unroll
@@ -760,7 +852,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         // epilogue follow in the next item's FIRST step
         SEG(14);
         if (NW == 8 && nt == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned qbad_next = read_q();
+        unsigned qbad_next = read_q();
+        if constexpr (LENS) qbad_next = stream_pad_q<LENS>(qf, qbad_next, nxtL.qlen - (nxt.q0 + 32 * wave));
         SEG(15);
         step(K3{}, t, sB, sA, pA, pB);
 #ifdef MHA_STREAM_STAMPS
@@ -782,6 +875,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         qbad = qbad_next;
         const bool more = j + G < je;
         nxt = stream_item<MULTI, OSZ, NW>(a, more ? j + G : j, more);
+        if constexpr (LENS) {
+            curL = nxtL;
+            stream_settle(cur, curL);
+            nxtL = stream_lens<MULTI>(a, more ? j + G : j);
+        }
     }
     // SPEC's rare path: this wave's 32 rows of item jj, exactly — a running max per 64-key tile (exact
     // online softmax, rescale at every move) on the step's MFMA forms and fragment reads. Runs after
@@ -794,8 +892,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
     const unsigned xs_base = (unsigned)wave * (unsigned)kSSlot;
     const unsigned xs_m0 = (unsigned)__builtin_amdgcn_readfirstlane(lds0 + xs_base);
     auto exact_item = [&](int jj) {
-        const StreamItem it = stream_item<MULTI, OSZ, NW>(a, jj, true);
-        const StreamLoader kv = stream_kv<MULTI>(a, jj, true);
+        StreamItem it = stream_item<MULTI, OSZ, NW>(a, jj, true);
+        StreamLens itL = {};
+        if constexpr (LENS) {
+            itL = stream_lens<MULTI>(a, jj);
+            stream_settle(it, itL);
+        }
+        const StreamLoader kv = stream_kv<MULTI, LENS>(a, jj, true, it.nkv);
         auto load_tile = [&](int t) {  // pieces p = rows 8p..8p+7 of K and V (swizzles as issue_tile)
             const unsigned so = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(t * kTileBytes));
 #pragma unroll
@@ -810,7 +913,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         for (int s = 0; s < 4; ++s)
             qf[s] = stream_scale_q(__builtin_bit_cast(
                 f16x8, __builtin_amdgcn_raw_buffer_load_b128(it.q, qrow * 128u + (unsigned)(2 * s + hh) * 16u, 0, 0)));
-        const unsigned qb = q_nonfinite_fix(qf);
+        const unsigned qb = stream_pad_q<LENS>(qf, q_nonfinite_fix(qf), LENS ? itL.qlen - (it.q0 + 32 * wave) : 32);
         float m = -INFINITY, l = 0.f;
         o0 = f32x16{};
         o1 = f32x16{};
@@ -914,12 +1017,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
 }
 #undef MHA_SEL
 
-template <typename TOut, int NW>
+template <typename TOut, int NW, bool LENS = false>
 hipError_t launch_stream_t(const FwdArgs& a, int grid, hipStream_t stream) {
     if (a.n_calls > 1)
-        hipLaunchKernelGGL((mha_hd64_stream_kernel<TOut, true, NW>), dim3(grid), dim3(64 * NW), 0, stream, a);
+        hipLaunchKernelGGL((mha_hd64_stream_kernel<TOut, true, NW, LENS>), dim3(grid), dim3(64 * NW), 0, stream, a);
     else
-        hipLaunchKernelGGL((mha_hd64_stream_kernel<TOut, false, NW>), dim3(grid), dim3(64 * NW), 0, stream, a);
+        hipLaunchKernelGGL((mha_hd64_stream_kernel<TOut, false, NW, LENS>), dim3(grid), dim3(64 * NW), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -931,9 +1034,14 @@ int stream_grid(int items, int waves) {
 }
 
 // waves: 4 (128-row items) or 8 (256-row items); a.total_blocks counts items of that size
-hipError_t launch_stream(const FwdArgs& a, int waves, bool out_f32, hipStream_t stream) {
+hipError_t launch_stream(const FwdArgs& a, int waves, bool out_f32, hipStream_t stream, bool lens) {
     const int grid = stream_grid(a.total_blocks, waves);
     if (grid <= 0) return hipSuccess;
+    if (lens) {
+        if (waves == 8)
+            return out_f32 ? launch_stream_t<float, 8, true>(a, grid, stream) : launch_stream_t<f16, 8, true>(a, grid, stream);
+        return out_f32 ? launch_stream_t<float, 4, true>(a, grid, stream) : launch_stream_t<f16, 4, true>(a, grid, stream);
+    }
     if (waves == 8) return out_f32 ? launch_stream_t<float, 8>(a, grid, stream) : launch_stream_t<f16, 8>(a, grid, stream);
     return out_f32 ? launch_stream_t<float, 4>(a, grid, stream) : launch_stream_t<f16, 4>(a, grid, stream);
 }

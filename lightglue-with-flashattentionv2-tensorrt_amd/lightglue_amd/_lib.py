@@ -117,6 +117,9 @@ SIGNATURES = {
     "mha_hd64_launch_grouped": ([ctypes.POINTER(CallDesc), _I, _I, _I, _P, _S, _P], _I),
     "mha_hd64_grouped_workspace_bytes": ([ctypes.POINTER(CallDesc), _I], _S),
     "mha_hd64_grouped_workspace_bytes_typed": ([ctypes.POINTER(CallDesc), _I, _I], _S),
+    "mha_hd64_launch_grouped_lens": ([ctypes.POINTER(CallDesc), ctypes.POINTER(_P), _I, _I, _I, _P, _S, _P], _I),
+    "mha_hd64_launch_grouped_qkv_lens": ([ctypes.POINTER(CallDesc), ctypes.POINTER(_P), ctypes.POINTER(_P), _I, _I, _I, _P,
+                                          _S, _P], _I),
     "mha_hd64_set_concurrency_hint": ([_I], _I),
     "mha_hd64_last_error": ([], _C),
     "mha_hd64_set_abort_on_error": ([_I], None),
@@ -139,6 +142,9 @@ SIGNATURES.update({
     "lg_assign_scores": ([_P, ctypes.c_int64, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "lg_assign_matches_workspace": ([_I, _I, _I], _S),
     "lg_assign_matches": ([_P, ctypes.c_int64, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "lg_assign_scores_lens": ([_P, ctypes.c_int64, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "lg_assign_matches_lens": ([_P, ctypes.c_int64, _I, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P,
+                                _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),
@@ -160,6 +166,7 @@ SIGNATURES.update({
     "mha_hd64_set_stream_mode": ([_I], _I),
     # test and benchmark hooks (include/mha_hd64.h "test and benchmark hooks")
     "mha_hd64_launch_forced": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _S, _P, _I], _I),
+    "mha_hd64_launch_stream_lens": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P], _I),
     "mha_hd64_plan": ([_I, _I, _I, _I, _S, ctypes.POINTER(ctypes.c_int32)], _S),
     "mha_hd64_set_stamp_buffer": ([_P], None),
     "mha_hd64_last_combine_form": ([], _I),

@@ -24,6 +24,10 @@ What is different, and why:
   outputs ``filter_matches`` keeps commented out, :241-252, and the compacted list): on the fp16 hip
   path from ``lg_assign_matches``, which never writes the scores tensor; elsewhere from
   ``filter_matches_dense``, the same semantics in framework ops;
+* ``forward`` / ``match_batch`` take per-pair keypoint counts (``counts0``, ``counts1``) for padded
+  batches of pairs of different sizes, and ``match_pairs`` pads a list of pairs itself: on the fp16 hip
+  path the equal-size forward's launches, with the counts as the attention's key and query-row counts
+  and the heads' lens forms (no valid row's result reads a padded row); elsewhere pair by pair;
 * ``attention=`` lets tests substitute the oracle for the kernel on CPU; the default path
   requires GPU tensors and fails loudly otherwise (no CPU fallback).
 """
@@ -257,24 +261,31 @@ class _Hip:
     _last_assign_ws = None  # (tests read the similarity copy the kernel leaves in its workspace)
 
     @staticmethod
-    def assign_scores(v, m, zc):
+    def assign_scores(v, m, zc, lens=None):
         """v [P, m + n, C] fp16: the assignment projection of both images' rows (scaled descriptors at
         channels 0..255, the matchability logit at zc) -> fp32 scores [P, m, n] (lg_assign_scores: the
-        similarity and the dual log-softmax in two launches)."""
+        similarity and the dual log-softmax in two launches). lens = (m_len, n_len), int32 [P] on the
+        device: the ragged form (lg_assign_scores_lens; -inf on padded rows and columns)."""
         pr, n, ch = v.shape[0], v.shape[1] - m, v.shape[2]
         lib = _lib.load()
         out = torch.empty((pr, m, n), dtype=torch.float32, device=v.device)
         stream = _Hip._stream(v)
         ws = _workspace(v.device, stream, lib.lg_assign_scores_workspace(m, n, pr))
         _Hip._last_assign_ws = ws
+        if lens is not None:
+            st = lib.lg_assign_scores_lens(v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, lens[0].data_ptr(),
+                                           lens[1].data_ptr(), out.data_ptr(), ws.data_ptr(), stream)
+            _check(st, "lg_assign_scores_lens")
+            return out
         st = lib.lg_assign_scores(v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, out.data_ptr(), ws.data_ptr(), stream)
         _check(st, "lg_assign_scores")
         return out
 
     @staticmethod
-    def assign_matches(v, m, zc, threshold):
+    def assign_matches(v, m, zc, threshold, lens=None):
         """v as for assign_scores -> MatchResult for all P pairs (lg_assign_matches: at most three
-        launches, no fp32 scores tensor, no framework op, no host synchronisation)."""
+        launches, no fp32 scores tensor, no framework op, no host synchronisation). lens as for
+        assign_scores (lg_assign_matches_lens: -1 / 0 on padded rows and columns)."""
         pr, n, ch = v.shape[0], v.shape[1] - m, v.shape[2]
         k = min(m, n)
         lib = _lib.load()
@@ -283,6 +294,14 @@ class _Hip:
         out = MatchResult(i32(pr, m), i32(pr, n), f32(pr, m), f32(pr, n), i32(pr, k, 2), f32(pr, k), i32(pr))
         stream = _Hip._stream(v)
         ws = _workspace(v.device, stream, lib.lg_assign_matches_workspace(m, n, pr))
+        if lens is not None:
+            st = lib.lg_assign_matches_lens(v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, lens[0].data_ptr(),
+                                            lens[1].data_ptr(), float(threshold), out.matches0.data_ptr(),
+                                            out.matches1.data_ptr(), out.scores0.data_ptr(), out.scores1.data_ptr(),
+                                            out.matches.data_ptr(), out.match_scores.data_ptr(), out.counts.data_ptr(),
+                                            ws.data_ptr(), stream)
+            _check(st, "lg_assign_matches_lens")
+            return out
         st = lib.lg_assign_matches(v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, float(threshold), out.matches0.data_ptr(),
                                    out.matches1.data_ptr(), out.scores0.data_ptr(), out.scores1.data_ptr(),
                                    out.matches.data_ptr(), out.match_scores.data_ptr(), out.counts.data_ptr(),
@@ -412,6 +431,15 @@ def _kernel_attention(calls):
             raise PluginError("LightGlueMatcher: the attention op runs on the GPU only (no CPU fallback)")
     qs, ks, vs = (list(t) for t in zip(*calls))
     return torch.ops.lightglue_amd.mha_hd64_grouped(qs, ks, vs)  # ops.py: grouped launches
+
+
+def _kernel_attention_lens(calls, q_lens, kv_lens):
+    """_kernel_attention on a ragged batch: q_lens[i] / kv_lens[i] (int32 [P] on the device) are call
+    i's real query rows and keys. Keys past the count are never read; query rows past it are written
+    as NaN and kept out of the decisions a wave takes for its 32 rows together, so a real row's bits
+    depend on no padded row."""
+    qs, ks, vs = (list(t) for t in zip(*calls))
+    return torch.ops.lightglue_amd.mha_hd64_grouped_qkv_lens(qs, ks, vs, list(q_lens), list(kv_lens))  # ops.py
 
 
 class FourierPositionalEncoding(nn.Module):
@@ -725,12 +753,95 @@ class LightGlueMatcher(nn.Module):
                 and self.posenc.Wr.weight.dtype == f16 and desc0.shape[-1] == 256 and desc1.shape[-1] == 256
                 and kpts0.shape[-1] == 2 and kpts1.shape[-1] == 2 and tuple(self.posenc.Wr.weight.shape) == (32, 2))
 
-    def forward(self, kpts0, kpts1, desc0, desc1):
-        return self._forward(kpts0, kpts1, desc0, desc1)
+    def forward(self, kpts0, kpts1, desc0, desc1, counts0=None, counts1=None):
+        """counts0 / counts1 (ragged batches): pair p's leading counts0[p] rows of image 0 and counts1[p]
+        of image 1 are real, the rest padding of any content (_ragged). Padded rows of the returned
+        descriptors are unspecified on the fast path and zero elsewhere; scores are -inf on padded rows
+        and columns."""
+        if counts0 is None and counts1 is None:
+            return self._forward(kpts0, kpts1, desc0, desc1)
+        return self._ragged(kpts0, kpts1, desc0, desc1, counts0, counts1, None)
 
-    def _forward(self, kpts0, kpts1, desc0, desc1, threshold: Optional[float] = None):
+    @staticmethod
+    def _counts(counts, pr: int, limit: int, name: str, device):
+        """One image's counts -> (host list or None, int32 [P] on `device`). Python ints or a CPU integer
+        tensor: validated here (length P, 1 <= c <= limit, else ValueError) and uploaded once from
+        pinned memory without synchronising. An int32 tensor already on `device` is taken as it is,
+        unvalidated (the kernels clamp into [1, limit]): the form to use under stream capture, where
+        new counts are written into the same tensor between replays. None: every pair has `limit`."""
+        if isinstance(counts, torch.Tensor) and counts.is_cuda:
+            if counts.dtype != torch.int32 or tuple(counts.shape) != (pr,) or counts.device != device:
+                raise ValueError(f"{name}: a device tensor of counts must be int32 [{pr}] on {device}")
+            return None, counts.contiguous()
+        if counts is None:
+            host = [limit] * pr
+        elif isinstance(counts, torch.Tensor):
+            if counts.is_floating_point() or counts.dim() != 1:
+                raise ValueError(f"{name}: expected a 1-d integer tensor")
+            host = [int(c) for c in counts.tolist()]
+        else:
+            host = [int(c) for c in counts]
+        if len(host) != pr:
+            raise ValueError(f"{name}: {len(host)} counts for {pr} pairs")
+        for c in host:
+            if not 1 <= c <= limit:
+                raise ValueError(f"{name}: count {c} outside [1, {limit}]")
+        t = torch.tensor(host, dtype=torch.int32)
+        if device.type == "cuda":
+            t = t.pin_memory().to(device, non_blocking=True)
+        return host, t
+
+    def _ragged(self, kpts0, kpts1, desc0, desc1, counts0, counts1, threshold: Optional[float]):
+        """forward (threshold None) or match_batch on a padded batch with per-pair counts. fp16 hip
+        path with the kernel attention and the chained layers (chain_ok): the equal-size forward with
+        the counts as the attention's key counts (self attention of image i: counts_i; cross i -> j:
+        counts_j) and the heads' lens forms; the same launches as an equal-size batch, no loop over
+        pairs, no host synchronisation. Row-wise kernels compute the padded rows too (wasted, harmless:
+        no valid row reads a padded one). Every other case: the pairs one at a time on their valid
+        slices through the equal-size code, the results padded (scores -inf, descriptors 0, matches
+        -1, match scores 0)."""
+        pr, m, n = desc0.shape[0], desc0.shape[1], desc1.shape[1]
+        dev = desc0.device
+        h0, c0 = self._counts(counts0, pr, m, "counts0", dev)
+        h1, c1 = self._counts(counts1, pr, n, "counts1", dev)
+        d = self.transformers[0].self_attn.Wqkv.in_features if self.n_layers else desc0.shape[-1]
+        fast = (self.glue == "hip" and self.attention is _kernel_attention and desc0.is_cuda and
+                desc0.dtype == torch.float16 and self.posenc.Wr.weight.dtype == torch.float16 and
+                self.chain_ok(desc0.new_empty((1, 0, d)), m, n))  # (x after input_proj: [.., d] in desc0's dtype)
+        if fast:
+            out = self._forward(kpts0, kpts1, desc0, desc1, threshold, lens=(c0, c1))
+            return out if threshold is None else out[2]
+        h0 = h0 if h0 is not None else c0.tolist()  # (device counts off the fast path: one synchronisation)
+        h1 = h1 if h1 is not None else c1.tolist()
+        k = min(m, n)
+        if threshold is None:
+            o0, o1 = desc0.new_zeros((pr, m, d)), desc1.new_zeros((pr, n, d))
+            sc = torch.full((pr, m, n), float("-inf"), dtype=torch.float32, device=dev)
+        else:
+            i32 = lambda *s: torch.full(s, -1, dtype=torch.int32, device=dev)      # noqa: E731
+            f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)       # noqa: E731
+            res = MatchResult(i32(pr, m), i32(pr, n), f32(pr, m), f32(pr, n), i32(pr, k, 2), f32(pr, k),
+                              torch.zeros((pr,), dtype=torch.int32, device=dev))
+        for p in range(pr):
+            a, b = h0[p], h1[p]
+            args = (kpts0[p:p + 1, :a], kpts1[p:p + 1, :b], desc0[p:p + 1, :a], desc1[p:p + 1, :b])
+            if threshold is None:
+                q0, q1, s = self._forward(*args)
+                o0[p, :a], o1[p, :b], sc[p, :a, :b] = q0[0].to(o0.dtype), q1[0].to(o1.dtype), s[0].float()
+            else:
+                r = self.match_batch(*args)
+                kk = min(a, b)
+                res.matches0[p, :a], res.matches1[p, :b] = r.matches0[0], r.matches1[0]
+                res.scores0[p, :a], res.scores1[p, :b] = r.scores0[0].float(), r.scores1[0].float()
+                res.matches[p, :kk], res.match_scores[p, :kk] = r.matches[0], r.match_scores[0].float()
+                res.counts[p] = r.counts[0]
+        return (o0, o1, sc) if threshold is None else res
+
+    def _forward(self, kpts0, kpts1, desc0, desc1, threshold: Optional[float] = None, lens=None):
         """forward; with `threshold` (match_batch) the fp16 hip head returns a MatchResult from
-        lg_assign_matches in the scores' place. Every other path returns scores as ever."""
+        lg_assign_matches in the scores' place. Every other path returns scores as ever. lens
+        (_ragged's fast path only: the chained fp16 path): the per-pair counts (counts0, counts1) on
+        the device."""
         pr, m, n = desc0.shape[0], desc0.shape[1], desc1.shape[1]
         hip = self.glue == "hip"
         rows_out = threshold is not None and self.attention is _kernel_attention
@@ -752,10 +863,12 @@ class LightGlueMatcher(nn.Module):
                 cos, sin = cos.contiguous(), sin.contiguous()
         head = self.log_assignment[self.n_layers - 1]
         if hip and self.chain_ok(x, m, n):
-            x, scores = self._forward_chain(x, cos, sin, splits, rows=rows_out)
+            x, scores = self._forward_chain(x, cos, sin, splits, rows=rows_out, lens=lens)
             if rows_out:  # the head's projected rows v: the matches without the scores tensor
-                scores = _Hip.assign_matches(scores, m, x.shape[-1], threshold)
+                scores = _Hip.assign_matches(scores, m, x.shape[-1], threshold, lens)
         else:
+            if lens is not None:
+                raise PluginError("LightGlueMatcher: per-pair counts reached a path that cannot mask them")
             for layer in self.transformers:
                 x = layer(x, cos, sin, splits, self.attention, hip)
             if hip and head.hip16_ok(x, m, n):
@@ -790,7 +903,7 @@ class LightGlueMatcher(nn.Module):
         return (self.n_layers > 0 and all(_fused_ok(x, layer.self_attn) for layer in self.transformers) and
                 self.log_assignment[self.n_layers - 1].hip16_ok(x, m, n))
 
-    def _forward_chain(self, x, cos, sin, splits, rows: bool = False):
+    def _forward_chain(self, x, cos, sin, splits, rows: bool = False, lens=None):
         """fp16 hip path with the layers chained (round 6): FFN launches also project their output for
         the attention that follows (lg_linear_cat_ffn_proj) — by default the self block's FFN the cross
         block's to_qk | to_v, the cross block's FFN the next layer's Wqkv (+ rotary) and the last FFN
@@ -802,13 +915,18 @@ class LightGlueMatcher(nn.Module):
         kinds = self._chain_kinds(x.shape[1])
         layers = self.transformers
         head = self.log_assignment[len(layers) - 1]
+        if lens is None:
+            attn_self = attn_cross = self.attention
+        else:  # ragged: image i's rows end at lens[i] (self attention: keys of its own image, cross: the other's)
+            attn_self = lambda calls: _kernel_attention_lens(calls, lens, (lens[0], lens[1]))   # noqa: E731
+            attn_cross = lambda calls: _kernel_attention_lens(calls, lens, (lens[1], lens[0]))  # noqa: E731
         qkv = None
         for li, layer in enumerate(layers):
             sa, ca = layer.self_attn, layer.cross_attn
             if qkv is None:
                 wq, bq = _qkv_perm(sa, dt)
                 qkv = _Hip.linear_qkv_rotary(x, wq, bq, cos, sin, sa.heads, splits)
-            c0, c1 = self.attention(qkv)                                          # self0, self1: one launch
+            c0, c1 = attn_self(qkv)                                               # self0, self1: one launch
             _, b0 = _ffn_in_fused(sa, sa.out_proj, dt)
             wc, bc = _cross_qkv(ca, dt)
             if "s" in kinds:
@@ -819,7 +937,7 @@ class LightGlueMatcher(nn.Module):
                 w0, _ = _ffn_in_fused(sa, sa.out_proj, dt)
                 x = _Hip.ffn(x, c0, c1, w0, b0, sa.ffn[1], sa.ffn[3].weight, sa.ffn[3].bias, _ffn_packed(sa, sa.out_proj, dt))
                 (qk0, qk1), (v0, v1) = _Hip.linear_split2(x, wc, bc, ca.heads, splits)
-            m0, m1 = self.attention([(qk0, qk1, v1), (qk1, qk0, v0)])          # cross: one launch
+            m0, m1 = attn_cross([(qk0, qk1, v1), (qk1, qk0, v0)])              # cross: one launch
             w0, b0 = _ffn_in_fused(ca, ca.to_out, dt)
             qkv = v = None
             if li + 1 < len(layers) and "q" in kinds:
@@ -841,7 +959,7 @@ class LightGlueMatcher(nn.Module):
         v = v.view(pr, m + n, 384)
         if rows:  # (match_batch: the head's projected rows instead of the scores)
             return x, v
-        return x, _Hip.assign_scores(v, m, x.shape[-1])
+        return x, _Hip.assign_scores(v, m, x.shape[-1], lens)
 
     def match(self, kpts0, kpts1, desc0, desc1):
         """forward + filter_matches (the demo's post-processing); for P > 1 pairs a list of
@@ -851,15 +969,38 @@ class LightGlueMatcher(nn.Module):
             return filter_matches(scores, self.filter_threshold)
         return [filter_matches(scores[i:i + 1], self.filter_threshold) for i in range(scores.shape[0])]
 
-    def match_batch(self, kpts0, kpts1, desc0, desc1) -> MatchResult:
+    def match_batch(self, kpts0, kpts1, desc0, desc1, counts0=None, counts1=None) -> MatchResult:
         """The matches of all P pairs as one MatchResult (dense matches and scores of both images and
         the compacted list), without a loop over pairs or a host synchronisation. On the fp16 hip path
         the forward stops at the head's projection and lg_assign_matches takes its rows (the forward's
         launches through the last FFN, then at most three; the fp32 scores tensor is never written).
         Every other case (fp32 model, glue='torch', n % 8 != 0, more than 2048 keypoints, a substituted
-        attention=) computes the scores as forward does and runs filter_matches_dense on them."""
+        attention=) computes the scores as forward does and runs filter_matches_dense on them.
+        counts0 / counts1: a ragged batch, as for forward (matches -1 and scores 0 on padded rows and
+        columns; the list keeps min(M, N) rows per pair)."""
+        if counts0 is not None or counts1 is not None:
+            return self._ragged(kpts0, kpts1, desc0, desc1, counts0, counts1, self.filter_threshold)
         out = self._forward(kpts0, kpts1, desc0, desc1, threshold=self.filter_threshold)[2]
         return out if isinstance(out, MatchResult) else filter_matches_dense(out, self.filter_threshold)
+
+    def match_pairs(self, pairs):
+        """pairs: a sequence of (kpts0 [m_p, 2], kpts1 [n_p, 2], desc0 [m_p, D], desc1 [n_p, D]) of any
+        sizes (one device and dtype). Zero-pads them to M = max m_p and N = max n_p rounded up to 8 and
+        runs match_batch with the counts: (MatchResult of the padded batch, counts0, counts1), the
+        counts as Python ints. Also how a single pair with n % 8 != 0 reaches the fp16 fast path."""
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("match_pairs: no pairs")
+        c0, c1 = [int(p[0].shape[0]) for p in pairs], [int(p[1].shape[0]) for p in pairs]
+        m, n = max(c0), (max(c1) + 7) // 8 * 8
+        batch = []
+        for j, size in enumerate((m, n, m, n)):
+            ref = pairs[0][j]
+            t = ref.new_zeros((len(pairs), size, ref.shape[-1]))
+            for p, pair in enumerate(pairs):
+                t[p, :pair[j].shape[0]] = pair[j]
+            batch.append(t)
+        return self.match_batch(*batch, counts0=c0, counts1=c1), c0, c1
 
 
 # --------------------------------------------------------------------------------------------

@@ -334,12 +334,18 @@ def mha_hd64_batched(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor
 _DT = {torch.float16: _lib.DT_HALF, torch.float32: _lib.DT_FLOAT}
 
 
-def mha_hd64_grouped(calls, out_dtype=None, outs=None):
+def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None):
     """Grouped launcher: several independent calls [(q, k, v), ...] of possibly different shapes
     ([B, H, Nq_i, 64] / [B, H, Nkv_i, 64]) in one launch (up to 4 per launch, chunked beyond).
 
     The four attention calls of a LightGlue layer (self0, self1, cross0->1, cross1->0;
-    lightglue_pytorch_with_plugin/lightglue.py:137-152, 188-205) run as two such launches."""
+    lightglue_pytorch_with_plugin/lightglue.py:137-152, 188-205) run as two such launches.
+
+    kv_lens (ragged batches; fp16 inputs): one entry per call, an int32 tensor [B] on the calls'
+    device (item b attends to its first kv_lens[i][b] keys, clamped into [1, Nkv_i]; keys past it are
+    never read) or None for all Nkv_i keys: mha_hd64_launch_grouped_lens, the streaming kernel.
+    q_lens: the same for query rows (mha_hd64_launch_grouped_qkv_lens): rows at or past q_lens[i][b]
+    are padding, written as NaN, and no real row's output bits depend on what they hold."""
     calls = list(calls)
     if not calls:
         return []
@@ -362,6 +368,33 @@ def mha_hd64_grouped(calls, out_dtype=None, outs=None):
     lib = _lib.load()
     device = calls[0][0].device
     stream = torch.cuda.current_stream(device).cuda_stream
+    if q_lens is not None and kv_lens is None:
+        kv_lens = [None] * len(calls)
+    if kv_lens is not None:
+        if in_dtype != torch.float16:
+            raise PluginError("kv_lens / q_lens: float16 inputs only")
+
+        def table(lens, what):
+            lens = list(lens)
+            if len(lens) != len(calls):
+                raise PluginError(f"{what}: one entry per call")
+            ptrs = (ctypes.c_void_p * len(calls))()
+            for i, (t, (q, _, _)) in enumerate(zip(lens, calls)):
+                if t is None:
+                    continue
+                if t.dtype != torch.int32 or t.device != q.device or not t.is_contiguous() or tuple(t.shape) != (q.shape[0],):
+                    raise PluginError(f"{what}[i]: a contiguous int32 tensor [B] on the call's device, or None")
+                ptrs[i] = t.data_ptr()
+            return ptrs
+
+        kp = table(kv_lens, "kv_lens")
+        if q_lens is None:
+            status = lib.mha_hd64_launch_grouped_lens(descs, kp, len(calls), _DT[in_dtype], _DT[out_dtype], None, 0, stream)
+        else:
+            status = lib.mha_hd64_launch_grouped_qkv_lens(descs, table(q_lens, "q_lens"), kp, len(calls), _DT[in_dtype],
+                                                          _DT[out_dtype], None, 0, stream)
+        _check(status, "mha_hd64_launch_grouped_lens")
+        return outs
     # (fp32 groups: includes the fp16 copies of Q/K/V the convert launch writes when a single-pass
     # kernel that does not round fp32 inputs itself runs them; largest chunk of 4 calls)
     nbytes = lib.mha_hd64_grouped_workspace_bytes_typed(descs, len(calls), _DT[in_dtype])
