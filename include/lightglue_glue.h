@@ -74,7 +74,8 @@ int32_t lg_merge_heads_cat(int32_t dtype, const void* x, const void* x0, const v
 int32_t lg_layernorm_gelu(int32_t dtype, const void* x, const void* gamma, const void* beta, int32_t rows,
                           int32_t dim, float eps, void* y, hipStream_t stream);
 
-/* ---- projections with their neighbours fused (fp16 only; csrc/lightglue_linear.hip) ----
+/* ---- projections with their neighbours fused (fp16 only; csrc/lightglue_linear.hip; the FFN entry
+ * points lg_linear_cat_ln_gelu, lg_linear_cat_ffn*, lg_ffn_pack: csrc/lightglue_ffn.hip) ----
  * W [n, k] row-major (nn.Linear layout), bias [n]; k in {256, 512}; n a multiple of 64; rows m
  * any. A/W/x/ctx 16-byte aligned, bias/out/res/cos/sin 8-byte aligned.
  * lg_linear:            out [m, n] = A [m, k] · Wᵀ + bias (+ res [m, n] when res != NULL). */
@@ -172,7 +173,8 @@ int32_t lg_log_double_softmax_f16(const void* sim, const void* z0, const void* z
                                   int64_t z_row_stride, int32_t m, int32_t n, int32_t batch, float* scores,
                                   void* workspace, hipStream_t stream);
 
-/* The fp16 assignment head in two launches (round 6): v [batch][m + n][ld] fp16 is the final
+/* The fp16 assignment head in two launches (round 6; csrc/lightglue_assign.hip, with the match head
+ * below): v [batch][m + n][ld] fp16 is the final
  * projection of both images' rows (image 0's m rows, then image 1's n; pairs pair_stride elements
  * apart), channels 0..255 the scaled descriptors m0 / m1 (final_proj(d) / d^0.25) and channel zc
  * (>= 256) the matchability logit. scores [batch, m, n] fp32 = log_softmax(sim, 2) + log_softmax(sim, 1)

@@ -2,22 +2,14 @@
 //
 // Memory-bound layout/normalisation kernels: one pass over the data each, 16-B accesses where the
 // layout allows, one wave64 per row for row statistics (shuffle-xor reductions), fp32 math.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
-#include "lightglue_glue.h"
-#include "mha_hd64.h"
-#include "mha_hd64_internal.h"
+#include "lightglue_device.h"  // (f16, kD, gelu_as2, launched)
 
 namespace {
 
-typedef _Float16 f16;
-
 template <typename T> __device__ __forceinline__ float ld(const T* p) { return (float)*p; }
 template <typename T> __device__ __forceinline__ void st(T* p, float v) { *p = (T)v; }
-
-constexpr int kD = 64;  // head dim
 
 // Row n of the stacked rows (`pairs` image pairs, pair-major: n0 rows of image 0, then n1 rows of
 // image 1) -> which image, and the offset of the row's head-h segment in that image's
@@ -165,40 +157,6 @@ __global__ __launch_bounds__(256) void ln_gelu_kernel(const T* x, const T* __res
         const float t = v[i] * rstd * ld(g + c) + ld(bta + c);
         st(yr + c, 0.5f * t * (1.f + erff(t * 0.70710678118654752f)));
     }
-}
-
-// Exact (erf) GELU for the fp16 FFN with erf from Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, far
-// below the fp16 rounding of the output), folded: with z = |x| / sqrt(2), r = 1 / (1 + p z) and
-// erf(z) = 1 - y(r) e^{-z^2}, x Phi(x) = max(x, 0) - |x| (y / 2) e^{-x^2 / 2} for either sign of x (no
-// 1 + erf cancellation for negative x); one v_rcp_f32 and one v_exp_f32, the 1/2 and 1/sqrt(2) in
-// the constants. (lightglue_glue.hip and lightglue_linear.hip compute it alike.)
-__device__ __forceinline__ float gelu_as(float x) {
-    const float ax = fabsf(x);
-    const float r = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, ax, 1.f));
-    float p = fmaf(0.5f * 1.061405429f, r, 0.5f * -1.453152027f);
-    p = fmaf(p, r, 0.5f * 1.421413741f);
-    p = fmaf(p, r, 0.5f * -0.284496736f);
-    p = fmaf(p, r, 0.5f * 0.254829592f);
-    const float w = p * r * ax;
-    const float e = __builtin_amdgcn_exp2f(x * x * (-0.5f * 1.4426950408889634f));
-    return fmaf(-w, e, fmaxf(x, 0.f));
-}
-// The same on a pair of values, written on float2 so that the FMAs and products issue as packed
-// v_pk_fma_f32 / v_pk_mul_f32 (two values per instruction: the vector pipe's full fp32 rate; the
-// rcp, exp, abs and max stay per value)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 gelu_as2(f32x2 x) {
-    const f32x2 ax = f32x2{fabsf(x[0]), fabsf(x[1])};
-    const f32x2 den = ax * (0.3275911f * 0.70710678118654752f) + 1.f;
-    const f32x2 r = f32x2{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-    f32x2 p = r * (0.5f * 1.061405429f) + (0.5f * -1.453152027f);
-    p = p * r + (0.5f * 1.421413741f);
-    p = p * r + (0.5f * -0.284496736f);
-    p = p * r + (0.5f * 0.254829592f);
-    const f32x2 w = p * r * ax;
-    const f32x2 a = x * x * (-0.5f * 1.4426950408889634f);
-    const f32x2 e = f32x2{__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
-    return f32x2{fmaxf(x[0], 0.f), fmaxf(x[1], 0.f)} - w * e;
 }
 
 // fp16, dim 512 (the matcher's FFN width): a lane owns 8 contiguous columns (one 16-B load of x,
@@ -663,12 +621,6 @@ __global__ __launch_bounds__(256) void pair_inputs_kernel(const f16* __restrict_
 }
 
 inline unsigned blocks_for(long threads) { return (unsigned)((threads + 255) / 256); }
-
-int32_t launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return MHA_HD64_STATUS_SUCCESS;
-    return mha_hd64::report_error(MHA_HD64_STATUS_LAUNCH_FAILED, what, hipGetErrorString(e));
-}
 
 bool bad_dtype(int32_t dt) { return dt != MHA_HD64_DT_HALF && dt != MHA_HD64_DT_FLOAT; }
 

@@ -110,7 +110,7 @@ class _Hip:
         _check(st, "lg_merge_heads_cat")
         return out
 
-    # ---- projections with their neighbours fused (fp16; csrc/lightglue_linear.hip) ----
+    # ---- projections with their neighbours fused (fp16; csrc/lightglue_linear.hip, lightglue_ffn.hip) ----
     @staticmethod
     def linear(a, w, b, res=None):
         """a [1, M, K] -> a·wᵀ + b (+ res) [1, M, N]."""

@@ -504,6 +504,92 @@ def test_ffn_and_form_hooks_validate_before_touching_the_device(lib):
         lib.lg_linear_set_ffn_fused(prev)
 
 
+A = 4096  # a fake 16-B aligned address: never dereferenced on the paths below
+
+
+def _rejects(call, bads):
+    """Every bad case returns BAD_PARAM (1), on an otherwise empty launch wherever its own arguments
+    allow one: the check comes before the empty-launch return, and nothing reaches the device."""
+    for bad in bads:
+        assert call(**bad) == 1, bad
+
+
+def test_projections_validate_before_touching_the_device(lib):
+    """lg_linear, lg_linear_cat, lg_linear_cat_ln_gelu, lg_linear_qkv_rotary, lg_linear_split2: an empty
+    launch returns success and every clause of the argument check rejects, without a device call."""
+    def linear(**kw):
+        a = dict(a=A, w=A, b=A, res=None, m=0, n=256, k=256, out=A)
+        a.update(kw)
+        return lib.lg_linear(a["a"], a["w"], a["b"], a["res"], a["m"], a["n"], a["k"], a["out"], None)
+
+    assert linear() == 0 and linear(res=A + 8, b=A + 8, out=A + 8, k=512, n=64) == 0
+    _rejects(linear, [dict(a=None), dict(w=None), dict(b=None), dict(out=None), dict(a=A + 8), dict(w=A + 8),
+                      dict(b=A + 4), dict(out=A + 4), dict(res=A + 4), dict(k=128), dict(k=384), dict(n=0), dict(n=96),
+                      dict(m=-1)])
+
+    def cat(fn="cat", **kw):
+        a = dict(x=A, c0=A, c1=A, heads=4, n0=8, n1=8, pairs=0, w=A, b=A, n=512, g=A, be=A, eps=1e-5, out=A)
+        a.update(kw)
+        if fn == "cat":
+            return lib.lg_linear_cat(a["x"], a["c0"], a["c1"], a["heads"], a["n0"], a["n1"], a["pairs"], a["w"], a["b"],
+                                     a["n"], a["out"], None)
+        return lib.lg_linear_cat_ln_gelu(a["x"], a["c0"], a["c1"], a["heads"], a["n0"], a["n1"], a["pairs"], a["w"],
+                                         a["b"], a["g"], a["be"], a["eps"], a["out"], None)
+
+    both = [dict(x=None), dict(w=None), dict(b=None), dict(out=None), dict(x=A + 8), dict(c0=A + 8), dict(c1=A + 8),
+            dict(w=A + 8), dict(b=A + 4), dict(out=A + 4), dict(heads=0), dict(heads=1), dict(heads=3),
+            dict(n0=-1), dict(n1=-1), dict(pairs=-1)]
+    assert cat() == 0 and cat(n=64, b=A + 8, out=A + 8) == 0 and cat(heads=2, n=256) == 0
+    assert cat(n0=0, c0=A + 8) == 0 and cat(n1=0, c1=None) == 0  # (an absent image's ctx is not checked)
+    _rejects(cat, both + [dict(n=0), dict(n=96)])
+
+    def ln(**kw):
+        return cat(fn="ln", **kw)
+
+    assert ln() == 0 and ln(heads=2, b=A + 8, out=A + 8, eps=0.0) == 0
+    _rejects(ln, both + [dict(g=None), dict(be=None), dict(eps=-1.0), dict(eps=float("nan"))])
+
+    def qkv(**kw):
+        a = dict(x=A, w=A, b=A, cs=A, sn=A, heads=4, n0=8, n1=8, pairs=0, k=256)
+        a.update(kw)
+        return lib.lg_linear_qkv_rotary(a["x"], a["w"], a["b"], a["cs"], a["sn"], a["heads"], a["n0"], a["n1"], a["pairs"],
+                                        a["k"], A, A, A, A, A, A, None)
+
+    assert qkv() == 0 and qkv(k=512, heads=1, b=A + 8, cs=A + 8, sn=A + 8) == 0
+    _rejects(qkv, [dict(x=None), dict(w=None), dict(b=None), dict(cs=None), dict(sn=None), dict(x=A + 8), dict(w=A + 8),
+                   dict(b=A + 4), dict(cs=A + 4), dict(sn=A + 4), dict(k=128), dict(heads=0), dict(n0=-1), dict(n1=-1),
+                   dict(pairs=-1)])
+
+    def split2(**kw):
+        a = dict(x=A, w=A, b=A, heads=4, n0=8, n1=8, pairs=0, k=256)
+        a.update(kw)
+        return lib.lg_linear_split2(a["x"], a["w"], a["b"], a["heads"], a["n0"], a["n1"], a["pairs"], a["k"], A, A, A, A,
+                                    None)
+
+    assert split2() == 0 and split2(k=512, heads=1, b=A + 8) == 0
+    _rejects(split2, [dict(x=None), dict(w=None), dict(b=None), dict(x=A + 8), dict(w=A + 8), dict(b=A + 4), dict(k=128),
+                      dict(heads=0), dict(n0=-1), dict(n1=-1), dict(pairs=-1)])
+
+
+def test_assign_scores_validates_before_touching_the_device(lib):
+    """lg_assign_scores (the heads' other entry points: test_match_head.py, test_ragged.py) and the two
+    workspace queries, whose values are part of the C ABI (a host sizes its buffer once)."""
+    def scores(**kw):
+        a = dict(v=A, ps=16 * 384, ld=384, zc=256, m=8, n=8, batch=1, sc=A, ws=A)
+        a.update(kw)
+        return lib.lg_assign_scores(a["v"], a["ps"], a["ld"], a["zc"], a["m"], a["n"], a["batch"], a["sc"], a["ws"], None)
+
+    assert scores(batch=0) == 0 and scores(batch=0, v=None, sc=None, ws=None) == 0
+    assert scores(m=0, ps=8 * 384) == 0 and scores(n=0, ps=8 * 384, v=None, sc=None, ws=None) == 0
+    _rejects(scores, [dict(n=12), dict(m=2049, ps=(2049 + 8) * 384), dict(n=2056, ps=(8 + 2056) * 384), dict(zc=255),
+                      dict(zc=384), dict(zc=400), dict(ld=380), dict(ld=248, zc=240), dict(ps=16 * 384 - 1), dict(m=-1),
+                      dict(n=-8), dict(batch=-1), dict(v=None), dict(sc=None), dict(ws=None), dict(v=A + 8), dict(sc=A + 8),
+                      dict(ws=A + 8), dict(batch=0, n=12), dict(batch=0, zc=255)])
+    for (m, n, b), want_s, want_m in (((0, 136, 3), 0, 0), ((150, 136, 3), 181504, 201728), ((2048, 2048, 1), 8470528, 9584640)):
+        assert lib.lg_assign_scores_workspace(m, n, b) == want_s, (m, n, b)
+        assert lib.lg_assign_matches_workspace(m, n, b) == want_m, (m, n, b)
+
+
 @pytest.mark.parametrize("version", [None, 1])
 def test_stale_library_is_reported_as_missing(tmp_path, monkeypatch, version):
     """A library built from older sources (no lg_glue_abi_version, or an older ABI) raises

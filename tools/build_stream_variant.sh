@@ -9,8 +9,7 @@ mkdir -p lib/ab
 make -s lib/libmha_hd64.so
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-mfma-vgpr-form -fno-honor-nans \
       "$@" -I../include -Icsrc -c csrc/mha_hd64_stream.hip -o lib/ab/s_$NAME.o
-hipcc --offload-arch=gfx950 -shared -fPIC lib/obj/mha_hd64_kernels.o lib/obj/mha_hd64_direct.o \
-      lib/obj/mha_hd64_direct16.o lib/ab/s_$NAME.o lib/obj/mha_hd64_plugin.o lib/obj/lightglue_glue.o \
-      lib/obj/lightglue_linear.o -o lib/ab/libmha_hd64_$NAME.so
+OBJ=$(make -s print-objs)
+hipcc --offload-arch=gfx950 -shared -fPIC ${OBJ/lib\/obj\/mha_hd64_stream.o/lib\/ab\/s_$NAME.o} -o lib/ab/libmha_hd64_$NAME.so
 rm -f lib/ab/s_$NAME.o
 echo lib/ab/libmha_hd64_$NAME.so
