@@ -49,7 +49,9 @@ struct FwdArgs {
     CallArgs c[kMaxCalls];
     int n_calls;
     int total_blocks;            // grid size (kept here so the first scalar-load round has it)
-    unsigned long long* stamps;  // diagnostic builds only (MHA_STAMPS): 8 x u64 per workgroup
+    // diagnostic builds only (MHA_STAMPS): u64 stamps per workgroup, 8 (ring and 32-row kernels) or
+    // 16 (16-row kernel: at most 256 workgroups x 16, below the per-step region at +(1 << 16))
+    unsigned long long* stamps;
     // In-launch combine (non-null): one arrival ticket per query group, indexed by the group's
     // first block j; zero between launches (the last arriver resets its ticket).
     unsigned* tickets;
@@ -309,8 +311,9 @@ __device__ __forceinline__ void lds_dma16(unsigned m0, unsigned voff, __amdgpu_b
 }
 // The same with one wait state, for call sites whose M0, soffset and descriptor are SALU values
 // (a SALU write of M0 needs 1 wait state before an LDS-DMA load; no VALU writes them): the hot
-// refill of the streaming kernel. tools/check_dma_hazards.py audits every LDS-DMA load of the
-// built library against both rules (tests/test_abi.py runs it).
+// refill of the streaming kernel and the one-pass forms of the 16-row single-pass kernel.
+// tools/check_dma_hazards.py audits every LDS-DMA load of the built library against both rules
+// (tests/test_abi.py runs it).
 __device__ __forceinline__ void lds_dma16_s(unsigned m0, unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned soff) {
     asm volatile(
         "s_nop 0\n\t"
@@ -324,7 +327,10 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
 #ifndef MHA_DMA_ASM
-#define MHA_DMA_ASM 1  // 0: the LDS-DMA builtin in the single-pass kernels (A/B hook)
+// 0: the LDS-DMA builtin in the single-pass kernels (A/B hook). 1: the asm DMA in every form of
+// the 16-row kernel (two-pass: lds_dma16; one-pass: lds_dma16_s, whose PVs run under counted waits)
+// and in the two-pass forms of the 32-row kernel, whose one-pass forms keep the builtin.
+#define MHA_DMA_ASM 1
 #endif
 
 // L2 prefetch for the single-pass kernels (issued by one wave per workgroup, before its own

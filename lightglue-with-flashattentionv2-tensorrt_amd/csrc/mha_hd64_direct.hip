@@ -163,7 +163,9 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
             if (MHA_ABL & ABL_NO_GLOAD) return;
             // asm DMA in the multi-pass forms (no compiler drain before the transposing reads:
             // 1x4x1024x2048 7.28 vs 7.64 us); the one-pass forms measured neutral (1024^2 5.02 vs
-            // 5.00, 768^2 4.48 vs 4.28) and keep the builtin
+            // 5.00, 768^2 4.48 vs 4.28) and keep the builtin. (Their code has the compiler's
+            // vmcnt(0) in front of the first transposing read, as the 16-row kernel's had. There,
+            // PV under counted waits is worth about 1 % of a call, so this kernel's schedule stays.)
             if (MHA_DMA_ASM && PASSES > 1) {
                 lds_dma16(lds_addr(smem + region + 1024 * li), voff, rs, 1024u * i);
             } else {

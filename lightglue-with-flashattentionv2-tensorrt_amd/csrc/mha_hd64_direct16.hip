@@ -19,6 +19,11 @@
 //  * Softmax as the 32-row kernel: the first tile sets the running max, the later tiles' scores
 //    wait for ONE lazy-rescale decision (threshold 8, log2 units), row sums on the matrix pipe
 //    (an all-ones A operand), masking of keys past nkv on the vector pipe (partial tiles only).
+//  * One-pass forms (nkv <= 1024): K/V by the asm LDS-DMA, so no compiler-inserted vmcnt(0) sits in
+//    front of the first PV (that is where the gain over the builtin comes from). 4-tile form:
+//    PV(t) starts under the counted wait that covers V(t), with tile t + 1's exponentials beside
+//    it, and the last tile goes in two halves (vmcnt(4), vmcnt(0)). 2-tile form: PV(0) beside
+//    tile 1's exponentials, then one vmcnt(0) and PV(1).
 //  * Epilogue: each wave stages Oᵀ (fp32) and (m, l) in its region; one barrier; 256 threads
 //    merge (row, 4 dims) over the 4 waves and store O.
 // LDS images (bank rule of cdna_hip_programming.md §2): K rows XOR chunk (row>>1)&7 (k_off: the
@@ -32,18 +37,29 @@
 #include "mha_hd64_device.h"
 #include "mha_hd64_internal.h"
 
-// Diagnostic timestamps (-DMHA_STAMPS builds, tools/dstamps.py ... 22): wave 0's s_memtime at the
-// phase boundaries of mha_hd64_direct.hip's slots (0 entry, 1 Q + K(0) landed, 3 V(0) landed,
-// 2 later tiles' exponentials done, 4 PV done, 5 after the epilogue barrier, 6 stores acked).
+// Diagnostic timestamps (-DMHA_STAMPS builds, tools/dstamps.py ... 22): wave 0's s_memtime at its
+// phase boundaries, 16 slots per workgroup: 0 entry, 1 Q + K(0) landed, 2 last score done (the
+// rescale decision taken), 3 later tiles' exponentials done, 4 PV done, 5 after the epilogue
+// barrier, 6 stores acked, 7 rows 0-31 of the last V tile landed, 8 + t V(t) landed. The stamps
+// stay in scalar registers until the end: a store in the middle of the K/V stream would sit on the
+// VM counter that the counted waits read.
 #ifdef MHA_STAMPS
-#define DSTAMP(slot)                                                                              \
+#define DSTAMP_DECL unsigned long long dstamp_[16] = {}
+#define DSTAMP(slot) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dstamp_[slot])::"memory")
+#define DSTAMP_FLUSH                                                                              \
     do {                                                                                          \
-        unsigned long long t_;                                                                    \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-        if (threadIdx.x == 0) a.stamps[blockIdx.x * 8 + (slot)] = t_;                             \
+        if (threadIdx.x == 0)                                                                     \
+            _Pragma("unroll") for (int s_ = 0; s_ < 16; ++s_)                                     \
+                a.stamps[blockIdx.x * 16 + s_] = dstamp_[s_];                                     \
     } while (0)
 #else
+#define DSTAMP_DECL \
+    do {            \
+    } while (0)
 #define DSTAMP(slot) \
+    do {             \
+    } while (0)
+#define DSTAMP_FLUSH \
     do {             \
     } while (0)
 #endif
@@ -58,8 +74,9 @@ namespace {
 
 template <int N>
 __device__ __forceinline__ void wait_vmc() {
-    static_assert(N % 8 == 0 && N <= 40, "vmcnt");
+    static_assert((N % 8 == 0 || N == 4) && N <= 40, "vmcnt");
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // half a tile
     else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else if constexpr (N == 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
@@ -123,6 +140,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
     lds_char* const lds = (lds_char*)smem;
 
+    DSTAMP_DECL;
     DSTAMP(0);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -370,10 +388,20 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
         const unsigned v_lane_off = lrow + (((lane & 7) ^ (((lane >> 4) & 3) << 1)) << 4);
         // source piece i of the wave's key slice into region piece li (li = i except in pass 1)
         auto dma_piece = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, int i, int li) {
-            // asm DMA in the multi-pass forms (no compiler drain before the transposing reads:
-            // 1x4x1024x2048 7.28 vs 7.64 us); the one-pass forms measured neutral (1024^2 5.02 vs
-            // 5.00, 768^2 4.48 vs 4.28) and keep the builtin
-            if (MHA_DMA_ASM && PASSES > 1) {
+            // asm DMA in every form of this kernel: with the builtin the compiler drains every DMA
+            // in flight (vmcnt(0)) before the first transposing read, so no PV can start under a
+            // counted wait (two-pass forms: 1x4x1024x2048 7.28 vs 7.64 us; one-pass forms, same
+            // schedule, profiles/direct_overlap/ab_forced.jsonl `parent_asms` against `parent`:
+            // 1024^2 5.07-5.23 vs 5.13-5.30 us, 320^2 3.31-3.39 vs 3.39-3.43, 768^2 and 512^2 equal).
+            if (MHA_DMA_ASM && PASSES == 1) {
+                // M0, the offset and the descriptor are SALU values here (region comes from the
+                // wave index read once at entry), so the one-wait-state form is enough;
+                // tools/check_dma_hazards.py audits every piece. The `s_nop 4` of lds_dma16 on
+                // each of a wave's 64 pieces cost the shapes that are not bound by the K/V stream
+                // more than the drain did (768^2 4.58-4.73 vs 4.35-4.50 us with the builtin, 512^2
+                // 3.53-3.61 vs 3.46-3.50), which is why the one-pass forms had kept the builtin.
+                lds_dma16_s(lds_addr(smem + region + 1024 * li), voff, rs, 1024u * i);
+            } else if (MHA_DMA_ASM) {
                 lds_dma16(lds_addr(smem + region + 1024 * li), voff, rs, 1024u * i);
             } else {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(smem + region + 1024 * li),
@@ -459,8 +487,9 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
         f16x8 p[TPW][2];   // P (fp16), B operand of step u of tile t
         f32x4 sc[TPW][4];  // raw scores of tiles 1..
         // Oᵀ += Vᵀ·Pᵀ for the tile in slot t; first: accumulators from an inline 0; refill: V's
-        // fragments all in registers, then K of tile TPW + t into slot t, then the MFMAs
-        auto pv = [&](int t, bool first, bool refill) {
+        // fragments all in registers, then K of tile TPW + t into slot t, then the MFMAs. Steps
+        // [u0, u1) only: step u reads rows 32u..32u+31 of the tile (DMA pieces 4u..4u+3).
+        auto pv = [&](int t, bool first, bool refill, int u0 = 0, int u1 = 2) {
             f16x8 va[2][4];
             auto read_v = [&](int u, int db) {
                 const unsigned off = (unsigned)(t * kTileBytes + 128 * 32 * u);
@@ -478,6 +507,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
+                if (u < u0 || u >= u1) continue;
 #pragma unroll
                 for (int db = 0; db < 4; ++db) {
                     if (!refill) read_v(u, db);
@@ -546,17 +576,63 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
                 m_run += d;
             }
         }
-        wait_vmc<8 * (TPW - 1)>();  // V(0) landed
-        DSTAMP(3);
-        pv(0, true, PASSES > 1);    // beside the later tiles' exponentials
-#pragma unroll
-        for (int t = 1; t < TPW; ++t) exp_pack(sc[t], p[t], m_run);
         DSTAMP(2);
-        if constexpr (PASSES == 1) {
-            wait_vmc<0>();
+        if constexpr (PASSES == 1 && TPW > 2) {
+            // Phase 2 of the 4-tile form, under the V stream: PV(t) as soon as V(t) is covered,
+            // tile t + 1's exponentials beside it (matrix pipe and vector pipe), the last tile in
+            // two halves, so that only five MFMAs and the epilogue follow the final landing. The
+            // DMA is the asm form (dma_piece): the only waits are these, and every transposing read
+            // of slot t follows, in program order, the wait that retires V(t) (each wait is an asm
+            // statement with a memory clobber; a wave reads only slots its own DMA filled, so its
+            // own vmcnt is the whole ordering). Tiles, steps and dim blocks accumulate in the old
+            // order: the outputs are bit for bit those of the schedule with one vmcnt(0) before
+            // PV(1..). Issue order of the V groups, 8 pieces each, nothing after them: V(0), ..,
+            // V(TPW-1).
+            // What it is worth (profiles/direct_overlap/ab_forced.jsonl, us per launch; `asm-only`
+            // is the 2-tile form's schedule below with the same DMA): at 1x4x1024^2 nothing beyond
+            // the DMA form (sessions 2 and 3: 5.08-5.24, asm-only 5.07-5.23, builtin DMA 5.13-5.30);
+            // at 768^2 (a wave without keys) 4.37-4.43 against asm-only 4.40-4.53. Measured and
+            // dropped (session 1, builtin DMA 5.06-5.11): all later exponentials ahead of the V(0)
+            // wait 5.16-5.25, and with a scheduling barrier in front of every wait 5.20-5.27. The
+            // stamps say why (tools/dstamps.py ... 22): wave 0's V tiles have all landed ~0.8 k
+            // cycles after its last score, about when 48 exponentials alone are done, so
+            // exponentials run ahead of PV(0) only delay the matrix pipe.
 #pragma unroll
-            for (int t = 1; t < TPW; ++t) pv(t, false, false);
+            for (int t = 0; t < TPW - 1; ++t) {
+                wait_groups(TPW - 1 - t);  // V(t) landed: younger are V(t+1..TPW-1), vmcnt(8·(TPW-1-t))
+                DSTAMP(8 + t);
+                pv(t, t == 0, false);                      // on the matrix pipe, beside
+                exp_pack(sc[t + 1], p[t + 1], m_run);      // the next tile's exponentials
+                if (t == TPW - 2) DSTAMP(3);
+            }
+            // the last tile in two halves: step 0 reads rows 0-31 (its pieces 0-3), step 1 the rest
+            wait_vmc<4>();  // pieces 0-3 of V(TPW-1) landed: younger are its pieces 4-7
+            DSTAMP(7);
+            pv(TPW - 1, false, false, 0, 1);
+            wait_vmc<0>();  // pieces 4-7: nothing is younger
+            DSTAMP(8 + TPW - 1);
+            pv(TPW - 1, false, false, 1, 2);
+        } else if constexpr (PASSES == 1) {
+            // Phase 2 of the 2-tile form: PV(0) beside tile 1's exponentials once V(0) is covered,
+            // then PV(1) behind one vmcnt(0). The schedule above lost to it here (320^2 3.36-3.40
+            // against 3.31-3.39 us, 512^2 3.46-3.48 against 3.44-3.51; builtin DMA 3.39-3.43 and
+            // 3.47-3.50): with two tiles there is no PV left to move under the stream, and the
+            // split last tile only adds waits.
+            wait_vmc<8>();  // V(0) landed: younger is V(1)
+            DSTAMP(8);
+            pv(0, true, false);
+            exp_pack(sc[1], p[1], m_run);
+            DSTAMP(3);
+            wait_vmc<0>();  // V(1): nothing is younger
+            DSTAMP(9);
+            pv(1, false, false);
         } else {
+            wait_vmc<8 * (TPW - 1)>();  // V(0) landed
+            DSTAMP(8);
+            pv(0, true, true);  // beside the later tiles' exponentials
+#pragma unroll
+            for (int t = 1; t < TPW; ++t) exp_pack(sc[t], p[t], m_run);
+            DSTAMP(3);
             // pass 1: tiles TPW + u through slot u, raw scores; ONE rescale decision for the pass
             // (O and the row sums rescaled), then exponentials against the running max and PV.
             // score2(u): K(TPW+u) landed (`younger` DMA groups after it), its fragments in registers,
@@ -668,6 +744,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
 #ifdef MHA_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     DSTAMP(6);
+    DSTAMP_FLUSH;
 #endif
 }
 
