@@ -289,6 +289,15 @@ int32_t mha_hd64_launch_stream_lens(const void* q, const void* k, const void* v,
  * tiles_per_split} (streaming plan: {23, 4 or 8 waves, 1, ...}); returns the workspace bytes that
  * plan uses. */
 size_t mha_hd64_plan(int32_t batch, int32_t heads, int32_t nq, int32_t nkv, size_t ws_bytes, int32_t* out4);
+/* How one launch of n <= 4 calls (shapes only; pointers unused) is routed with ws_bytes of workspace
+ * (has_workspace 0: a NULL workspace) and forced plan fields as mha_hd64_launch_forced takes them:
+ * out5 = {route: 0 the plan for in_type, 1 fp32 rounded inside the 16-row kernel, 2 convert launch +
+ * fp16 kernel; plan code as out4[0] above; kv_waves; rows_per_wave; direct_tiles}; splits,
+ * tiles_per_split, ws_offset: n entries each. Returns the workspace bytes the route uses
+ * ((size_t)-1: bad arguments). */
+size_t mha_hd64_plan_route(const mha_hd64_call_t* calls, int32_t n, int32_t in_type, size_t ws_bytes,
+                           int32_t has_workspace, int32_t q_waves, int32_t kv_waves, int32_t splits, int32_t* out5,
+                           int32_t* splits_out, int32_t* tiles_per_split, size_t* ws_offset);
 /* Per-workgroup timestamp buffer of -DMHA_STAMPS diagnostic builds (ignored by release builds). */
 void mha_hd64_set_stamp_buffer(void* p);
 /* How the calling thread's last launch merged its KV splits: 0 no split, 1 in-launch, 2 kernel. */

@@ -1,5 +1,5 @@
 // mha_hd64_device.h — device-side types and helpers shared by the gfx950 attention kernels
-// (mha_hd64_kernels.hip: the LDS-ring kernel and the split combine; mha_hd64_direct.hip: the
+// (mha_hd64_ring.hip: the LDS-ring kernel and the split combine; mha_hd64_direct.hip: the
 // single-pass kernel). Included by HIP translation units only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,13 +22,12 @@ typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
 
 constexpr float kScaleLog2 = 0.18033688011112042f;  // 0.125 * log2(e)
 constexpr float kRescaleThr = 8.0f;                  // lazy-rescale threshold (log2 units)
-constexpr int kTileKV = 64;                          // keys per LDS tile
 constexpr int kTileBytes = kTileKV * kHeadDim * 2;   // 8 KiB fp16 tile
 
 // One call of a launch (a launch carries up to kMaxCalls independent calls of any shapes: the
 // grouped launcher runs self0+self1 or cross0->1+cross1->0 of a LightGlue layer as one launch).
 constexpr int kMaxCalls = kGroupCalls;
-constexpr int kMaxSplits = 16;  // KV splits per query group (combine loads them all in one round)
+constexpr int kConvMax = 3 * kMaxCalls;  // tensors of one convert launch (Q, K, V of every call)
 struct CallArgs {
     const void* q;
     const void* k;
@@ -64,6 +63,14 @@ struct FwdArgs {
     const int* qlens[kMaxCalls];
 };
 
+// LDS-ring kernel (mha_hd64_ring.hip): workgroups of qw x kw waves of 32*rb query rows each.
+hipError_t launch_ring(const FwdArgs& a, int grid, int qw, int kw, int rb, bool in_f32, bool out_f32,
+                       hipStream_t stream);
+// Its split-combine kernel, for the launch described by a (block_m = its query rows per workgroup).
+hipError_t launch_combine(const FwdArgs& a, int block_m, bool out_f32, hipStream_t stream);
+// fp32 -> fp16 (RNE) of count <= kConvMax tensors; end8 = prefix sums of their element counts / 8.
+hipError_t launch_convert(const void* const* src, void* const* dst, const unsigned* end8, int count,
+                          hipStream_t stream);
 // Single-pass kernel (mha_hd64_direct.hip): 8 waves x tiles_per_wave 64-key tiles per 32-row block.
 hipError_t launch_direct(const FwdArgs& a, int grid, int tiles_per_wave, bool out_f32, hipStream_t stream);
 // 16-row single-pass kernel (mha_hd64_direct16.hip): 4 waves x 2*tiles_per_wave 64-key tiles.

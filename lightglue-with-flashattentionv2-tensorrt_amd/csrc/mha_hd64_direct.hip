@@ -1,6 +1,6 @@
 // mha_hd64_direct.hip — single-pass FlashAttention forward, head_dim = 64, for gfx950 (MI355X).
 //
-// The same operator as mha_hd64_kernels.hip (O = softmax(Q·Kᵀ·0.125)·V per (batch, head); the
+// The same operator as mha_hd64_ring.hip (O = softmax(Q·Kᵀ·0.125)·V per (batch, head); the
 // reference's attention_headdim_64_fp16in_fp16out.cu:253-733 / …fp16in_fp32out.cu:253-703), laid
 // out for launches that cannot fill the chip with query blocks alone — the plugin's single
 // 1x4x1024x1024 call is 128 blocks of 32 rows.
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
         }
         qbad = q_nonfinite_fix(qf);  // non-finite query rows: zeroed here, NaN rows at the store
 
-        // Row sums on the matrix pipe and the bias k-step: as the ring kernel (mha_hd64_kernels.hip).
+        // Row sums on the matrix pipe and the bias k-step: as the ring kernel (mha_hd64_ring.hip).
         const f16 sel = (((lane & 15) >> 2) & 1) == ((lane >> 4) & 1) ? (f16)1.f : (f16)0.f;
         const f16x8 a_sum = f16x8{sel, sel, sel, sel, sel, sel, sel, sel};
         const f16 one_h = hh == 0 ? (f16)1.f : (f16)0.f;

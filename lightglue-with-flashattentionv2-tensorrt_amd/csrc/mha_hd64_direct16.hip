@@ -1,7 +1,7 @@
 // mha_hd64_direct16.hip — single-pass FlashAttention forward, head_dim = 64, 16-row query blocks,
 // for gfx950 (MI355X).
 //
-// The operator of mha_hd64_kernels.hip / mha_hd64_direct.hip (O = softmax(Q·Kᵀ·0.125)·V per
+// The operator of mha_hd64_ring.hip / mha_hd64_direct.hip (O = softmax(Q·Kᵀ·0.125)·V per
 // (batch, head); the reference's attention_headdim_64_fp16in_fp16out.cu:253-733 /
 // …fp16in_fp32out.cu:253-703) for launches whose 32-row blocks fill at most half the chip: the
 // plugin's single 1x4x1024x1024 call is 128 blocks of 32 rows (128 of 256 CUs busy, the other

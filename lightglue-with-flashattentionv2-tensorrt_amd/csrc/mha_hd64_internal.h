@@ -10,6 +10,8 @@ namespace mha_hd64 {
 constexpr int kHeadDim = 64;
 constexpr int kMaxSeqLen = 2048;
 constexpr int kNumHeads = 4;
+constexpr int kTileKV = 64;     // keys per LDS tile
+constexpr int kMaxSplits = 16;  // KV splits per query group (combine loads them all in one round)
 
 enum class InType { F16, F32 };
 enum class OutType { F16, F32 };
@@ -28,18 +30,6 @@ struct Call {
     int nkv;
 };
 
-// Launch-shape choice for one call (exposed so tests/bench can force a variant).
-struct LaunchPlan {
-    int q_waves;          // waves per workgroup that own distinct 32-row query slices
-    int kv_waves;         // waves per workgroup that split the keys of every iteration
-    int rows_per_wave;    // 32, or 64 (two query blocks per wave); 16: the 16-row single-pass kernel
-    int splits;           // KV split across workgroups (1 = no combine pass)
-    int tiles_per_split;  // KV super-tiles (64 * kv_waves keys) per split
-    size_t ws_needed;     // workspace bytes the plan uses
-    int direct_tiles;     // > 0: single-pass kernel, 8 waves x direct_tiles 64-key tiles (no split)
-    int stream;           // 1: the persistent streaming kernel (128-row items, no split)
-};
-
 // Up to kGroupCalls calls share one launch (grouped launcher); larger groups are chunked.
 constexpr int kGroupCalls = 4;
 
@@ -48,9 +38,9 @@ constexpr int kGroupCalls = 4;
 struct GroupPlan {
     int q_waves;
     int kv_waves;
-    int rows_per_wave;  // 32 or 64 (two query blocks per wave share every K/V fragment read)
-    int splits[kGroupCalls];
-    int tiles_per_split[kGroupCalls];
+    int rows_per_wave;  // 32, or 64 (two query blocks per wave share every K/V fragment read); 16: the 16-row kernel
+    int splits[kGroupCalls];           // KV split across workgroups (1 = no combine pass)
+    int tiles_per_split[kGroupCalls];  // KV super-tiles (64 * kv_waves keys) per split
     size_t ws_offset[kGroupCalls];
     size_t ws_needed;
     int direct_tiles;  // > 0: the single-pass kernel (mha_hd64_direct.hip), q_waves 1 x kv_waves 8
@@ -62,8 +52,36 @@ constexpr int kForceDirect = 21;
 constexpr int kForceDirect16 = 22;
 // force_q_waves = kForceStream selects the persistent streaming kernel (mha_hd64_stream.hip).
 constexpr int kForceStream = 23;
+// The plan as the test hooks report and force it: 21 / 22 / 23, or q_waves (+ 10 with 64-row waves).
+inline int plan_code(const GroupPlan& p) {
+    if (p.stream) return kForceStream;
+    if (p.direct_tiles > 0) return p.rows_per_wave == 16 ? kForceDirect16 : kForceDirect;
+    return p.q_waves + (p.rows_per_wave == 64 ? 10 : 0);
+}
+// Workgroup shapes compiled (mha_hd64_ring.hip): (q_waves, kv_waves) in {(4,1), (2,2), (1,2), (4,2),
+// (2,4), (1,4), (1,8)} with 32-row waves, and (2,2) with 64-row waves (forced as q_waves = 12).
+bool valid_shape(int q_waves, int kv_waves, int row_blocks);
 GroupPlan plan_group(const Call* calls, int n, size_t ws_bytes, int force_q_waves = 0, int force_kv_waves = 0,
                      int force_splits = 0, InType in = InType::F16);
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+size_t split_workspace_bytes(const Call& c, int splits);
+// Workspace bytes of the fp16 copy of `rows` rows per (batch, head) of call c (the convert route).
+inline size_t f16_copy_bytes(const Call& c, int rows) {
+    return align256((size_t)c.batch * c.heads * rows * kHeadDim * 2);
+}
+
+// How one launch (a chunk of n <= kGroupCalls calls) runs: the planner's plan for its input type,
+// or for fp32 inputs one of the two routes onto the fp16 single-pass / streaming kernels.
+enum class Route { Planned, F32InKernel, F32Convert };
+struct ChunkRoute {
+    Route route;
+    GroupPlan plan;   // the plan to launch (F32InKernel: the fp16 16-row plan; F32Convert: the fp16 plan)
+    size_t ws_bytes;  // workspace the route uses: split partials, or the fp16 copies of Q, K, V
+};
+// The one routing decision of a launch, shared by the launcher and the workspace query
+// (ws_bytes = (size_t)-1 with has_workspace: what the launch would use at best).
+ChunkRoute route_chunk(const Call* calls, int n, InType in, size_t ws_bytes, bool has_workspace,
+                       int force_q_waves = 0, int force_kv_waves = 0, int force_splits = 0);
 // lens (non-null only with force_q_waves = kForceStream and fp16 inputs): lens[i] is a device table of
 // calls[i].batch int32 key counts, or null; item b of call i attends to its first lens[i][b] keys
 // (clamped into [1, nkv] in the kernel). qlens (with lens only; may be null): the same for query rows
@@ -75,12 +93,6 @@ hipError_t launch_group(const Call* calls, int n, InType in, OutType out, void* 
 // chunk's need (chunks of kGroupCalls reuse the workspace in stream order) -- split partials, or
 // for fp32 inputs the fp16 copies the convert launch writes when a single-pass kernel runs them.
 size_t group_workspace_bytes(const Call* calls, int n, InType in = InType::F16);
-
-// Workgroup shapes compiled: (q_waves, kv_waves) in {(4,1), (2,2), (1,2), (4,2)} with 32-row waves,
-// and (2,2) with 64-row waves (forced as q_waves = 12).
-LaunchPlan plan_call(const Call& c, size_t ws_bytes, int force_q_waves = 0, int force_kv_waves = 0,
-                     int force_splits = 0, InType in = InType::F16);
-size_t split_workspace_bytes(const Call& c, int splits);
 
 // Returns hipSuccess or the launch error. phase_mask (measurement hook): bit 0 = main
 // kernel, bit 1 = split-KV combine kernel.

@@ -307,10 +307,7 @@ int32_t mha_hd64_launch_fp32in_fp32out(const void* q, const void* k, const void*
 }
 
 size_t mha_hd64_launch_workspace_bytes(int32_t batch, int32_t heads, int32_t nq, int32_t nkv) {
-    if (batch <= 0 || heads <= 0 || nq <= 0 || nkv <= 0) return 0;
-    const mha_hd64::Call c{nullptr, nullptr, nullptr, nullptr, batch, heads, nq, nkv};
-    // Plan with an unbounded workspace to learn what the preferred split needs.
-    return mha_hd64::plan_call(c, (size_t)-1).ws_needed;
+    return mha_hd64_launch_workspace_bytes_typed(batch, heads, nq, nkv, MHA_HD64_DT_HALF);
 }
 
 size_t mha_hd64_launch_workspace_bytes_typed(int32_t batch, int32_t heads, int32_t nq, int32_t nkv, int32_t in_type) {
@@ -439,13 +436,10 @@ int32_t mha_hd64_launch_forced(const void* q, const void* k, const void* v, void
     if (batch == 0 || heads == 0 || nq == 0) return MHA_HD64_STATUS_SUCCESS;
     MHA_CHECK(nkv >= 1);
     const mha_hd64::Call c{q, k, v, o, batch, heads, nq, nkv};
-    const mha_hd64::LaunchPlan plan =
-        mha_hd64::plan_call(c, workspace ? ws_bytes : 0, q_waves, kv_waves, splits,
-                            in_f32 ? mha_hd64::InType::F32 : mha_hd64::InType::F16);
-    const int plan_qw = plan.stream ? mha_hd64::kForceStream
-                        : plan.direct_tiles > 0
-                            ? (plan.rows_per_wave == 16 ? mha_hd64::kForceDirect16 : mha_hd64::kForceDirect)
-                            : plan.q_waves + (plan.rows_per_wave == 64 ? 10 : 0);
+    const mha_hd64::GroupPlan plan =
+        mha_hd64::plan_group(&c, 1, workspace ? ws_bytes : 0, q_waves, kv_waves, splits,
+                             in_f32 ? mha_hd64::InType::F32 : mha_hd64::InType::F16);
+    const int plan_qw = mha_hd64::plan_code(plan);
     // (2,4), (1,4), (1,8) take one split per super-tile and fall back to (2,2) past 16 of them
     const bool single_tile = kv_waves >= 4;
     const bool fell_back = single_tile && plan_qw == 2 && plan.kv_waves == 2;
@@ -458,7 +452,7 @@ int32_t mha_hd64_launch_forced(const void* q, const void* k, const void* v, void
                     "single-pass / streaming kernel: fp16 input, nkv <= 1024 (16-row) / 2048 (32-row)");
     if (q_waves != 0 && !direct && !fell_back && (plan_qw != q_waves || plan.kv_waves != kv_waves))
         return fail(MHA_HD64_STATUS_BAD_PARAM, __FILE__, __LINE__, "forced workgroup shape is not compiled");
-    if (splits > 1 && !single_tile && !direct && plan.splits != splits)
+    if (splits > 1 && !single_tile && !direct && plan.splits[0] != splits)
         return fail(MHA_HD64_STATUS_WORKSPACE, __FILE__, __LINE__, "forced split does not fit the workspace/keys");
     return launch_status(mha_hd64::launch_attention(c, in_f32 ? mha_hd64::InType::F32 : mha_hd64::InType::F16,
                                                     out_f32 ? mha_hd64::OutType::F32 : mha_hd64::OutType::F16,
@@ -484,16 +478,37 @@ int32_t mha_hd64_last_combine_form(void) { return mha_hd64::last_combine_form();
 // Plan query hook for tests/bench: fills {q_waves, kv_waves, splits, tiles_per_split}; returns workspace bytes.
 size_t mha_hd64_plan(int32_t batch, int32_t heads, int32_t nq, int32_t nkv, size_t ws_bytes, int32_t* out4) {
     const mha_hd64::Call c{nullptr, nullptr, nullptr, nullptr, batch, heads, nq, nkv};
-    const mha_hd64::LaunchPlan p = mha_hd64::plan_call(c, ws_bytes);
+    const mha_hd64::GroupPlan p = mha_hd64::plan_group(&c, 1, ws_bytes);
     if (out4) {
-        out4[0] = p.stream ? mha_hd64::kForceStream
-                  : p.direct_tiles > 0 ? (p.rows_per_wave == 16 ? mha_hd64::kForceDirect16 : mha_hd64::kForceDirect)
-                                       : p.q_waves + (p.rows_per_wave == 64 ? 10 : 0);
+        out4[0] = mha_hd64::plan_code(p);
         out4[1] = p.kv_waves;
-        out4[2] = p.splits;
-        out4[3] = p.tiles_per_split;
+        out4[2] = p.splits[0];
+        out4[3] = p.tiles_per_split[0];
     }
     return p.ws_needed;
+}
+
+// Routing query hook for tests (include/mha_hd64.h): one launch as launch_group_chunk routes it.
+size_t mha_hd64_plan_route(const mha_hd64_call_t* calls, int32_t n, int32_t in_type, size_t ws_bytes,
+                           int32_t has_workspace, int32_t q_waves, int32_t kv_waves, int32_t force_splits,
+                           int32_t* out5, int32_t* splits, int32_t* tiles_per_split, size_t* ws_offset) {
+    if (!calls || n < 1 || n > mha_hd64::kGroupCalls || !out5 || !splits || !tiles_per_split || !ws_offset)
+        return (size_t)-1;
+    mha_hd64::Call c[mha_hd64::kGroupCalls];
+    for (int i = 0; i < n; ++i)
+        c[i] = mha_hd64::Call{nullptr, nullptr, nullptr, nullptr, calls[i].batch, calls[i].heads, calls[i].nq, calls[i].nkv};
+    const mha_hd64::ChunkRoute r =
+        mha_hd64::route_chunk(c, n, in_type == MHA_HD64_DT_FLOAT ? mha_hd64::InType::F32 : mha_hd64::InType::F16,
+                              ws_bytes, has_workspace != 0, q_waves, kv_waves, force_splits);
+    const int32_t head[5] = {(int32_t)r.route, mha_hd64::plan_code(r.plan), r.plan.kv_waves, r.plan.rows_per_wave,
+                             r.plan.direct_tiles};
+    std::memcpy(out5, head, sizeof(head));
+    for (int i = 0; i < n; ++i) {
+        splits[i] = r.plan.splits[i];
+        tiles_per_split[i] = r.plan.tiles_per_split[i];
+        ws_offset[i] = r.plan.ws_offset[i];
+    }
+    return r.ws_bytes;
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// mha_hd64_kernels.hip — fused FlashAttention-v2 forward, head_dim = 64, for gfx950 (MI355X, CDNA4).
+// mha_hd64_ring.hip — fused FlashAttention-v2 forward, head_dim = 64, for gfx950 (MI355X, CDNA4).
 //
 // Computes, per (batch, head):  O = softmax(Q·Kᵀ · 0.125) · V
 // the operator of the reference's TensorRT plugin "MHAHeadDim64"
@@ -37,13 +37,7 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <utility>
-#include <vector>
 
 #include "mha_hd64_device.h"
 #include "mha_hd64_internal.h"
@@ -881,386 +875,11 @@ hipError_t launch_combine(const CombineArgs& c, hipStream_t stream) {
     return hipGetLastError();
 }
 
-bool valid_shape(int qw, int kw, int rb) {
-    if (rb == 2) return qw == 2 && kw == 2;
-    return rb == 1 && ((qw == 4 && kw == 1) || (qw == 2 && kw == 2) || (qw == 1 && kw == 2) || (qw == 4 && kw == 2) ||
-                       (qw == 2 && kw == 4) || (qw == 1 && kw == 4) || (qw == 1 && kw == 8));
-}
-
-unsigned long long* g_stamps = nullptr;  // diagnostic builds (MHA_STAMPS) only
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-}  // namespace
-
-void set_stamp_buffer(void* p) { g_stamps = reinterpret_cast<unsigned long long*>(p); }
-
-// ---- arrival tickets of the in-launch combine ----
-// Every ticket a launch uses is zero when it starts and zero when it ends (the last arriver of
-// each group resets its own), so a ticket array needs no per-call reset as long as no two launches
-// that use it run concurrently:
-//  * eager launches: one array per (device, stream) -- launches on one stream are serialised;
-//  * launches recorded under stream capture: a slice of their own, carved from a per-device arena
-//    (an instantiated graph never runs concurrently with itself, while two graphs captured on one
-//    stream may be replayed side by side).
-// Arrays are created only outside capture (hipMalloc + memset, then a one-time stream sync for the
-// arena); a launch that finds no tickets combines in the second kernel instead. Nothing is freed
-// (a launch in flight or a graph may still reference it). A half-used arena is replaced at the
-// next eager launch (tickets_for), at most kMaxArenas times per device: memory for tickets is
-// bounded by (kMaxArenas + 1) x 4 MiB per device plus the per-stream arrays; past the cap, captures
-// that find the arena full use the combine kernel (same bits). So an EAGER split launch may
-// allocate device memory (never more than that bound); it does so with this thread's capture mode
-// exchanged to relaxed, so a global-mode capture running on another thread stays valid.
-namespace {
-int g_fused = -1;  // -1: unset (env MHA_HD64_FUSED_COMBINE, default on), 0 off, 1 on
-std::mutex g_ticket_mu;
-std::map<std::pair<int, hipStream_t>, std::pair<unsigned*, int>> g_tickets;
-struct Arena {
-    unsigned* base = nullptr;
-    int cap = 0;
-    int used = 0;
-    int replaced = 0;
-};
-std::map<int, Arena> g_arena;
-thread_local int g_last_combine = 0;  // this thread's last launch: 0 no split, 1 in-launch, 2 kernel
-constexpr int kArenaTickets = 1 << 20;  // 4 MiB per device
-constexpr int kMaxArenas = 4;           // replacements per device
-// Scoped relaxed capture mode for this thread: allocation calls stay legal (and do not invalidate
-// another thread's global-mode capture) while any capture is in progress in the process.
-struct RelaxedCapture {
-    hipStreamCaptureMode prev = hipStreamCaptureModeRelaxed;
-    RelaxedCapture() { (void)hipThreadExchangeStreamCaptureMode(&prev); }
-    ~RelaxedCapture() { (void)hipThreadExchangeStreamCaptureMode(&prev); }
-};
-}  // namespace
-
-int last_combine_form() { return g_last_combine; }
-
-namespace {
-std::atomic<int> g_concurrency{1};
-}
-int concurrency_hint() { return g_concurrency.load(std::memory_order_relaxed); }
-int set_concurrency_hint(int streams) { return g_concurrency.exchange(std::max(1, streams)); }
-
-void set_fused_combine(int enable) {
-    std::lock_guard<std::mutex> lk(g_ticket_mu);
-    g_fused = enable ? 1 : 0;
-}
-
-static bool fused_enabled() {
-    std::lock_guard<std::mutex> lk(g_ticket_mu);
-    if (g_fused < 0) {
-        const char* e = std::getenv("MHA_HD64_FUSED_COMBINE");
-        g_fused = (e && e[0] == '0') ? 0 : 1;
-    }
-    return g_fused == 1;
-}
-
-static unsigned* zeroed_tickets(int count, hipStream_t stream) {
-    unsigned* p = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&p), (size_t)count * sizeof(unsigned)) != hipSuccess) return nullptr;
-    if (hipMemsetAsync(p, 0, (size_t)count * sizeof(unsigned), stream) != hipSuccess) {
-        (void)hipFree(p);
-        return nullptr;
-    }
-    return p;
-}
-
-static unsigned* tickets_for(hipStream_t stream, int count) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_ticket_mu);
-    Arena& ar = g_arena[dev];
-    if (cs != hipStreamCaptureStatusNone) {  // a slice owned by this recorded launch
-        const int n = (count + 63) & ~63;
-        if (!ar.base || ar.used + n > ar.cap) return nullptr;
-        unsigned* p = ar.base + ar.used;
-        ar.used += n;
-        return p;
-    }
-    // First eager launch on this device: the arena for later captures. An arena more than half
-    // carved is replaced by a fresh one at the next eager launch (the old one stays allocated: graphs
-    // recorded from it may still run), at most kMaxArenas times, so captures run out only after
-    // 512 Ki tickets recorded with no eager launch in between.
-    RelaxedCapture relaxed;
-    if (!ar.base || (ar.used > ar.cap / 2 && ar.replaced < kMaxArenas)) {
-        unsigned* fresh = zeroed_tickets(kArenaTickets, stream);
-        if (fresh && hipStreamSynchronize(stream) == hipSuccess) {
-            if (ar.base) ++ar.replaced;  // (counted only once a fresh arena is installed)
-            ar.base = fresh;
-            ar.cap = kArenaTickets;
-            ar.used = 0;
-        } else {
-            if (fresh) (void)hipFree(fresh);  // a failed attempt leaks nothing
-            if (!ar.base) ar.cap = 0;
-        }
-    }
-    auto& slot = g_tickets[{dev, stream}];
-    if (slot.first && slot.second >= count) return slot.first;
-    const int cap = std::max(count, 4096);
-    unsigned* p = zeroed_tickets(cap, stream);
-    if (!p) return nullptr;
-    slot = {p, cap};
-    return p;
-}
-
-size_t split_workspace_bytes(const Call& c, int splits) {
-    if (splits <= 1) return 0;
-    const size_t rows = (size_t)c.batch * c.heads * splits * c.nq;
-    const size_t o_bytes = rows * kHeadDim * sizeof(float);  // fp32 bound (fp16 partials use half)
-    return align256(o_bytes) + align256(rows * sizeof(float2));
-}
-
-static bool direct_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("MHA_HD64_DIRECT");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// Tiles of 64 keys per wave of the single-pass kernels for this launch, or 0 if they do not apply:
-// fp16 input, every call's keys within 8 waves x 2 tiles (x 2 passes for 32-row blocks), and at most max_wgs workgroups of `rows`
-// query rows. 16-row blocks: at most 256 (one per CU, one round). 32-row blocks: at most 768 —
-// up to three rounds of 256 still beat the LDS ring's plans there (tools/batch_sweep.py, graph
-// replay, us per launch, 32-row kernel vs planner's ring plan: B=3 N=1024 10.3 vs 18.1, B=6 15.3 vs
-// 19.7, B=6 N=512 6.3 vs 9.5, B=12 N=512 8.7 vs 13.5; at 1024 blocks the ring wins: B=8 N=1024
-// 15.5 vs 21.0, B=16 N=512 10.4 vs 11.2). Past one round with 512 < nkv <= 1024 the 32-row kernel
-// runs its two-workgroups-per-CU form (launch_direct): B=3 8.86 vs 10.28 for one per CU (ring
-// 10.43), B=4 9.41 vs 10.68 (10.77), B=6 13.15 vs 15.23 (14.11); B=8 16.85 vs ring 15.33.
-constexpr long kDirectMaxWgs16 = 256, kDirectMaxWgs32 = 768;
-static int direct_tiles_for(const Call* calls, int n, InType in, bool forced, int rows = 32) {
-    if (in != InType::F16 || (!forced && !direct_enabled())) return 0;
-    long wgs = 0;
-    int tiles = 1;
-    // keys per call: <= 2048 (tiles 3, 4: the two-pass forms, 4 waves x 2 x 4 tiles)
-    const int max_tiles = 4;
-    for (int i = 0; i < n; ++i) {
-        if (calls[i].nkv > 8 * max_tiles * kTileKV) return 0;
-        tiles = std::max(tiles, (calls[i].nkv + 8 * kTileKV - 1) / (8 * kTileKV));
-        wgs += (long)calls[i].batch * calls[i].heads * ((calls[i].nq + rows - 1) / rows);
-    }
-    // two-pass forms (tiles 3, 4), one round: 16-row blocks up to 256, 32-row blocks from 96 on (tools/batch_sweep.py, us per launch, two-pass 16-row / 32-row
-    // kernel vs ring plan: 2048^2 B=1 - / 9.87 vs 13.04, B=2 - / 17.6 vs 17.3; 1536^2 B=1 - / 8.13
-    // vs 11.12; Nq x Nkv 1024x2048 7.40 / 8.57 vs 10.74, 768x2048 6.79 / 8.38 vs 10.24,
-    // 512x2048 6.68 / 8.33 vs 7.95, 256x2048 6.61 / 8.31 vs 7.69, 1024x1536 6.32 / 8.05 vs 9.84)
-    // Past one round the 32-row kernel's two-workgroups-per-CU form (4 passes x 2 tiles) takes
-    // over up to 768 blocks (vs the ring plan: 2x4x2048^2 16.1 vs 17.8, 3x 21.7 vs 23.3; 2x4x1536^2
-    // 12.0 vs 13.5, 3x 18.0 vs 17.7, 4x 18.6 vs 18.7; 4x4x1024x2048 15.0 vs 17.8).
-    if (tiles > 2 && !forced && (rows == 16 ? wgs > 256 : wgs < 96)) return 0;
-    const long max_wgs = rows == 16 ? kDirectMaxWgs16 : kDirectMaxWgs32;
-    return (forced || wgs <= max_wgs) ? tiles : 0;
-}
-
-// The 16-row single-pass kernel first (default; MHA_HD64_DIRECT_ROWS=32 keeps 32-row blocks)
-static bool direct16_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("MHA_HD64_DIRECT_ROWS");
-        return !(e && e[0] == '3');
-    }();
-    return on;
-}
-
-// The persistent streaming kernel (mha_hd64_stream.hip) for fp16 launches of more than one round
-// of 128-row blocks (MHA_HD64_STREAM=1 / set_stream_mode(1), the default; 0: never). Round 4's
-// branch-free step loop: 16 batched 1x4x1024^2 calls 23.6 vs 26.0 us for the ring kernel, 32
-// calls 44.2 vs 49.8 (profiles/r04/stream_check.jsonl).
-std::atomic<int> g_stream_mode{-1};
-int stream_env() {
-    int v = g_stream_mode.load();
-    if (v < 0) {
-        const char* e = std::getenv("MHA_HD64_STREAM");
-        int expect = -1;
-        g_stream_mode.compare_exchange_strong(expect, (e && e[0] == '0') ? 0 : 1);
-        v = g_stream_mode.load();
-    }
-    return v;
-}
-static bool stream_auto(const Call* calls, int n, InType in) {
-    if (in != InType::F16 || stream_env() <= 0) return false;
-    long blocks128 = 0;
-    for (int i = 0; i < n; ++i) blocks128 += (long)calls[i].batch * calls[i].heads * ((calls[i].nq + 127) / 128);
-    return blocks128 > 256;
-}
-
-GroupPlan plan_group(const Call* calls, int n, size_t ws_bytes, int force_q_waves, int force_kv_waves,
-                     int force_splits, InType in) {
-    GroupPlan p{};
-    if (force_q_waves == kForceStream || (force_q_waves == 0 && stream_auto(calls, n, in))) {
-        if (in == InType::F16) {
-            // 8 waves (256-row items, one workgroup per CU: the two waves of a SIMD stay in step, no
-            // co-resident imbalance) when their last round of 256 items is at least 3/4 full; else
-            // 4 (128-row items, two per CU: the older workgroup of a CU takes the extra items of a
-            // partial round). tools/stream_check.py, 1024^2 calls per launch, us: 12 calls 20.0 vs
-            // 21.1, 16: 22.5 vs 23.4, 24: 38.5 vs 34.0, 32: 43.3 vs 44.7, 64: 81.1 vs 84.3.
-            // force_kv_waves 4 / 8 (forced plan 23) picks one.
-            long blocks256 = 0;
-            for (int i = 0; i < n; ++i) blocks256 += (long)calls[i].batch * calls[i].heads * ((calls[i].nq + 255) / 256);
-            const long rounds8 = (blocks256 + 255) / 256;
-            const int nw = (force_q_waves == kForceStream && (force_kv_waves == 4 || force_kv_waves == 8))
-                               ? force_kv_waves
-                               : (4 * (256 * rounds8 - blocks256) <= 256 ? 8 : 4);
-            p.q_waves = nw;  // items of 32·nw rows
-            p.kv_waves = nw;  // (reported by the plan query)
-            p.rows_per_wave = 32;
-            p.stream = 1;
-            for (int i = 0; i < n; ++i) {
-                p.splits[i] = 1;
-                p.tiles_per_split[i] = 1;
-            }
-            return p;
-        }
-        force_q_waves = 0;  // fp32 inputs: the planner's choice
-    }
-    // 16-row blocks first: a launch of at most 256 of them runs every block on its own CU. Under a
-    // concurrency hint >= 2 (several streams of independent calls) a call takes 32-row blocks on
-    // half the CUs instead (launch_direct: two-per-CU form from hint 3), so the streams overlap.
-    if (force_q_waves == kForceDirect16 ||
-        (force_q_waves == 0 && direct16_enabled() && concurrency_hint() < 2)) {
-        const int dt = direct_tiles_for(calls, n, in, force_q_waves == kForceDirect16, 16);
-        if (dt > 0) {
-            p.q_waves = 1;
-            p.kv_waves = 4;
-            p.rows_per_wave = 16;
-            p.direct_tiles = dt;
-            for (int i = 0; i < n; ++i) {
-                p.splits[i] = 1;
-                p.tiles_per_split[i] = 1;
-            }
-            return p;
-        }
-        if (force_q_waves == kForceDirect16) force_q_waves = 0;  // not applicable: the planner's choice
-    }
-    if (force_q_waves == kForceDirect || force_q_waves == 0) {
-        const int dt = direct_tiles_for(calls, n, in, force_q_waves == kForceDirect);
-        if (dt > 0) {
-            p.q_waves = 1;
-            p.kv_waves = 8;
-            p.rows_per_wave = 32;
-            p.direct_tiles = dt;
-            for (int i = 0; i < n; ++i) {
-                p.splits[i] = 1;
-                p.tiles_per_split[i] = 1;
-            }
-            return p;
-        }
-        if (force_q_waves == kForceDirect) force_q_waves = 0;  // not applicable: the planner's choice
-    }
-    // Forced shapes (test/bench hook): q_waves >= 10 selects 64-row waves (RB = 2) of q_waves - 10.
-    int rb = force_q_waves >= 10 ? 2 : 1;
-    int qw = force_q_waves >= 10 ? force_q_waves - 10 : force_q_waves, kw = force_kv_waves;
-    if (!valid_shape(qw, kw, rb)) {
-        rb = 1;
-        long blocks128 = 0;
-        for (int i = 0; i < n; ++i) blocks128 += (long)calls[i].batch * calls[i].heads * ((calls[i].nq + 127) / 128);
-        // (bench.py --sweep, profiles/r01/ring_plan_sweep.json; eager us per launch)
-        if (blocks128 > 256) {
-            // more than one round of 128-row blocks: 4 waves (48 KiB LDS, several workgroups per
-            // CU) beat (4,2)'s 8 (96 KiB, one per CU): 1024^2 B=16 29.3 vs 33.1, 2048^2 B=8 51.5
-            // vs 57.1, 1536^2 B=8 36.3 vs 40.8
-            qw = 4;
-            kw = 1;
-        } else if (blocks128 > 128) {
-            // one round of 128-row blocks: (4,2), no cross-WG split (1536^2 B=3 21.6 vs 29.0 for
-            // the (2,2) split plans, B=4 22.6 vs 29.8; 1024^2 B=8 18.8 vs 19.6 for (4,1))
-            qw = 4;
-            kw = 2;
-        } else {
-            qw = 2;
-            kw = 2;
-            // A launch that does not fill the chip with 64-row blocks: one super-tile per split
-            // (single-stage LDS ring, straight-line body) while the grid stays within one
-            // residency round. First choice (1,8): 32 rows x 512 keys per workgroup (128 KiB
-            // LDS, one workgroup per CU, <= 256 of them): half the splits of (2,4), so half the
-            // partial round trip; else (2,4): 64 rows x 256 keys (72 KiB, two per CU, <= 512).
-            long g64 = 0, wgs4 = 0, wgs8 = 0;
-            bool fits4 = true, fits8 = true;
-            for (int i = 0; i < n; ++i) {
-                const long b = (long)calls[i].batch * calls[i].heads;
-                const long g = b * ((calls[i].nq + 63) / 64);
-                const long st4 = (calls[i].nkv + 255) / 256, st8 = (calls[i].nkv + 511) / 512;
-                fits4 = fits4 && st4 <= kMaxSplits;
-                fits8 = fits8 && st8 <= kMaxSplits;
-                g64 += g;
-                wgs4 += g * st4;
-                wgs8 += b * ((calls[i].nq + 31) / 32) * st8;
-            }
-            if (g64 < 256 && fits8 && wgs8 <= 256) {
-                qw = 1;
-                kw = 8;
-            } else if (g64 < 256 && fits4 && wgs4 <= 512) {
-                kw = 4;
-            }
-        }
-    }
-    p.q_waves = qw;
-    p.kv_waves = kw;
-    p.rows_per_wave = 32 * rb;
-    const int block_m = 32 * qw * rb;
-    long groups = 0;
-    for (int i = 0; i < n; ++i)
-        groups += (long)calls[i].batch * calls[i].heads * ((calls[i].nq + block_m - 1) / block_m);
-    // splits: as many as keep the grid within one round of 256 workgroups (a second partial
-    // round costs more than the split saves: 1536^2 B=1 (2,2) 3-way 19.1 vs 2-way 13.9 us)
-    int want = force_splits > 0 ? force_splits : (int)std::max(1L, 256 / std::max(1L, groups));
-    want = std::max(1, std::min(want, kMaxSplits));
-    if (kw >= 4) {
-        // single-super-tile shapes: every split must be exactly one super-tile (their LDS ring
-        // has one stage); otherwise (too many keys, or no workspace for the partials) use (2,2).
-        size_t off = 0;
-        bool ok = true;
-        for (int i = 0; i < n; ++i) {
-            const int super_total = std::max(1, (calls[i].nkv + 64 * kw - 1) / (64 * kw));
-            ok = ok && super_total <= kMaxSplits;
-            p.splits[i] = super_total;
-            p.tiles_per_split[i] = 1;
-            p.ws_offset[i] = off;
-            off += split_workspace_bytes(calls[i], super_total);
-        }
-        p.ws_needed = off;
-        if (ok && off <= ws_bytes) return p;
-        return plan_group(calls, n, ws_bytes, 2, 2, force_splits, in);
-    }
-    for (;;) {
-        size_t off = 0;
-        for (int i = 0; i < n; ++i) {
-            const int super_total = std::max(1, (calls[i].nkv + 64 * kw - 1) / (64 * kw));
-            const int w = std::min(want, super_total);
-            p.tiles_per_split[i] = (super_total + w - 1) / w;
-            p.splits[i] = (super_total + p.tiles_per_split[i] - 1) / p.tiles_per_split[i];
-            p.ws_offset[i] = off;
-            off += split_workspace_bytes(calls[i], p.splits[i]);
-        }
-        p.ws_needed = off;
-        if (want <= 1 || off <= ws_bytes) break;
-        --want;
-    }
-    return p;
-}
-
-LaunchPlan plan_call(const Call& c, size_t ws_bytes, int force_q_waves, int force_kv_waves, int force_splits,
-                     InType in) {
-    const GroupPlan g = plan_group(&c, 1, ws_bytes, force_q_waves, force_kv_waves, force_splits, in);
-    LaunchPlan p{};
-    p.q_waves = g.q_waves;
-    p.kv_waves = g.kv_waves;
-    p.rows_per_wave = g.rows_per_wave;
-    p.splits = g.splits[0];
-    p.tiles_per_split = g.tiles_per_split[0];
-    p.ws_needed = g.ws_needed;
-    p.direct_tiles = g.direct_tiles;
-    p.stream = g.stream;
-    return p;
-}
 
 // ---- Float boundary onto the single-pass kernels ----
 // fp32 Q/K/V of launches the single-pass kernels take (as fp16) are rounded to fp16 (RNE, the
 // reference's convert kernel …fp16in_fp32out.cu:706-804 without its padding) into the caller's
 // workspace by one elementwise launch, then run there; the LDS-ring kernel converts on load instead.
-namespace {
-constexpr int kConvMax = 3 * kMaxCalls;
 struct ConvArgs {
     const float* src[kConvMax];
     f16* dst[kConvMax];
@@ -1281,200 +900,35 @@ __global__ __launch_bounds__(256) void convert_f32_f16_kernel(ConvArgs c) {
     reinterpret_cast<f16x8*>(c.dst[t])[idx] = f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
-bool f32_convert_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("MHA_HD64_F32_CONVERT");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-// fp32 inputs rounded inside the 16-row kernel (one launch) where its one-pass forms apply
-// (MHA_HD64_F32_INKERNEL=0 or set_f32_inkernel(0): the convert launch + fp16 kernel instead)
-std::atomic<int> g_f32_inkernel{-1};
-bool f32_inkernel_enabled() {
-    int v = g_f32_inkernel.load();
-    if (v < 0) {
-        const char* e = std::getenv("MHA_HD64_F32_INKERNEL");
-        int expect = -1;
-        g_f32_inkernel.compare_exchange_strong(expect, (e && e[0] == '0') ? 0 : (e && e[0] == '2') ? 2 : 1);
-        v = g_f32_inkernel.load();
-    }
-    return v >= 1;
-}
-// 2 (MHA_HD64_F32_INKERNEL=2 / set_f32_inkernel(2)): the two-pass forms (1024 < nkv <= 2048) round
-// fp32 in the kernel too. Diagnostic: measured slower than convert + fp16 kernel.
-bool f32_inkernel_two_pass() { return f32_inkernel_enabled() && g_f32_inkernel.load() == 2; }
 }  // namespace
 
-void set_f32_inkernel(int enable) { g_f32_inkernel.store(enable <= 0 ? 0 : enable >= 2 ? 2 : 1); }
-int set_stream_mode(int mode) {
-    const int prev = stream_env();
-    g_stream_mode.store(mode ? 1 : 0);
-    return prev;
+// The launchers below are what the host side (mha_hd64_launch.hip) sees of this file; the kernels'
+// argument structs stay in the anonymous namespace (their names are part of the kernels' symbols).
+bool valid_shape(int qw, int kw, int rb) {
+    if (rb == 2) return qw == 2 && kw == 2;
+    return rb == 1 && ((qw == 4 && kw == 1) || (qw == 2 && kw == 2) || (qw == 1 && kw == 2) || (qw == 4 && kw == 2) ||
+                       (qw == 2 && kw == 4) || (qw == 1 && kw == 4) || (qw == 1 && kw == 8));
 }
 
-static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutType out, void* workspace,
-                                     size_t ws_bytes, hipStream_t stream, int force_q_waves, int force_kv_waves,
-                                     int force_splits, int phase_mask, const int* const* lens = nullptr,
-                                     const int* const* qlens = nullptr);
-
-// Whether an fp32-input launch whose fp16 plan is p16 takes the convert launch + that fp16 kernel
-// (true) or the ring kernel rounding fp32 on load (false). The 32-row single-pass kernel after a
-// convert loses to the ring kernel past one round of its blocks and at short key ranges, where
-// the ring kernel's 128-row blocks share each K/V tile over four query waves (tools/f32_routes.py,
-// profiles/r03/f32_routes.jsonl, us per launch, convert + 32-row kernel vs ring: 4x4x1024^2 16.4
-// vs 13.9, 4x4x512^2 8.7 vs 7.6; kept: 2x4x1024^2 10.4 vs 12.8, 2x4x2048^2 22.4 vs 22.1).
-static bool f32_convert_route(const Call* calls, int n, const GroupPlan& p16) {
-    if (p16.stream) return true;
-    if (p16.direct_tiles == 0) return false;
-    if (p16.rows_per_wave == 16) return true;  // the 16-row kernel's two-pass forms (nkv > 1024)
-    long blocks = 0;
-    int max_nkv = 0;
-    for (int i = 0; i < n; ++i) {
-        blocks += (long)calls[i].batch * calls[i].heads * ((calls[i].nq + 31) / 32);
-        max_nkv = std::max(max_nkv, calls[i].nkv);
-    }
-    return blocks <= 256 && max_nkv > 512;
+hipError_t launch_ring(const FwdArgs& a, int grid, int qw, int kw, int rb, bool in_f32, bool out_f32,
+                       hipStream_t stream) {
+    if (!in_f32)
+        return out_f32 ? launch_fwd_shape<f16, float>(a, grid, qw, kw, rb, stream)
+                       : launch_fwd_shape<f16, f16>(a, grid, qw, kw, rb, stream);
+    return out_f32 ? launch_fwd_shape<float, float>(a, grid, qw, kw, rb, stream)
+                   : launch_fwd_shape<float, f16>(a, grid, qw, kw, rb, stream);
 }
 
-// The convert + single-pass form of an fp32-input launch, or hipErrorNotSupported when it does
-// not apply (not the planner's choice, no single-pass plan for these shapes, workspace too small).
-static hipError_t launch_f32_via_f16(const Call* calls, int n, OutType out, void* workspace, size_t ws_bytes,
-                                     hipStream_t stream, int phase_mask) {
-    if (!f32_convert_enabled() || !workspace) return hipErrorNotSupported;
-    const GroupPlan p16 = plan_group(calls, n, 0, 0, 0, 0, InType::F16);
-    if (!f32_convert_route(calls, n, p16)) return hipErrorNotSupported;
-    Call c16[kMaxCalls];
-    ConvArgs cv{};
-    size_t off = 0;
-    unsigned total8 = 0;
-    char* ws = reinterpret_cast<char*>(workspace);
-    for (int i = 0; i < n; ++i) {
-        c16[i] = calls[i];
-        if (calls[i].nq <= 0 || calls[i].batch <= 0 || calls[i].heads <= 0) continue;
-        const size_t bh = (size_t)calls[i].batch * calls[i].heads;
-        const size_t elems[3] = {bh * calls[i].nq * kHeadDim, bh * calls[i].nkv * kHeadDim,
-                                 bh * calls[i].nkv * kHeadDim};
-        const void* src[3] = {calls[i].q, calls[i].k, calls[i].v};
-        const void** dstp[3] = {&c16[i].q, &c16[i].k, &c16[i].v};
-        for (int j = 0; j < 3; ++j) {
-            const size_t bytes = align256(elems[j] * sizeof(f16));
-            if (off + bytes > ws_bytes) return hipErrorNotSupported;
-            total8 += (unsigned)(elems[j] / 8);
-            cv.src[cv.count] = reinterpret_cast<const float*>(src[j]);
-            cv.dst[cv.count] = reinterpret_cast<f16*>(ws + off);
-            cv.end8[cv.count] = total8;
-            ++cv.count;
-            *dstp[j] = ws + off;
-            off += bytes;
-        }
-    }
-    if (total8 > 0 && (phase_mask & 1)) {
-        hipLaunchKernelGGL(convert_f32_f16_kernel, dim3((total8 + 255) / 256), dim3(256), 0, stream, cv);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return launch_group_chunk(c16, n, InType::F16, out, nullptr, 0, stream, 0, 0, 0, phase_mask);
-}
-
-// lens (the streaming kernel's per-item key counts, launch_group's comment): lens[i] belongs to calls[i]
-static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutType out, void* workspace,
-                                     size_t ws_bytes, hipStream_t stream, int force_q_waves, int force_kv_waves,
-                                     int force_splits, int phase_mask, const int* const* lens, const int* const* qlens) {
-    bool in32_direct = false;  // fp32 inputs into the 16-row kernel's one-pass forms
-    GroupPlan p{};
-    if (in == InType::F32 && force_q_waves == 0 && force_kv_waves == 0 && force_splits == 0) {
-        if (f32_inkernel_enabled() && f32_convert_enabled()) {
-            const GroupPlan p16 = plan_group(calls, n, 0, 0, 0, 0, InType::F16);
-            // one-pass forms only (nkv <= 1024): the two-pass form rounding fp32 in the kernel
-            // measured slower than convert + fp16 kernel (1x4x1024x2048 11.32 vs 10.75 us,
-            // 512x1536 9.78 vs 9.24; profiles/r02/float_inkernel.jsonl)
-            in32_direct = p16.direct_tiles > 0 && p16.direct_tiles <= (f32_inkernel_two_pass() ? 4 : 2) &&
-                          p16.rows_per_wave == 16;
-            if (in32_direct) p = p16;
-        }
-        if (!in32_direct) {
-            const hipError_t e = launch_f32_via_f16(calls, n, out, workspace, ws_bytes, stream, phase_mask);
-            if (e != hipErrorNotSupported) return e;
-        }
-    }
-    if (!in32_direct) p = plan_group(calls, n, workspace ? ws_bytes : 0, force_q_waves, force_kv_waves, force_splits, in);
-    FwdArgs a{};
+hipError_t launch_combine(const FwdArgs& a, int block_m, bool out_f32, hipStream_t stream) {
     CombineArgs cb{};
-    a.stamps = g_stamps;
-    int blocks = 0, n_live = 0;
-    bool any_split = false;
-    for (int i = 0; i < n; ++i) {
-        const Call& c = calls[i];
-        if (c.nq <= 0 || c.batch <= 0 || c.heads <= 0) continue;  // nothing to compute
-        CallArgs& ca = a.c[n_live];
-        ca.q = c.q;
-        ca.k = c.k;
-        ca.v = c.v;
-        ca.o = c.o;
-        ca.nq = c.nq;
-        ca.nkv = c.nkv;
-        ca.splits = p.splits[i];
-        ca.tiles_per_split = p.tiles_per_split[i];
-        ca.bh = c.batch * c.heads;
-        ca.heads = c.heads;
-        a.lens[n_live] = lens ? lens[i] : nullptr;
-        a.qlens[n_live] = lens && qlens ? qlens[i] : nullptr;
-        const int block_m = p.rows_per_wave == 16 ? 16 : 32 * p.q_waves * (p.rows_per_wave / 32);
-        ca.qtiles = (c.nq + block_m - 1) / block_m;
-        ca.block_begin = blocks;
-        if (ca.splits > 1) {
-            const size_t rows = (size_t)ca.bh * ca.splits * c.nq;
-            char* base = reinterpret_cast<char*>(workspace) + p.ws_offset[i];
-            ca.part_o = base;
-            ca.part_ml = reinterpret_cast<float2*>(base + align256(rows * kHeadDim * sizeof(float)));
-            any_split = true;
-        }
-        CombineCall& cc = cb.c[n_live];
-        cc.part_o = ca.part_o;
-        cc.part_ml = ca.part_ml;
-        cc.out = c.o;
-        cc.nq = c.nq;
-        cc.splits = ca.splits;
-        cc.qtiles = ca.qtiles;
-        blocks += ca.qtiles * ca.bh * ca.splits;
-        ++n_live;
+    for (int i = 0; i < a.n_calls; ++i) {
+        const CallArgs& ca = a.c[i];
+        cb.c[i] = CombineCall{ca.part_o, ca.part_ml, ca.o, ca.nq, ca.splits, ca.qtiles, 0};
     }
-    if (n_live == 0) return hipSuccess;
-    a.n_calls = n_live;
-    a.total_blocks = blocks;
-    const int rbw = p.rows_per_wave / 32;
-    if (p.stream) {  // persistent streaming kernel: no split, no workspace
-        g_last_combine = 0;
-        if (!(phase_mask & 1)) return hipSuccess;
-        return launch_stream(a, p.q_waves, out == OutType::F32, stream, lens != nullptr);
-    }
-    if (lens) return hipErrorInvalidValue;  // (only the streaming kernel takes key counts)
-    if (p.direct_tiles > 0) {  // single-pass kernel: no split, no workspace
-        g_last_combine = 0;
-        if (!(phase_mask & 1)) return hipSuccess;
-        return p.rows_per_wave == 16 ? launch_direct16(a, blocks, p.direct_tiles, out == OutType::F32, stream, in32_direct)
-                                     : launch_direct(a, blocks, p.direct_tiles, out == OutType::F32, stream);
-    }
-    // Split calls combine inside the main launch when a ticket array is available (phase_mask 3,
-    // the production form); otherwise (or MHA_HD64_FUSED_COMBINE=0) in the combine kernel.
-    if (any_split && (phase_mask & 3) == 3 && fused_enabled()) a.tickets = tickets_for(stream, blocks);
-    g_last_combine = !any_split ? 0 : (a.tickets ? 1 : 2);
-    hipError_t e = hipSuccess;
-    if (phase_mask & 1) {
-        if (in == InType::F16) {
-            e = (out == OutType::F16) ? launch_fwd_shape<f16, f16>(a, blocks, p.q_waves, p.kv_waves, rbw, stream)
-                                      : launch_fwd_shape<f16, float>(a, blocks, p.q_waves, p.kv_waves, rbw, stream);
-        } else {
-            e = (out == OutType::F16) ? launch_fwd_shape<float, f16>(a, blocks, p.q_waves, p.kv_waves, rbw, stream)
-                                      : launch_fwd_shape<float, float>(a, blocks, p.q_waves, p.kv_waves, rbw, stream);
-        }
-    }
-    if (e != hipSuccess || !any_split || !(phase_mask & 2) || a.tickets) return e;
     // Combine grid: for every XCD x, the groups (of calls that split) whose first split block
     // ran on x (same bijective order as the main kernel), 16 rows per block.
+    const int blocks = a.total_blocks, n_live = a.n_calls;
     cb.n_calls = n_live;
-    const int block_m = 32 * p.q_waves * rbw;
     cb.block_m_log2 = block_m == 32 ? 5 : (block_m == 64 ? 6 : 7);
     auto xb = [&](int xx) {
         const int q8 = blocks >> 3, r8 = blocks & 7;
@@ -1504,55 +958,20 @@ static hipError_t launch_group_chunk(const Call* calls, int n, InType in, OutTyp
     cb.per_xcd = std::max(1, per_xcd);
     cb.main_blocks = blocks;
     cb.groups0 = a.c[0].qtiles * a.c[0].bh;
-    return (out == OutType::F16) ? launch_combine<f16>(cb, stream) : launch_combine<float>(cb, stream);
+    return out_f32 ? launch_combine<float>(cb, stream) : launch_combine<f16>(cb, stream);
 }
 
-hipError_t launch_group(const Call* calls, int n, InType in, OutType out, void* workspace, size_t ws_bytes,
-                        hipStream_t stream, int force_q_waves, int force_kv_waves, int force_splits,
-                        int phase_mask, const int* const* lens, const int* const* qlens) {
-    // Chunks of kMaxCalls calls share one launch; each chunk reuses the workspace (stream order).
-    for (int i = 0; i < n; i += kMaxCalls) {
-        const hipError_t e = launch_group_chunk(calls + i, std::min(kMaxCalls, n - i), in, out, workspace, ws_bytes,
-                                                stream, force_q_waves, force_kv_waves, force_splits, phase_mask,
-                                                lens ? lens + i : nullptr, qlens ? qlens + i : nullptr);
-        if (e != hipSuccess) return e;
+hipError_t launch_convert(const void* const* src, void* const* dst, const unsigned* end8, int count,
+                          hipStream_t stream) {
+    ConvArgs cv{};
+    for (int i = 0; i < count; ++i) {
+        cv.src[i] = reinterpret_cast<const float*>(src[i]);
+        cv.dst[i] = reinterpret_cast<f16*>(dst[i]);
+        cv.end8[i] = end8[i];
     }
-    return hipSuccess;
-}
-
-// What launch_group_chunk uses for one chunk (same decisions, in the same order).
-static size_t chunk_workspace_bytes(const Call* calls, int n, InType in) {
-    if (in == InType::F32 && f32_convert_enabled()) {
-        const GroupPlan p16 = plan_group(calls, n, 0, 0, 0, 0, InType::F16);
-        const bool in32_direct = f32_inkernel_enabled() && p16.direct_tiles > 0 &&
-                                 p16.direct_tiles <= (f32_inkernel_two_pass() ? 4 : 2) && p16.rows_per_wave == 16;
-        if (in32_direct) return 0;
-        if (f32_convert_route(calls, n, p16)) {  // convert launch into the workspace, then the fp16 kernel
-            size_t off = 0;
-            for (int i = 0; i < n; ++i) {
-                if (calls[i].nq <= 0 || calls[i].batch <= 0 || calls[i].heads <= 0) continue;
-                const size_t bh = (size_t)calls[i].batch * calls[i].heads;
-                off += align256(bh * calls[i].nq * kHeadDim * sizeof(f16)) +
-                       2 * align256(bh * calls[i].nkv * kHeadDim * sizeof(f16));
-            }
-            return off;
-        }
-    }
-    return plan_group(calls, n, (size_t)-1, 0, 0, 0, in).ws_needed;
-}
-
-size_t group_workspace_bytes(const Call* calls, int n, InType in) {
-    size_t need = 0;
-    for (int i = 0; i < n; i += kMaxCalls)
-        need = std::max(need, chunk_workspace_bytes(calls + i, std::min(kMaxCalls, n - i), in));
-    return need;
-}
-
-hipError_t launch_attention(const Call& c, InType in, OutType out, void* workspace, size_t ws_bytes,
-                            hipStream_t stream, int force_q_waves, int force_kv_waves, int force_splits,
-                            int phase_mask) {
-    return launch_group_chunk(&c, 1, in, out, workspace, ws_bytes, stream, force_q_waves, force_kv_waves,
-                              force_splits, phase_mask);
+    cv.count = count;
+    hipLaunchKernelGGL(convert_f32_f16_kernel, dim3((end8[count - 1] + 255) / 256), dim3(256), 0, stream, cv);
+    return hipGetLastError();
 }
 
 }  // namespace mha_hd64

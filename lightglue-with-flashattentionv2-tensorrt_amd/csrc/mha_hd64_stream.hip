@@ -1,7 +1,7 @@
 // mha_hd64_stream.hip — persistent streaming FlashAttention forward, head_dim = 64, for gfx950
 // (MI355X): the throughput form of the MHAHeadDim64 operator.
 //
-// Same operator as mha_hd64_kernels.hip (O = softmax(Q·Kᵀ·0.125)·V per (batch, head); reference
+// Same operator as mha_hd64_ring.hip (O = softmax(Q·Kᵀ·0.125)·V per (batch, head); reference
 // lightglue_attention_plugin/attention_headdim_64_fp16in_fp16out.cu:253-733 and
 // …fp16in_fp32out.cu:253-703, oracle lightglue_pytorch_no_plugin/lightglue.py:75-85) for launches
 // that carry more 128-row query blocks than one round of the chip holds: batched image-pair

@@ -168,6 +168,8 @@ SIGNATURES.update({
     "mha_hd64_launch_forced": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _S, _P, _I], _I),
     "mha_hd64_launch_stream_lens": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P], _I),
     "mha_hd64_plan": ([_I, _I, _I, _I, _S, ctypes.POINTER(ctypes.c_int32)], _S),
+    "mha_hd64_plan_route": ([ctypes.POINTER(CallDesc), _I, _I, _S, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I),
+                             ctypes.POINTER(_I), ctypes.POINTER(_S)], _S),
     "mha_hd64_set_stamp_buffer": ([_P], None),
     "mha_hd64_last_combine_form": ([], _I),
 })

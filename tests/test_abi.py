@@ -342,6 +342,43 @@ def test_planner_invariants_fuzzed(lib):
         assert lib.mha_hd64_launch_workspace_bytes_typed(b, h, nq, nkv, 0) >= 0
 
 
+def test_recorded_plan_routes(lib):
+    """tests/golden/plan_routes.json, recorded from the commit its header names, replayed through
+    mha_hd64_plan_route: route, plan and workspace of every row, field by field (single calls and
+    groups, both input types, workspace sizes around the need with and without a workspace pointer,
+    the switches, forced plans). For every unforced entry the workspace query equals what the route
+    uses given an unlimited workspace: the query and the launcher decide together."""
+    import json
+
+    spec = importlib.util.spec_from_file_location("make_plan_golden", os.path.join(REPO, "tests", "golden", "make_plan_golden.py"))
+    gold = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gold)
+    doc = json.load(open(os.path.join(REPO, "tests", "golden", "plan_routes.json")))
+    assert tuple(doc["header"]["fields"]) == gold.FIELDS
+    recorded = doc["entries"]
+    listed = [(calls, t, sw, forced) for calls, t, sw, forced in gold.entries()]
+    assert len(recorded) == len(listed) > 300
+    for e, (calls, t, sw, forced) in zip(recorded, listed):
+        key = [[list(c) for c in calls], t, list(sw), list(forced)]
+        assert e[:4] == key  # the script's order
+        query, rows, results = e[4:]
+        with gold.switches(lib, sw):
+            sizes = gold.workspaces(query)
+            assert len(rows) == len(sizes), key
+            for (ws, has), idx in zip(sizes, rows):
+                got, want = gold.route(lib, calls, t, ws, has, forced), results[idx]
+                assert len(got) == len(want), (key, ws, has)
+                for chunk, (g, w) in enumerate(zip(got, want)):
+                    for name, a, b in zip(gold.FIELDS, g, w):
+                        assert a == b, (key, ws, has, chunk, name, a, b)
+            if forced == (0, 0, 0):
+                at_best = max(c[-1] for c in gold.route(lib, calls, t, gold.UNLIMITED, 1, forced))
+                assert gold.query(lib, calls, t) == at_best == query, key
+    out = (ctypes.c_int32 * 4)()  # the switches are back: the metric call plans as by default
+    lib.mha_hd64_plan(1, 4, 1024, 1024, 5242880, out)
+    assert out[0] == 22 and lib.mha_hd64_set_concurrency_hint(1) == 1 and lib.mha_hd64_set_stream_mode(1) == 1
+
+
 def _dma_checker():
     import importlib.util
 

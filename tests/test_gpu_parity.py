@@ -209,6 +209,40 @@ def test_float_boundary_in_kernel_equals_convert_launch(nq, nkv, batch, heads, d
     assert _maxdiff(outs[0].cpu().numpy()[:, :, rows], ref) <= TOL
 
 
+def test_float_convert_route_falls_back_without_room(dev, oracle_mod):
+    """fp32 1x4x16x1100: its fp16 plan is the 16-row kernel's two-pass form, so with the queried
+    workspace the launch converts into it and runs that kernel (no split: combine form 0, which the
+    ring kernel's split plan for this shape would not report). With 256 bytes less, or with no
+    workspace at all, the fp16 copies have no room and the ring kernel rounds on load instead. All
+    three match the oracle at the Float path's tolerance."""
+    from lightglue_amd import _lib, synth
+
+    lib = _lib.load()
+    nq, nkv, FLOAT = 16, 1100, 0
+    qn, kn, vn = synth.qkv(1100, nq, nkv)
+    ref = oracle_mod.attention_c(qn, kn, vn)
+    q, k, v = (_t(x, dev, torch.float32) for x in (qn, kn, vn))
+    need = lib.mha_hd64_launch_workspace_bytes_typed(1, 4, nq, nkv, FLOAT)
+    assert need == 4 * (nq + 2 * nkv) * 64 * 2  # Q, K, V in fp16
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    call = (_lib.CallDesc * 1)(_lib.CallDesc(0, 0, 0, 0, 1, 4, nq, nkv))
+    head, one, off = (ctypes.c_int32 * 5)(), (ctypes.c_int32 * 1)(), (ctypes.c_size_t * 1)()
+    for ws_ptr, ws_bytes, route in ((ws.data_ptr(), need, 2), (ws.data_ptr(), need - 256, 0), (None, 0, 0)):
+        lib.mha_hd64_plan_route(call, 1, FLOAT, ws_bytes, ws_ptr is not None, 0, 0, 0, head, one, one, off)
+        assert head[0] == route and (route == 0) == (head[1] not in (21, 22, 23)), (ws_bytes, list(head))
+        o = torch.full(q.shape, float("nan"), dtype=torch.float32, device=dev)
+        st = lib.mha_hd64_launch_fp32in_fp32out(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), 1, 4, nq, nkv,
+                                                ws_ptr, ws_bytes, torch.cuda.current_stream().cuda_stream)
+        assert st == 0, _lib.last_error()
+        form = lib.mha_hd64_last_combine_form()
+        torch.cuda.synchronize()
+        err = _maxdiff(o.cpu().numpy(), ref)
+        print(f"ws {ws_bytes}: route {route}, combine form {form}, max-abs {err:.2e}")
+        assert err <= TOL and err <= REG_FLOAT
+        if route == 2:
+            assert form == 0
+
+
 @pytest.mark.parametrize("shapes", [[(1024, 1024)], [(512, 512), (300, 257)], [(33, 65), (777, 1000), (64, 128)],
                                     [(1024, 2048)], [(200, 1500), (64, 2048)]])
 @pytest.mark.parametrize("out_dtype", [torch.float32, torch.float16])
@@ -464,7 +498,7 @@ def test_grouped_matches_single_calls_bitwise_when_plans_agree(dev):
     assert torch.equal(a, b)
 
 
-# ---- in-launch split combine (arrival tickets; csrc/mha_hd64_kernels.hip epilogue) ----
+# ---- in-launch split combine (arrival tickets; csrc/mha_hd64_ring.hip epilogue; tickets: mha_hd64_launch.hip) ----
 FUSED_SHAPES = [  # (nq, nkv, q_waves, kv_waves, splits)
     (1024, 1024, 2, 4, 0), (1024, 1024, 2, 2, 4), (300, 2048, 2, 2, 3), (100, 1000, 12, 2, 3),
     (64, 4000, 2, 4, 0), (33, 65, 4, 1, 2), (257, 1000, 4, 2, 2), (1024, 1024, 1, 8, 0), (300, 2000, 1, 8, 0),
