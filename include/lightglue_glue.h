@@ -236,6 +236,63 @@ int32_t lg_assign_matches_lens(const void* v, int64_t pair_stride, int32_t ld, i
                                int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1, int32_t* matches,
                                float* mscores, int32_t* counts, void* workspace, hipStream_t stream);
 
+/* ---- adaptive depth and width (csrc/lightglue_adaptive.hip; fp16 rows of 256 channels) ----
+ * The published LightGlue rules the reference ships the pieces of (TokenConfidence lightglue.py:54-66,
+ * MatchAssignment.get_matchability :230-232) and never applies. New symbols only: LG_GLUE_ABI_VERSION
+ * stays 4. Rows are pair-major as everywhere ([pairs * (m + n), ...]); m_len / n_len are the lens forms'
+ * DEVICE int32 [pairs] tables (null: all m / n rows; clamped into [1, m] / [1, n] by the kernels), and
+ * no row past a pair's count is ever read. Every call checks its arguments before any device call.
+ *
+ * lg_token_scores: for each valid row r of x [pairs * (m + n), 256]
+ *   conf = sigmoid(w_tok · x_r + b_tok), mtch = sigmoid(w_match · x_r + b_match)
+ * (w_* fp16 [256], 16-B aligned; b_* one fp16 value each, on the device; fp32 accumulation in a fixed
+ * order and an fp32 sigmoid), and
+ *   keep = 1                                              for an image whose LG_ADAPT_WIDTHi flag is clear,
+ *   keep = mtch > t_keep || (LG_ADAPT_DEPTH && conf <= t_conf)   otherwise;
+ * a pruned segment (one image of one pair) that kept no row keeps its row of highest mtch, the lowest
+ * index on ties. conf, mtch fp32 [pairs, m + n]; keep uint8 [pairs, m + n]; padded rows: 0 in all three.
+ * stats int32 [pairs, 4] = (kept rows of image 0, of image 1, valid rows of both images with
+ * conf < t_conf, valid rows of both images); the call zeroes it first. One launch, and a second tiny
+ * one for the min-one rule when a width flag is set. 0 <= t_conf <= 1. */
+#define LG_ADAPT_DEPTH 1
+#define LG_ADAPT_WIDTH0 2
+#define LG_ADAPT_WIDTH1 4
+int32_t lg_token_scores(const void* x, int32_t m, int32_t n, int32_t pairs, const int32_t* m_len, const int32_t* n_len,
+                        const void* w_tok, const void* b_tok, const void* w_match, const void* b_match, float t_conf,
+                        float t_keep, int32_t flags, float* conf, float* mtch, uint8_t* keep, int32_t* stats,
+                        hipStream_t stream);
+
+/* lg_compact_rows: the stable gather of the rows with keep != 0 (keep [pairs, m + n], read below each
+ * pair's count only) from the layout (m, n) into the layout (m_out <= m, n_out <= n): x [.., 256], cos and
+ * sin [.., 64] (bitwise copies; 16-B aligned, the outputs distinct from the inputs), and the running
+ * index maps ind0 [pairs, m] -> ind0_out [pairs, m_out], ind1 [pairs, n] -> ind1_out [pairs, n_out] (a
+ * null input map is the identity). m_len_out / n_len_out [pairs]: the kept rows per segment, the next
+ * layout's counts (a segment with no kept row gets 0, which every lens form reads as 1: lg_token_scores
+ * never leaves one). A kept row whose destination is past m_out / n_out is dropped and the count capped
+ * (the caller sizes the layout from lg_token_scores' stats); output rows past the new counts are not
+ * written. One launch over 64-row tiles; a tile's first destination is the count of its segment's flags
+ * before it. With prune0 [pairs, m_orig] / prune1 [pairs, n_orig] (both or neither): the dropped rows'
+ * entries, at their original index, are set to `layers` (the layers they took part in). */
+int32_t lg_compact_rows(const void* x, const void* cosv, const void* sinv, const uint8_t* keep, const int32_t* ind0,
+                        const int32_t* ind1, int32_t m, int32_t n, int32_t pairs, const int32_t* m_len, const int32_t* n_len,
+                        int32_t m_out, int32_t n_out, void* x_out, void* cos_out, void* sin_out, int32_t* ind0_out,
+                        int32_t* ind1_out, int32_t* m_len_out, int32_t* n_len_out, int32_t* prune0, int32_t* prune1,
+                        int32_t m_orig, int32_t n_orig, int32_t layers, hipStream_t stream);
+
+/* lg_matches_scatter: lg_assign_matches' seven outputs for the surviving rows (layout m_cur x n_cur, the
+ * list min(m_cur, n_cur) long; counts m_len / n_len) mapped through ind0 [pairs, m_cur] / ind1 [pairs,
+ * n_cur] (null: identity) into the original layout m x n (m_cur <= m, n_cur <= n, m, n <= 2048): indices
+ * become original indices, rows and columns that no surviving row maps to hold -1 / 0, the list keeps its
+ * order (a stable compaction keeps i ascending) and min(m, n) rows. prune0 [pairs, m] / prune1 [pairs, n]
+ * (nullable): the surviving rows' entries are set to `stop`, the others left as lg_compact_rows (or the
+ * caller's initial zeros) wrote them. One launch; every output element is written exactly once. */
+int32_t lg_matches_scatter(const int32_t* matches0, const int32_t* matches1, const float* mscores0, const float* mscores1,
+                           const int32_t* matches, const float* mscores, const int32_t* counts, const int32_t* ind0,
+                           const int32_t* ind1, const int32_t* m_len, const int32_t* n_len, int32_t m_cur, int32_t n_cur,
+                           int32_t m, int32_t n, int32_t pairs, int32_t stop, int32_t* out_matches0, int32_t* out_matches1,
+                           float* out_mscores0, float* out_mscores1, int32_t* out_matches, float* out_mscores,
+                           int32_t* out_counts, int32_t* prune0, int32_t* prune1, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

@@ -16,8 +16,18 @@ from .plugin import (  # noqa: F401
     set_stream_mode,
 )
 from . import ops  # noqa: F401,E402  (registers torch.ops.lightglue_amd.*)
+from .matcher import (  # noqa: F401,E402
+    AdaptiveResult,
+    adaptive_reference,
+    adaptive_thresholds,
+    seeded_confidence_state_dict,
+)
 
 __all__ = [
+    "AdaptiveResult",
+    "adaptive_reference",
+    "adaptive_thresholds",
+    "seeded_confidence_state_dict",
     "Attention",
     "LightGlueAttentionPlugin",
     "LightGlueAttentionPluginCreator",

@@ -24,6 +24,11 @@ STATUS_BAD_PARAM = 1
 STATUS_LAUNCH_FAILED = 2
 STATUS_WORKSPACE = 3
 
+# include/lightglue_glue.h LG_ADAPT_* (lg_token_scores' mode flags)
+ADAPT_DEPTH = 1
+ADAPT_WIDTH0 = 2
+ADAPT_WIDTH1 = 4
+
 BATCH = 1
 NUM_HEADS = 4
 MAX_SEQ_LEN = 2048
@@ -145,6 +150,12 @@ SIGNATURES.update({
     "lg_assign_scores_lens": ([_P, ctypes.c_int64, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     "lg_assign_matches_lens": ([_P, ctypes.c_int64, _I, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P], _I),
+    # adaptive depth / width (csrc/lightglue_adaptive.hip)
+    "lg_token_scores": ([_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P, _P, _P], _I),
+    "lg_compact_rows": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I,
+                         _P], _I),
+    "lg_matches_scatter": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -28,6 +28,10 @@ What is different, and why:
   batches of pairs of different sizes, and ``match_pairs`` pads a list of pairs itself: on the fp16 hip
   path the equal-size forward's launches, with the counts as the attention's key and query-row counts
   and the heads' lens forms (no valid row's result reads a padded row); elsewhere pair by pair;
+* ``match_adaptive`` (opt-in: ``depth_confidence`` / ``width_confidence`` > 0) applies the published
+  LightGlue rules the reference ships the pieces of and never uses: a per-layer token confidence stops
+  the forward early, a per-layer matchability drops points; ``adaptive_reference`` is the same in
+  framework ops (the tests' oracle);
 * ``attention=`` lets tests substitute the oracle for the kernel on CPU; the default path
   requires GPU tensors and fails loudly otherwise (no CPU fallback).
 """
@@ -307,6 +311,65 @@ class _Hip:
                                    out.matches.data_ptr(), out.match_scores.data_ptr(), out.counts.data_ptr(),
                                    ws.data_ptr(), stream)
         _check(st, "lg_assign_matches")
+        return out
+
+    # ---- adaptive depth / width (csrc/lightglue_adaptive.hip) ----
+    @staticmethod
+    def token_scores(x, m, n, pr, lens, w_tok, b_tok, w_match, b_match, t_conf, t_keep, flags):
+        """lg_token_scores on x [1, P*(m+n), 256]: (conf, mtch fp32 [P, m+n], keep uint8 [P, m+n], stats
+        int32 [P, 4] = (kept0, kept1, unconfident, valid))."""
+        dev = x.device
+        conf = torch.empty((pr, m + n), dtype=torch.float32, device=dev)
+        mtch = torch.empty_like(conf)
+        keep = torch.empty((pr, m + n), dtype=torch.uint8, device=dev)
+        stats = torch.empty((pr, 4), dtype=torch.int32, device=dev)
+        l0, l1 = (t.data_ptr() if t is not None else None for t in (lens if lens is not None else (None, None)))
+        st = _lib.load().lg_token_scores(x.data_ptr(), m, n, pr, l0, l1, w_tok.data_ptr(), b_tok.data_ptr(),
+                                         w_match.data_ptr(), b_match.data_ptr(), float(t_conf), float(t_keep), int(flags),
+                                         conf.data_ptr(), mtch.data_ptr(), keep.data_ptr(), stats.data_ptr(), _Hip._stream(x))
+        _check(st, "lg_token_scores")
+        return conf, mtch, keep, stats
+
+    @staticmethod
+    def compact_rows(x, cos, sin, keep, ind, m, n, pr, lens, m_out, n_out, prune=None, layers=0):
+        """lg_compact_rows: the kept rows of x / cos / sin and of the index maps ind = (ind0, ind1) (None:
+        identity) in the layout (m_out, n_out): (x, cos, sin, (ind0, ind1), (len0, len1)). prune = (prune0
+        [P, m_orig], prune1 [P, n_orig]): the dropped rows' entries are set to `layers`."""
+        dev = x.device
+        rows = pr * (m_out + n_out)
+        xo = torch.empty((1, rows, x.shape[2]), dtype=x.dtype, device=dev)
+        co = torch.empty((1, rows, cos.shape[2]), dtype=cos.dtype, device=dev)
+        so = torch.empty_like(co)
+        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)  # noqa: E731
+        i0, i1, l0, l1 = i32(pr, m_out), i32(pr, n_out), i32(pr), i32(pr)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        lens = lens if lens is not None else (None, None)
+        p0, p1 = prune if prune is not None else (None, None)
+        st = _lib.load().lg_compact_rows(x.data_ptr(), cos.data_ptr(), sin.data_ptr(), keep.data_ptr(), ptr(ind[0]),
+                                         ptr(ind[1]), m, n, pr, ptr(lens[0]), ptr(lens[1]), m_out, n_out, xo.data_ptr(),
+                                         co.data_ptr(), so.data_ptr(), i0.data_ptr(), i1.data_ptr(), l0.data_ptr(),
+                                         l1.data_ptr(), ptr(p0), ptr(p1), p0.shape[1] if p0 is not None else 0,
+                                         p1.shape[1] if p1 is not None else 0, int(layers), _Hip._stream(x))
+        _check(st, "lg_compact_rows")
+        return xo, co, so, (i0, i1), (l0, l1)
+
+    @staticmethod
+    def matches_scatter(r, ind, lens, m, n, stop, prune=None):
+        """lg_matches_scatter: the MatchResult r of the surviving rows (layout r.matches0.shape[1] x
+        r.matches1.shape[1]) in the original layout m x n; prune's surviving entries are set to `stop`."""
+        pr, mc, nc = r.matches0.shape[0], r.matches0.shape[1], r.matches1.shape[1]
+        dev, k = r.matches0.device, min(m, n)
+        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)    # noqa: E731
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+        out = MatchResult(i32(pr, m), i32(pr, n), f32(pr, m), f32(pr, n), i32(pr, k, 2), f32(pr, k), i32(pr))
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        ind = ind if ind is not None else (None, None)
+        lens = lens if lens is not None else (None, None)
+        p0, p1 = prune if prune is not None else (None, None)
+        st = _lib.load().lg_matches_scatter(*(t.data_ptr() for t in r), ptr(ind[0]), ptr(ind[1]), ptr(lens[0]), ptr(lens[1]),
+                                            mc, nc, m, n, pr, int(stop), *(t.data_ptr() for t in out), ptr(p0), ptr(p1),
+                                            _Hip._stream(r.matches0))
+        _check(st, "lg_matches_scatter")
         return out
 
     @staticmethod
@@ -719,6 +782,88 @@ def filter_matches_dense(scores: torch.Tensor, th: float) -> MatchResult:
                        counts.to(i32))
 
 
+class TokenConfidence(nn.Module):
+    """lightglue.py:54-66: a per-token confidence Linear(d, 1) + Sigmoid (state-dict keys token.0.*).
+    The reference defines it and never calls it; match_adaptive does."""
+
+    def __init__(self, d: int) -> None:
+        super().__init__()
+        self.token = nn.Sequential(nn.Linear(d, 1), nn.Sigmoid())
+
+
+class AdaptiveResult(NamedTuple):
+    """match_adaptive's result. result: the MatchResult in original index space (pruned and padded rows
+    -1 / 0); stop: the number of layers run (the head is log_assignment[stop - 1]); prune0 [P, M] /
+    prune1 [P, N] int32: the number of layers each original point took part in (stop for a point never
+    pruned, 0 for padding). With both knobs off nothing is pruned and prune0 / prune1 are None."""
+    result: MatchResult
+    stop: int
+    prune0: Optional[torch.Tensor]
+    prune1: Optional[torch.Tensor]
+
+
+# ---- the published adaptive rules (LightGlue, ICCV 2023, section 3.3; the reference holds only their
+# pieces: lightglue.py:54-66, 230-232, 270-271, 304), shared by the kernel path and adaptive_reference ----
+def adaptive_thresholds(n_layers: int) -> List[float]:
+    """t_i = clip(0.8 + 0.1 exp(-4 i / L), 0, 1) per layer, in float64 (the kernel takes float32(t_i))."""
+    return [float(np.clip(0.8 + 0.1 * np.exp(-4.0 * i / n_layers), 0.0, 1.0)) for i in range(n_layers)]
+
+
+def _f32(v: float) -> float:
+    return float(np.float32(v))
+
+
+def exit_passes(unconfident: int, valid: int, depth_confidence: float) -> bool:
+    """A pair passes when the confident share of its valid rows (both images) exceeds depth_confidence."""
+    return 1.0 - unconfident / valid > depth_confidence
+
+
+def keep_rule(conf: torch.Tensor, mtch: torch.Tensor, t: float, depth_confidence: float,
+              width_confidence: float) -> torch.Tensor:
+    """The keep flags of one pruned segment (fp32 conf / mtch of its valid rows): mtch > float32(1 -
+    width_confidence), with depth on also conf <= float32(t); never empty (else the row of highest mtch,
+    the lowest index on ties)."""
+    keep = mtch > _f32(1.0 - width_confidence)
+    if depth_confidence > 0:
+        keep = keep | (conf <= _f32(t))
+    if keep.numel() and not bool(keep.any()):
+        keep = keep.clone()
+        keep[int((mtch == mtch.max()).nonzero()[0])] = True
+    return keep
+
+
+def compact_dims(kept0: Sequence[int], kept1: Sequence[int]) -> Tuple[int, int]:
+    """The layout after a compaction: (max kept0, max kept1 rounded up to 8: the head's n % 8 == 0)."""
+    return max(kept0), (max(kept1) + 7) // 8 * 8
+
+
+def scatter_matches_reference(r: MatchResult, ind0, ind1, len0, len1, m: int, n: int, stop: int = 0,
+                              prune0=None, prune1=None) -> MatchResult:
+    """lg_matches_scatter in framework ops: r (the surviving rows' MatchResult, ind0 [P, mc] / ind1 [P, nc]
+    their original indices, len0 / len1 their counts per pair) in the original layout m x n."""
+    pr, dev, k = r.matches0.shape[0], r.matches0.device, min(m, n)
+    i32 = lambda *s: torch.full(s, -1, dtype=torch.int32, device=dev)                # noqa: E731
+    f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)                 # noqa: E731
+    out = MatchResult(i32(pr, m), i32(pr, n), f32(pr, m), f32(pr, n), i32(pr, k, 2), f32(pr, k),
+                      torch.zeros((pr,), dtype=torch.int32, device=dev))
+    for p in range(pr):
+        a, b = int(len0[p]), int(len1[p])
+        i0, i1 = ind0[p, :a].long(), ind1[p, :b].long()
+        for own, other, mi, si, om, os in ((i0, i1, r.matches0[p, :a], r.scores0[p, :a], out.matches0, out.scores0),
+                                           (i1, i0, r.matches1[p, :b], r.scores1[p, :b], out.matches1, out.scores1)):
+            mi = mi.long()
+            om[p, own] = torch.where(mi >= 0, other[mi.clamp(min=0)], mi).to(torch.int32)
+            os[p, own] = si.float()
+        c = int(r.counts[p])
+        lst = r.matches[p, :c].long()
+        out.matches[p, :c, 0], out.matches[p, :c, 1] = i0[lst[:, 0]].to(torch.int32), i1[lst[:, 1]].to(torch.int32)
+        out.match_scores[p, :c] = r.match_scores[p, :c].float()
+        out.counts[p] = c
+        if prune0 is not None:
+            prune0[p, i0], prune1[p, i1] = stop, stop
+    return out
+
+
 class LightGlueMatcher(nn.Module):
     """LightGlue(features=None) of the reference with the MI355X attention (lightglue.py:265-353).
 
@@ -731,18 +876,28 @@ class LightGlueMatcher(nn.Module):
     grouped launch of P-batch calls. glue='torch' runs the pairs one by one."""
 
     def __init__(self, n_layers: int = 9, descriptor_dim: int = 256, input_dim: int = 256, num_heads: int = 4,
-                 filter_threshold: float = 0.1, attention: Optional[AttnFn] = None, glue: str = "hip") -> None:
+                 filter_threshold: float = 0.1, attention: Optional[AttnFn] = None, glue: str = "hip",
+                 depth_confidence: float = -1.0, width_confidence: float = -1.0, prune_min_keypoints: int = 0) -> None:
         super().__init__()
         d = descriptor_dim
+        self.depth_confidence, self.width_confidence = float(depth_confidence), float(width_confidence)
+        self.prune_min_keypoints = int(prune_min_keypoints)
         self.n_layers, self.filter_threshold = n_layers, filter_threshold
         self.input_proj = nn.Linear(input_dim, d) if input_dim != d else nn.Identity()
         self.posenc = FourierPositionalEncoding(2, d // num_heads)
         self.transformers = nn.ModuleList([TransformerLayer(d, num_heads) for _ in range(n_layers)])
         self.log_assignment = nn.ModuleList([MatchAssignment(d) for _ in range(n_layers)])
+        if self.adaptive:  # (only then: the default model's state dict is the reference's, key for key)
+            self.token_confidence = nn.ModuleList([TokenConfidence(d) for _ in range(n_layers - 1)])
         self.attention = attention or _kernel_attention
         if glue not in ("hip", "torch"):
             raise ValueError("glue must be 'hip' or 'torch'")
         self.glue = glue
+
+    @property
+    def adaptive(self) -> bool:
+        """match_adaptive exits early or prunes (a knob > 0); else it is match_batch."""
+        return self.depth_confidence > 0 or self.width_confidence > 0
 
     def pair_inputs_ok(self, kpts0, kpts1, desc0, desc1) -> bool:
         """lg_pair_inputs reads both descriptor sets, both keypoint sets and posenc.Wr as raw fp16
@@ -791,6 +946,14 @@ class LightGlueMatcher(nn.Module):
             t = t.pin_memory().to(device, non_blocking=True)
         return host, t
 
+    def _lens_fast(self, desc0, m: int, n: int) -> bool:
+        """The path that takes per-pair counts on the device: fp16, hip glue, the kernel attention and
+        the chained layers (chain_ok)."""
+        d = self.transformers[0].self_attn.Wqkv.in_features if self.n_layers else desc0.shape[-1]
+        return (self.glue == "hip" and self.attention is _kernel_attention and desc0.is_cuda and
+                desc0.dtype == torch.float16 and self.posenc.Wr.weight.dtype == torch.float16 and
+                self.chain_ok(desc0.new_empty((1, 0, d)), m, n))  # (x after input_proj: [.., d] in desc0's dtype)
+
     def _ragged(self, kpts0, kpts1, desc0, desc1, counts0, counts1, threshold: Optional[float]):
         """forward (threshold None) or match_batch on a padded batch with per-pair counts. fp16 hip
         path with the kernel attention and the chained layers (chain_ok): the equal-size forward with
@@ -805,10 +968,7 @@ class LightGlueMatcher(nn.Module):
         h0, c0 = self._counts(counts0, pr, m, "counts0", dev)
         h1, c1 = self._counts(counts1, pr, n, "counts1", dev)
         d = self.transformers[0].self_attn.Wqkv.in_features if self.n_layers else desc0.shape[-1]
-        fast = (self.glue == "hip" and self.attention is _kernel_attention and desc0.is_cuda and
-                desc0.dtype == torch.float16 and self.posenc.Wr.weight.dtype == torch.float16 and
-                self.chain_ok(desc0.new_empty((1, 0, d)), m, n))  # (x after input_proj: [.., d] in desc0's dtype)
-        if fast:
+        if self._lens_fast(desc0, m, n):
             out = self._forward(kpts0, kpts1, desc0, desc1, threshold, lens=(c0, c1))
             return out if threshold is None else out[2]
         h0 = h0 if h0 is not None else c0.tolist()  # (device counts off the fast path: one synchronisation)
@@ -1002,6 +1162,119 @@ class LightGlueMatcher(nn.Module):
             batch.append(t)
         return self.match_batch(*batch, counts0=c0, counts1=c1), c0, c1
 
+    # ---- adaptive depth and width ----
+    def _token_params(self, li: int, dtype: torch.dtype):
+        """Layer li's (w_tok, b_tok, w_match, b_match) as lg_token_scores reads them (cached)."""
+        tok, mat = self.token_confidence[li].token[0], self.log_assignment[li].matchability
+        return _cached(self.token_confidence[li], "_token_params", (tok.weight, tok.bias, mat.weight, mat.bias), dtype,
+                       lambda: (tok.weight.reshape(-1), tok.bias.reshape(-1), mat.weight.reshape(-1), mat.bias.reshape(-1)))
+
+    def match_adaptive(self, kpts0, kpts1, desc0, desc1, counts0=None, counts1=None,
+                       trace: Optional[list] = None) -> AdaptiveResult:
+        """match_batch with adaptive depth and width (the published LightGlue rules). After each layer
+        i < L - 1 every valid row gets conf = sigmoid(token_confidence[i](x)) and mtch =
+        sigmoid(log_assignment[i].matchability(x)), and with t_i = adaptive_thresholds(L)[i]:
+          depth_confidence > 0: a pair passes when 1 - #(conf < t_i) / #valid > depth_confidence (both
+            images' valid rows); when every pair passes the forward stops and log_assignment[i] is the head;
+          width_confidence > 0, per image whose row dimension exceeds prune_min_keypoints: a row is kept when
+            mtch > float32(1 - width_confidence), with depth on also when conf <= t_i; a segment (one image
+            of one pair) never empties (keep_rule); the kept rows go on, in their order.
+        Returns AdaptiveResult: the matches of the last layer run on the surviving rows, in original index
+        space. trace (a list): receives per checked layer a dict (layer, threshold, stats [P][4] = (kept0,
+        kept1, unconfident, valid), stop, dims = the layout that goes on, kept0 / kept1 = per pair the
+        original indices that go on), which adaptive_reference(decisions=) follows; it costs copies.
+
+        The fp16 hip path (forward's ragged fast path) runs the chained layer launches with the counts on
+        the device; at a checked layer boundary the next layer's Wqkv is not folded into the FFN launch
+        (its rows may be compacted first). lg_token_scores' [P, 4] stats are copied to pinned memory and
+        the host waits for that copy: ONE synchronisation per checked layer, so this method cannot be
+        captured in a graph. Rows are then compacted (lg_compact_rows) into the layout compact_dims gives
+        and the forward goes on at the smaller shape. Every other case (fp32, glue='torch', a substituted
+        attention=, off-size shapes): adaptive_reference. With both knobs <= 0: match_batch's launches and
+        bits, stop = n_layers, prune0 = prune1 = None."""
+        if not self.adaptive:
+            return AdaptiveResult(self.match_batch(kpts0, kpts1, desc0, desc1, counts0, counts1), self.n_layers, None, None)
+        pr, m, n = desc0.shape[0], desc0.shape[1], desc1.shape[1]
+        if not self._lens_fast(desc0, m, n):
+            return adaptive_reference(self, kpts0, kpts1, desc0, desc1, counts0, counts1, trace=trace)
+        dev, dt = desc0.device, desc0.dtype
+        h0, c0 = self._counts(counts0, pr, m, "counts0", dev)
+        h1, c1 = self._counts(counts1, pr, n, "counts1", dev)
+        if self.pair_inputs_ok(kpts0, kpts1, desc0, desc1):
+            x, cos, sin = _Hip.pair_inputs(desc0, desc1, kpts0, kpts1, self.posenc.Wr.weight)
+        else:
+            x = self.input_proj(torch.cat((desc0, desc1), 1))
+            cos, sin = self.posenc(torch.cat((kpts0, kpts1), 1).to(x.dtype))
+            x = x.reshape(1, pr * (m + n), x.shape[-1])
+            cos, sin = cos.reshape(1, pr * (m + n), -1).contiguous(), sin.reshape(1, pr * (m + n), -1).contiguous()
+        layers, nl = self.transformers, self.n_layers
+        depth, width = self.depth_confidence > 0, self.width_confidence > 0
+        thr = adaptive_thresholds(nl)
+        t_keep = _f32(1.0 - self.width_confidence) if width else 0.0
+        kinds = self._chain_kinds(x.shape[1])
+        pinned = self.__dict__.get("_stats_pinned")
+        if pinned is None or tuple(pinned.shape) != (max(nl - 1, 1), pr, 4):
+            pinned = self.__dict__["_stats_pinned"] = torch.empty((max(nl - 1, 1), pr, 4), dtype=torch.int32).pin_memory()
+        prune = tuple(torch.zeros((pr, k), dtype=torch.int32, device=dev) for k in (m, n))
+        lens, ind, mc, nc = (c0, c1), (None, None), m, n
+        host = [h0, h1]                     # (the counts on the host, where known: the trace's index maps)
+        v, stop = None, nl
+        for li, layer in enumerate(layers):
+            sa, ca = layer.self_attn, layer.cross_attn
+            splits = (mc, nc, pr)
+            wq, bq = _qkv_perm(sa, dt)
+            qkv = _Hip.linear_qkv_rotary(x, wq, bq, cos, sin, sa.heads, splits)
+            a0, a1 = _kernel_attention_lens(qkv, lens, (lens[0], lens[1]))
+            _, b0 = _ffn_in_fused(sa, sa.out_proj, dt)
+            wc, bc = _cross_qkv(ca, dt)
+            if "s" in kinds:
+                pk = _ffn_packed(sa, sa.out_proj, dt, ("_x", (ca.to_qk.weight, ca.to_qk.bias, ca.to_v.weight, ca.to_v.bias),
+                                                       lambda ca=ca: _cross_qkv(ca, dt)[0]))
+                x, ((qk0, qk1), (v0, v1)) = _Hip.ffn_proj(x, a0, a1, b0, sa.ffn[1], sa.ffn[3].bias, pk, 1, bc, splits)
+            else:
+                w0, _ = _ffn_in_fused(sa, sa.out_proj, dt)
+                x = _Hip.ffn(x, a0, a1, w0, b0, sa.ffn[1], sa.ffn[3].weight, sa.ffn[3].bias, _ffn_packed(sa, sa.out_proj, dt))
+                (qk0, qk1), (v0, v1) = _Hip.linear_split2(x, wc, bc, ca.heads, splits)
+            m0, m1 = _kernel_attention_lens([(qk0, qk1, v1), (qk1, qk0, v0)], lens, (lens[1], lens[0]))
+            w0, b0 = _ffn_in_fused(ca, ca.to_out, dt)
+            if li + 1 == nl and "h" in kinds:
+                head = self.log_assignment[li]
+                _, b3 = head.aug_weights(dt, 512)
+                hp = (head.final_proj.weight, head.final_proj.bias, head.matchability.weight, head.matchability.bias)
+                pk = _ffn_packed(ca, ca.to_out, dt, ("_h", hp, lambda head=head: head.aug_weights(dt, 512)[0]))
+                x, v = _Hip.ffn_proj(x, m0, m1, b0, ca.ffn[1], ca.ffn[3].bias, pk, 3, b3, splits, n_store=384)
+            else:  # (a checked boundary: the next Wqkv runs on the compacted rows)
+                x = _Hip.ffn(x, m0, m1, w0, b0, ca.ffn[1], ca.ffn[3].weight, ca.ffn[3].bias, _ffn_packed(ca, ca.to_out, dt))
+            if li + 1 == nl:
+                break
+            flags = ((_lib.ADAPT_DEPTH if depth else 0) | (_lib.ADAPT_WIDTH0 if width and mc > self.prune_min_keypoints else 0) |
+                     (_lib.ADAPT_WIDTH1 if width and nc > self.prune_min_keypoints else 0))
+            _, _, keep, stats = _Hip.token_scores(x, mc, nc, pr, lens, *self._token_params(li, dt), _f32(thr[li]), t_keep, flags)
+            pinned[li].copy_(stats, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+            done.synchronize()               # the one host wait of this layer boundary
+            st = pinned[li].tolist()
+            halt = depth and all(exit_passes(s[2], s[3], self.depth_confidence) for s in st)
+            if not halt and any(s[0] + s[1] < s[3] for s in st):
+                mo, no = compact_dims([s[0] for s in st], [s[1] for s in st])
+                x, cos, sin, ind, lens = _Hip.compact_rows(x, cos, sin, keep, ind, mc, nc, pr, lens, mo, no, prune, li + 1)
+                mc, nc = mo, no
+                host = [[s[0] for s in st], [s[1] for s in st]]
+            if trace is not None:
+                host = [h if h is not None else t.tolist() for h, t in zip(host, lens)]
+                maps = [[(i[p, :c].cpu().long() if i is not None else torch.arange(c)) for p, c in enumerate(h)]
+                        for i, h in zip(ind, host)]
+                trace.append(dict(layer=li, threshold=thr[li], stats=st, stop=halt, dims=(mc, nc), kept0=maps[0], kept1=maps[1]))
+            if halt:
+                stop = li + 1
+                break
+        if v is None:
+            w, b = self.log_assignment[stop - 1].aug_weights(dt, 384)
+            v = _Hip.linear(x, w, b)
+        r = _Hip.assign_matches(v.view(pr, mc + nc, 384), mc, x.shape[-1], self.filter_threshold, lens)
+        return AdaptiveResult(_Hip.matches_scatter(r, ind, lens, m, n, stop, prune), stop, prune[0], prune[1])
+
 
 # --------------------------------------------------------------------------------------------
 # Deterministic synthetic weights and inputs (no checkpoints offline): every parameter is drawn
@@ -1044,3 +1317,100 @@ def synthetic_pair(seed: int, m: int, n: int, input_dim: int = 256, overlap: int
         d1[0, :overlap] = d0[0, src] + 0.2 * synth.normal(seed * 4 + 7, (overlap, input_dim)) / np.sqrt(input_dim)
     d1 = d1 / np.linalg.norm(d1, axis=-1, keepdims=True)
     return tuple(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) for x in (k0, k1, d0, d1))
+
+
+def seeded_confidence_state_dict(seed: int, n_layers: int = 9, descriptor_dim: int = 256) -> dict:
+    """The token_confidence.* entries of an adaptive model (n_layers - 1 weight / bias pairs), drawn as
+    seeded_state_dict draws every other parameter: load {**seeded_state_dict(..), **this}."""
+    out = {}
+    for i in range(n_layers - 1):
+        for kind, shape in (("weight", (1, descriptor_dim)), ("bias", (1,))):
+            name = f"token_confidence.{i}.token.0.{kind}"
+            s = (seed * 1_000_003 + zlib.crc32(name.encode())) & 0x7FFFFFFF
+            arr = synth.normal(s, shape, 1.0 / np.sqrt(shape[-1]) if kind == "weight" else 0.02)
+            out[name] = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+    return out
+
+
+def adaptive_reference(model: "LightGlueMatcher", kpts0, kpts1, desc0, desc1, counts0=None, counts1=None,
+                       trace: Optional[list] = None, decisions: Optional[Sequence[dict]] = None) -> AdaptiveResult:
+    """match_adaptive's semantics in framework ops, one pair at a time on its valid rows (the layers in
+    lock-step over the pairs: the exit is a decision of the whole batch): the path of fp32 models,
+    glue='torch', a substituted attention= and off-size shapes, and the tests' oracle. conf and mtch are
+    computed in fp32 from the layer's output. A pair's row dimension (prune_min_keypoints) is its own
+    count here, and a trace entry's dims are the largest surviving counts (nothing is padded). decisions
+    (a trace of match_adaptive or of this function): follow the recorded stop layer and kept index maps
+    instead of this run's own scores."""
+    nl = model.n_layers
+    if not model.adaptive:
+        return AdaptiveResult(model.match_batch(kpts0, kpts1, desc0, desc1, counts0, counts1), nl, None, None)
+    pr, m, n = desc0.shape[0], desc0.shape[1], desc1.shape[1]
+    dev = desc0.device
+    hosts = []
+    for counts, limit, name in ((counts0, m, "counts0"), (counts1, n, "counts1")):
+        h, t = model._counts(counts, pr, limit, name, dev)
+        hosts.append(h if h is not None else t.tolist())
+    hip = model.glue == "hip"
+    depth, width = model.depth_confidence > 0, model.width_confidence > 0
+    thr = adaptive_thresholds(nl)
+    state = []                              # per pair: [x, cos, sin, ind0, ind1]
+    for p, (a, b) in enumerate(zip(*hosts)):
+        x = model.input_proj(torch.cat((desc0[p:p + 1, :a], desc1[p:p + 1, :b]), 1))
+        cos, sin = model.posenc(torch.cat((kpts0[p:p + 1, :a], kpts1[p:p + 1, :b]), 1).to(x.dtype))
+        state.append([x, cos.reshape(1, a + b, -1).contiguous(), sin.reshape(1, a + b, -1).contiguous(),
+                      torch.arange(a, device=dev), torch.arange(b, device=dev)])
+    prune0 = torch.zeros((pr, m), dtype=torch.int32, device=dev)
+    prune1 = torch.zeros((pr, n), dtype=torch.int32, device=dev)
+    stop = nl
+    for li, layer in enumerate(model.transformers):
+        for s in state:
+            s[0] = layer(s[0], s[1], s[2], (len(s[3]), len(s[4])), model.attention, hip)
+        if li + 1 == nl:
+            break
+        dec = decisions[li] if decisions is not None else None
+        tok, mat = model.token_confidence[li].token[0], model.log_assignment[li].matchability
+        st, keeps = [], []
+        for p, s in enumerate(state):
+            xf, mc = s[0][0].float(), len(s[3])
+            conf = torch.sigmoid(F.linear(xf, tok.weight.float(), tok.bias.float()))[:, 0]
+            mtch = torch.sigmoid(F.linear(xf, mat.weight.float(), mat.bias.float()))[:, 0]
+            ks = []
+            for cf, mt in ((conf[:mc], mtch[:mc]), (conf[mc:], mtch[mc:])):
+                on = width and cf.numel() > model.prune_min_keypoints
+                ks.append(keep_rule(cf, mt, thr[li], model.depth_confidence, model.width_confidence) if on
+                          else torch.ones_like(cf, dtype=torch.bool))
+            if dec is not None:
+                ks = [torch.isin(own, kept[p].to(dev)) for own, kept in ((s[3], dec["kept0"]), (s[4], dec["kept1"]))]
+            keeps.append(ks)
+            st.append([int(ks[0].sum()), int(ks[1].sum()), int((conf < _f32(thr[li])).sum()), conf.numel()])
+        halt = depth and all(exit_passes(s[2], s[3], model.depth_confidence) for s in st)
+        if dec is not None:
+            halt = bool(dec["stop"])
+        if not halt:
+            for p, (s, (k0, k1)) in enumerate(zip(state, keeps)):
+                mc = len(s[3])
+                prune0[p, s[3][~k0]], prune1[p, s[4][~k1]] = li + 1, li + 1
+                rows = torch.cat((k0, k1))
+                s[0], s[1], s[2] = (t[:, rows].contiguous() for t in s[:3])
+                s[3], s[4] = s[3][k0], s[4][k1]
+        if trace is not None:
+            k0s, k1s = [len(s[3]) for s in state], [len(s[4]) for s in state]
+            trace.append(dict(layer=li, threshold=thr[li], stats=st, stop=halt, dims=(max(k0s), max(k1s)),
+                              kept0=[s[3].cpu() for s in state], kept1=[s[4].cpu() for s in state]))
+        if halt:
+            stop = li + 1
+            break
+    head = model.log_assignment[stop - 1]
+    k = min(m, n)
+    i32 = lambda *s: torch.full(s, -1, dtype=torch.int32, device=dev)      # noqa: E731
+    f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)       # noqa: E731
+    res = MatchResult(i32(pr, m), i32(pr, n), f32(pr, m), f32(pr, n), i32(pr, k, 2), f32(pr, k),
+                      torch.zeros((pr,), dtype=torch.int32, device=dev))
+    for p, s in enumerate(state):
+        mc, nc = len(s[3]), len(s[4])
+        scores = head(s[0][:, :mc], s[0][:, mc:], hip)
+        r = filter_matches_dense(scores.float(), model.filter_threshold)
+        one = scatter_matches_reference(r, s[3][None], s[4][None], [mc], [nc], m, n, stop, prune0[p:p + 1], prune1[p:p + 1])
+        for dst, src in zip(res, one):
+            dst[p] = src[0]
+    return AdaptiveResult(res, stop, prune0, prune1)
