@@ -293,6 +293,50 @@ int32_t lg_matches_scatter(const int32_t* matches0, const int32_t* matches1, con
                            float* out_mscores0, float* out_mscores1, int32_t* out_matches, float* out_mscores,
                            int32_t* out_counts, int32_t* prune0, int32_t* prune1, hipStream_t stream);
 
+/* ---- keypoint front end (csrc/lightglue_frontend.hip) ----
+ * SuperPoint's two dense heads (the outputs of convPb and convDb, superpoint.py:157, 172) to the matcher's
+ * inputs (kpts, desc, counts) on the device: simple_nms (superpoint.py:52-69), sample_descriptors (:72-87) and
+ * SuperPointMonoTRT::PostProcess (demo/superpoint_mono_trt.cpp:153-253) without nonzero's synchronisation.
+ * All `batch` images of a call share one size, h = 8 hc, w = 8 wc, and go through every launch together
+ * (batch <= 65,535, h * w <= 2^26, batch * h * w <= 2^30). New symbols only: LG_GLUE_ABI_VERSION stays 4.
+ * Every call checks its arguments before any device call, runs on `stream`, is a no-op for batch == 0 and
+ * clamps every index it forms into range whatever its inputs hold.
+ *
+ * lg_kp_heatmap: logits [batch, 65, hc, wc] (dtype fp16 or fp32, contiguous) -> scores [batch, h, w] fp32
+ * (16-B aligned): the softmax over the 65 channels in fp32 with the maximum subtracted, the dustbin dropped,
+ * channel c of cell (i, j) at pixel (8 i + c / 8, 8 j + c % 8) (superpoint.py:160-165). One launch. */
+int32_t lg_kp_heatmap(int32_t dtype, const void* logits, int32_t hc, int32_t wc, int32_t batch, float* scores,
+                      hipStream_t stream);
+/* lg_kp_nms: simple_nms with radius 0..4 on scores [batch, h, w] fp32 (any h, w >= 1) -> out (not in place):
+ * the first maximum mask and the two suppression rounds with their == comparisons (every member of a
+ * plateau survives) and the pools' -inf padding at the image edge; bitwise the reference's result on finite
+ * input. One launch: 32 x 32 tiles with a halo of 5 * radius, the five pools separable in LDS. */
+int32_t lg_kp_nms(const float* scores, int32_t h, int32_t w, int32_t batch, int32_t radius, float* out,
+                  hipStream_t stream);
+/* lg_kp_select: the candidates of nms [batch, h, w] are the pixels at least `border` pixels inside every edge
+ * with a value > threshold (threshold >= 0); the k best of each image (1 <= k <= 2048, k % 8 == 0) in
+ * descending score, ties by ascending row-major pixel index: count [batch] = min(candidates, k), pix
+ * [batch, k] (row-major pixel index; -1 past the count), score [batch, k] (0 past the count). Bitwise
+ * reproducible. Two launches (a compaction into per-segment lists, then one workgroup per image: radix select
+ * and a bitonic sort), no state kept between calls; workspace (16-B aligned) >= lg_kp_select_workspace(h, w,
+ * batch) bytes. */
+size_t lg_kp_select_workspace(int32_t h, int32_t w, int32_t batch);
+int32_t lg_kp_select(const float* nms, int32_t h, int32_t w, int32_t batch, int32_t border, float threshold, int32_t k,
+                     int32_t* count, int32_t* pix, float* score, void* workspace, hipStream_t stream);
+/* lg_kp_describe: count / pix as lg_kp_select wrote them (count clamped into [0, k], pix into the image) and
+ * the dense descriptors, 256 channels on the hc x wc grid, element (b, c, y, x) at dense[b stride_b + c stride_c
+ * + y stride_y + x stride_x] (dense_dtype fp16 or fp32; strides >= 0: NCHW and channels-last without a copy).
+ * Per keypoint: grid_sample (bilinear, align_corners, zero padding) at ((x - 3.5) / (8 wc - 4.5)) (wc - 1),
+ * likewise y (sample_descriptors / PostProcess:219-232); with dense_normalized == 0 each corner vector is first
+ * divided by max(its channel norm, 1e-12) (superpoint.py:173, fused); the result is divided by max(its norm,
+ * 1e-12). desc [batch, k, 256] and kpts [batch, k, 2] = (xy - (w / 2, h / 2)) / (max(w, h) / 2) in out_dtype,
+ * kpts_px [batch, k, 2] int32 (x, y); rows past the count are zero in all three. One launch, one wave per
+ * keypoint. */
+int32_t lg_kp_describe(int32_t dense_dtype, const void* dense, int64_t stride_b, int64_t stride_c, int64_t stride_y,
+                       int64_t stride_x, int32_t hc, int32_t wc, int32_t batch, int32_t k, const int32_t* count,
+                       const int32_t* pix, int32_t dense_normalized, int32_t out_dtype, void* desc, int32_t* kpts_px,
+                       void* kpts, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

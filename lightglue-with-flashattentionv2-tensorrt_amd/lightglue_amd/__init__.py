@@ -22,8 +22,12 @@ from .matcher import (  # noqa: F401,E402
     adaptive_thresholds,
     seeded_confidence_state_dict,
 )
+from .frontend import Features, KeypointFrontend, frontend_reference  # noqa: F401,E402
 
 __all__ = [
+    "Features",
+    "KeypointFrontend",
+    "frontend_reference",
     "AdaptiveResult",
     "adaptive_reference",
     "adaptive_thresholds",

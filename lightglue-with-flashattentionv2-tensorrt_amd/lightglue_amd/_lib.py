@@ -156,6 +156,13 @@ SIGNATURES.update({
                          _P], _I),
     "lg_matches_scatter": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P,
                             _P, _P, _P], _I),
+    # keypoint front end (csrc/lightglue_frontend.hip)
+    "lg_kp_heatmap": ([_I, _P, _I, _I, _I, _P, _P], _I),
+    "lg_kp_nms": ([_P, _I, _I, _I, _I, _P, _P], _I),
+    "lg_kp_select_workspace": ([_I, _I, _I], _S),
+    "lg_kp_select": ([_P, _I, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P, _P], _I),
+    "lg_kp_describe": ([_I, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I, _I, _I, _I, _P, _P, _I,
+                        _I, _P, _P, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -32,6 +32,9 @@ What is different, and why:
   LightGlue rules the reference ships the pieces of and never uses: a per-layer token confidence stops
   the forward early, a per-layer matchability drops points; ``adaptive_reference`` is the same in
   framework ops (the tests' oracle);
+* ``match_features`` takes two ``frontend.Features`` (``KeypointFrontend``: SuperPoint's dense heads to
+  keypoints, descriptors and device counts on gfx950 kernels) and is ``match_batch`` with those counts,
+  pairs with an empty side masked on the device;
 * ``attention=`` lets tests substitute the oracle for the kernel on CPU; the default path
   requires GPU tensors and fails loudly otherwise (no CPU fallback).
 """
@@ -1142,6 +1145,19 @@ class LightGlueMatcher(nn.Module):
             return self._ragged(kpts0, kpts1, desc0, desc1, counts0, counts1, self.filter_threshold)
         out = self._forward(kpts0, kpts1, desc0, desc1, threshold=self.filter_threshold)[2]
         return out if isinstance(out, MatchResult) else filter_matches_dense(out, self.filter_threshold)
+
+    def match_features(self, f0, f1) -> MatchResult:
+        """match_batch on two frontend.Features (image 0 and image 1 of P pairs) with their device counts:
+        nothing is read back, so extract + match enqueue, or capture, as one piece. The kernels clamp
+        counts into [1, limit], so a pair with no keypoint on either side is masked afterwards on the
+        device: matches -1, scores 0, count 0."""
+        r = self.match_batch(f0.kpts, f1.kpts, f0.desc, f1.desc, counts0=f0.counts, counts1=f1.counts)
+        ok = (f0.counts > 0) & (f1.counts > 0)
+        row, cell = ok[:, None], ok[:, None, None]
+        return MatchResult(torch.where(row, r.matches0, -1), torch.where(row, r.matches1, -1),
+                           torch.where(row, r.scores0, 0.0), torch.where(row, r.scores1, 0.0),
+                           torch.where(cell, r.matches, -1), torch.where(row, r.match_scores, 0.0),
+                           torch.where(ok, r.counts, 0))
 
     def match_pairs(self, pairs):
         """pairs: a sequence of (kpts0 [m_p, 2], kpts1 [n_p, 2], desc0 [m_p, D], desc1 [n_p, D]) of any
