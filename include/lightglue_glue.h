@@ -337,6 +337,43 @@ int32_t lg_kp_describe(int32_t dense_dtype, const void* dense, int64_t stride_b,
                        const int32_t* pix, int32_t dense_normalized, int32_t out_dtype, void* desc, int32_t* kpts_px,
                        void* kpts, hipStream_t stream);
 
+/* ---- SuperPoint encoder (csrc/lightglue_superpoint.hip) ----
+ * The SuperPoint forward up to its two dense heads (superpoint.py:143-172) in fp16: activations are NHWC fp16
+ * ([batch, h, w, c], 16-B aligned), a layer accumulates in fp32, adds its bias (fp16 values) in fp32, applies
+ * ReLU if asked and rounds to fp16 once. Ten launches take images to lg_kp_heatmap's and lg_kp_describe's
+ * inputs: lg_sp_conv1, eight lg_sp_conv3x3 (convPa and convDa as one layer of 512 channels) and lg_sp_heads.
+ * Limits as the front end's (batch <= 65,535, h * w <= 2^26, batch * h * w <= 2^30). New symbols only:
+ * LG_GLUE_ABI_VERSION stays 4. Every call checks its arguments before any device call, runs on `stream`, is
+ * a no-op for batch == 0, keeps no state and uses no atomics.
+ *
+ * Packed weights (fp16, packed once by the host; lightglue_amd.superpoint.pack_conv is the packer): a
+ * convolution weight [cout, cin, kh, kw] (cout % 32 == 0, cin % 16 == 0) is stored fragment-major as
+ * [cout / 32][kh kw][cin / 16][2][32][8]: element (cb, t, ks, hi, r, j) is weight[32 cb + r][16 ks + 8 hi + j]
+ * [t / kw][t % kw], the 16 B lane 32 hi + r feeds v_mfma_f32_32x32x16_f16 as the A operand of tap t, k-step ks.
+ * lg_sp_packed_bytes: the size of that stream for a layer the kernels take (taps 9: cin 64 / 128, cout 64 /
+ * 128 / 256 / 512; taps 1: the heads' cin 256, cout 352), 0 otherwise. */
+#define LG_SP_RELU 1
+#define LG_SP_POOL2 2
+size_t lg_sp_packed_bytes(int32_t taps, int32_t cin, int32_t cout);
+/* lg_sp_conv1: conv1a, 1 -> 64 channels, 3 x 3, pad 1. image [batch, h, w] contiguous (image_dtype fp32 or
+ * fp16), weight [64, 1, 3, 3] and bias [64] fp16 (plain, not packed; 16-B aligned) -> out [batch, h, w, 64].
+ * flags: LG_SP_RELU. */
+int32_t lg_sp_conv1(int32_t image_dtype, const void* image, const void* weight, const void* bias, int32_t h, int32_t w,
+                    int32_t batch, int32_t flags, void* out, hipStream_t stream);
+/* lg_sp_conv3x3: 3 x 3, pad 1 (zeros outside each image), cin 64 / 128 -> cout 64 / 128 / 256 / 512. in
+ * [batch, h, w, cin], w_packed as above (16-B aligned), bias [cout] fp16 (8-B aligned) -> out [batch, h, w,
+ * cout], or with LG_SP_POOL2 (h and w even) the 2 x 2 / stride-2 maximum of that, [batch, h / 2, w / 2, cout].
+ * flags: LG_SP_RELU | LG_SP_POOL2. Not in place. One launch: 8 x 16 pixel tiles, patch and halo in LDS. */
+int32_t lg_sp_conv3x3(const void* in, const void* w_packed, const void* bias, int32_t cin, int32_t cout, int32_t h, int32_t w,
+                      int32_t batch, int32_t flags, void* out, hipStream_t stream);
+/* lg_sp_heads: the two 1 x 1 heads in one launch. in [batch, hc, wc, 512] = cPa | cDa; w_packed the packing of
+ * [convPb's [65, 256] padded with zero rows to 96 ; convDb's [256, 256]] (352 rows) and bias [352] alike (rows
+ * 65..95 unused). convPb reads channels 0..255 -> logits [batch, 65, hc, wc] contiguous (lg_kp_heatmap's input),
+ * convDb channels 256..511 -> dense [batch, hc, wc, 256] (lg_kp_describe's input through channels-last
+ * strides). No ReLU. */
+int32_t lg_sp_heads(const void* in, const void* w_packed, const void* bias, int32_t hc, int32_t wc, int32_t batch,
+                    void* logits, void* dense, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

@@ -23,11 +23,21 @@ from .matcher import (  # noqa: F401,E402
     seeded_confidence_state_dict,
 )
 from .frontend import Features, KeypointFrontend, frontend_reference  # noqa: F401,E402
+from .superpoint import (  # noqa: F401,E402
+    SuperPointEncoder,
+    match_images,
+    seeded_superpoint_state_dict,
+    superpoint_reference,
+)
 
 __all__ = [
     "Features",
     "KeypointFrontend",
     "frontend_reference",
+    "SuperPointEncoder",
+    "match_images",
+    "seeded_superpoint_state_dict",
+    "superpoint_reference",
     "AdaptiveResult",
     "adaptive_reference",
     "adaptive_thresholds",

@@ -28,6 +28,9 @@ STATUS_WORKSPACE = 3
 ADAPT_DEPTH = 1
 ADAPT_WIDTH0 = 2
 ADAPT_WIDTH1 = 4
+# include/lightglue_glue.h LG_SP_* (lg_sp_conv1 / lg_sp_conv3x3 flags)
+SP_RELU = 1
+SP_POOL2 = 2
 
 BATCH = 1
 NUM_HEADS = 4
@@ -163,6 +166,11 @@ SIGNATURES.update({
     "lg_kp_select": ([_P, _I, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P, _P], _I),
     "lg_kp_describe": ([_I, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I, _I, _I, _I, _P, _P, _I,
                         _I, _P, _P, _P, _P], _I),
+    # SuperPoint encoder (csrc/lightglue_superpoint.hip)
+    "lg_sp_packed_bytes": ([_I, _I, _I], _S),
+    "lg_sp_conv1": ([_I, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
+    "lg_sp_conv3x3": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "lg_sp_heads": ([_P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -6,8 +6,9 @@ The reference turns the detector logits (``convPb``'s output) and the dense desc
 five 9 x 9 max-pools, about a dozen framework ops, and a ``nonzero`` that makes the host wait for each image's
 count. ``KeypointFrontend`` does the same in at most five launches for any number of images (include/
 lightglue_glue.h, "keypoint front end"; csrc/lightglue_frontend.hip) and leaves the counts on the device, as
-the int32 table ``LightGlueMatcher.match_batch`` takes under stream capture. The CNN itself stays with the
-framework.
+the int32 table ``LightGlueMatcher.match_batch`` takes under stream capture. The CNN in front of it is
+``superpoint.SuperPointEncoder`` (ten launches on the lg_sp_* kernels), whose ``heads`` writes both inputs in
+the layouts ``extract`` reads in place; the heads of a framework SuperPoint are taken just the same.
 
 ``frontend_reference`` and the ``*_reference`` stages are the same contract in framework ops (CPU or GPU):
 our restatement of those three reference pieces with the one rule they leave open pinned — among equal
