@@ -133,6 +133,29 @@ def test_knobs_off_equals_match_batch():
     assert isinstance(res, matcher.AdaptiveResult) and res.result._fields == FIELDS
 
 
+def test_full_depth_loop_equals_match_batch():
+    """depth_confidence = 1.0 with width off: 1 - unconfident / valid > 1.0 never holds and nothing is
+    pruned, so the adaptive loop (not the knobs-off shortcut) runs all L layers and must give match_batch."""
+    from lightglue_amd import matcher
+
+    model, res, trace = _run(1.0, -1.0)
+    batch, c0, c1 = _batch()
+    m, n = batch[0].shape[1], batch[1].shape[1]
+    with torch.no_grad():
+        want = model.match_batch(*batch, counts0=c0, counts1=c1)
+        via = model.match_adaptive(*batch, counts0=c0, counts1=c1)
+    assert model.adaptive and res.stop == via.stop == L == 3
+    assert len(trace) == 2 and all(e["stop"] is False and e["dims"] == (120, 97) for e in trace)
+    for r in (res, via):
+        for prune, counts, size in ((r.prune0, c0, m), (r.prune1, c1, n)):
+            valid = torch.arange(size)[None] < torch.tensor(counts)[:, None]
+            assert torch.equal(prune, torch.where(valid, 3, 0).to(torch.int32))
+        for f in FIELDS:
+            assert torch.equal(getattr(r.result, f), getattr(want, f)), f
+    assert int(want.counts.sum()) >= 1
+    assert isinstance(via, matcher.AdaptiveResult)
+
+
 def test_state_dict_contract():
     from lightglue_amd import matcher
 

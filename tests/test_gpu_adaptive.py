@@ -364,6 +364,32 @@ def test_matcher_knobs_off_is_match_batch(dev):
         assert _same_bits(getattr(got.result, f), getattr(want, f)), f
 
 
+def test_matcher_full_depth_loop_is_match_batch(dev):
+    """depth_confidence = 1.0 with width off: the exit (1 - unconfident / valid > 1.0) never holds and
+    nothing is pruned, so match_adaptive's own loop runs all L layers on the fast path; it launches the
+    layer step match_batch launches, so the bits are match_batch's, whichever projections that one folds."""
+    batch, c0, c1 = _inputs()
+    model = _model((1.0, -1.0))
+    trace = []
+    with torch.no_grad():
+        got = model.match_adaptive(*batch, counts0=c0, counts1=c1, trace=trace)
+        want = model.match_batch(*batch, counts0=c0, counts1=c1)
+        model.chain_kinds = "sh"
+        try:
+            want_sh = model.match_batch(*batch, counts0=c0, counts1=c1)
+        finally:
+            del model.chain_kinds
+    torch.cuda.synchronize()
+    assert model.adaptive and got.stop == L and len(trace) == L - 1 and all(e["stop"] is False for e in trace)
+    for prune, counts in ((got.prune0, c0), (got.prune1, c1)):
+        valid = torch.arange(prune.shape[1], device=dev)[None] < torch.tensor(counts, device=dev)[:, None]
+        assert torch.equal(prune, torch.where(valid, L, 0).to(torch.int32))
+    assert int(want.counts.min()) >= 1
+    for f in FIELDS:
+        assert _same_bits(getattr(got.result, f), getattr(want, f)), f
+        assert _same_bits(getattr(got.result, f), getattr(want_sh, f)), (f, "sh")
+
+
 def _check_decisions(knobs, res, trace, c0, c1):
     """The recorded decisions are the rules applied to the recorded stats."""
     from lightglue_amd.matcher import adaptive_thresholds, compact_dims, exit_passes
