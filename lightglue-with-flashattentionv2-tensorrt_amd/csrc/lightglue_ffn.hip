@@ -287,26 +287,9 @@ struct Proj3 {
     f16* out[6];        // SPLIT2: a0 a1 b0 b1; QKV: q0 k0 v0 q1 k1 v1 (per-image head-major); PLAIN: [m, n_store]
     int n_store;        // E3_PLAIN: channels stored per row (the first n_store of 32 NB3 8)
 };
-// The A tile in two halves (LG_FFN_AHALF, default 1; 0: one tile wait, round 6's first form): the
-// x half's loads first, phase 1's first 256 k on it, the heads half written to LDS halfway through.
-#ifndef LG_FFN_AHALF
-#define LG_FFN_AHALF 1
-#endif
-// The weight stream's wave sync (A/B, -DLG_FFN_SYNC=<pieces>): a workgroup barrier every that many
-// 1-KiB pieces per wave inside each phase, so that no wave runs ahead of the others' streams. The
-// waves of a workgroup finish phase 1 ~3.8 k cycles apart (stamps: the LayerNorm's first barrier
-// waits for the slowest); with a barrier every 8 pieces 0.5 k apart, but phase 1 itself takes that
-// much longer: the CU's stream is bandwidth-bound either way (P = 1 / 4 / 16 FFN 10.0 / 14.6 / 46.0
-// us shipped, 10.1 / 15.1 / 46.4 with 8; forwards equal; profiles/r06/ffn_wave_sync_ab.jsonl). Off.
-#ifndef LG_FFN_SYNC
-#define LG_FFN_SYNC 0
-#endif
-#define FFN_SYNC(pieces_done, pieces_total)                                                   \
-    do {                                                                                      \
-        if constexpr (LG_FFN_SYNC > 0) {                                                      \
-            if ((pieces_done) % LG_FFN_SYNC == 0 && (pieces_done) < (pieces_total)) __builtin_amdgcn_s_barrier(); \
-        }                                                                                     \
-    } while (0)
+// (Tried and dropped: a workgroup barrier every few 1-KiB pieces of the weight stream, so that no wave
+// runs ahead of the others' streams; P = 1 / 4 / 16 FFN 10.0 / 14.6 / 46.0 us without, 10.1 / 15.1 / 46.4
+// with one every 8: the CU's stream is bandwidth-bound either way, profiles/r06/ffn_wave_sync_ab.jsonl.)
 // Diagnostic build (-DLG_FR_STAMPS, tools/fr_stamps.py; never shipped): per wave of the first 256
 // workgroups, s_memtime cycles of chained segments (0 entry -> A in LDS, 1 phase 1, 2 LayerNorm + GELU,
 // 3 phase 2, 4 epilogue), read back by lg_diag_fr_stamps.
@@ -362,10 +345,10 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
 
     // ---- A tile: row 8 i + wave, 16-B unit `lane` (x: units 0..31, head h of the attention output:
     // units 32 + 8 h .. + 7), loaded whole-row coalesced; rows past m repeat row m - 1 ----
-    // LG_FFN_AHALF (32-row tiles; the 64-row form measured 45.6 -> 47.6 us with it at P = 16): the x half
-    // first, then the heads half — row 16 i + 2 w + lane / 32, unit lane % 32 of each; phase 1's first
+    // The A tile in two halves (32-row tiles; the 64-row form measured 45.6 -> 47.6 us with it at P = 16): the
+    // x half first, then the heads half — row 16 i + 2 w + lane / 32, unit lane % 32 of each; phase 1's first
     // half (k < 256) runs on x while the heads land
-    constexpr bool AH = LG_FFN_AHALF && MB == 1;
+    constexpr bool AH = MB == 1;
     f16x8 av[AH ? 1 : 4 * MB], ax[2 * MB], ac[2 * MB];
     if constexpr (AH) {
 #pragma unroll
@@ -501,7 +484,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
         }
         af = an;
         __builtin_amdgcn_sched_barrier(0);
-        FFN_SYNC(2 * (j + 1), 2 * NS1);
     }
 
     FR_SEG(1);
@@ -586,7 +568,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
         for (int mb = 0; mb < MB; ++mb) o2[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa, hf.v[mb], o2[mb], 0, 0, 0);
         hf = hn;
         __builtin_amdgcn_sched_barrier(0);
-        FFN_SYNC(j + 1 - NS1, NS1);
     }
     FR_SEG(3);
     if constexpr (MB > 1) {  // (the staging rows lie over h: every wave done reading it)
@@ -664,7 +645,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
                 for (int mb = 0; mb < MB; ++mb) a3[b][mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w3[b], xf.v[mb], a3[b][mb], 0, 0, 0);
             xf = xn;
             __builtin_amdgcn_sched_barrier(0);
-            FFN_SYNC(NB3 * (j + 1), NB3 * NS3);
         }
         // epilogue: fp16(acc + b3) (+ rotary for q, k) as the standalone projections compute it, the
         // wave's rows x 32 channels of a block staged (its own rows of the staging region), then two
@@ -680,12 +660,7 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
                     const f16x4 b4 = *(__attribute__((address_space(3))) f16x4*)(lds + kB3 + c * 2);
                     f16x4 v = f16x4{lin_val(a3[b][mb][4 * g], b4[0]), lin_val(a3[b][mb][4 * g + 1], b4[1]),
                                     lin_val(a3[b][mb][4 * g + 2], b4[2]), lin_val(a3[b][mb][4 * g + 3], b4[3])};
-#ifndef LG_FR_ABL
-                    constexpr int kAbl = 0;
-#else
-                    constexpr int kAbl = LG_FR_ABL;  // diagnostic builds: 1 no rotary, 2 no phase-3 stores
-#endif
-                    if constexpr (E3 == E3_QKV && kAbl != 1) {
+                    if constexpr (E3 == E3_QKV) {
                         if (cb < 2 * NO) {  // q, k: rotary pairs (d, d + 1) from this row's tables
                             const int rw = 32 * mb + r;  // (tile row; rows past m hold row m - 1's tables)
                             const f16x4 cc = *(__attribute__((address_space(3))) f16x4*)(lds + kCS + rw * kCSP + (c % kD) * 2);
@@ -713,9 +688,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
                         dst = q3.out[E3 == E3_QKV ? (lr.first ? 0 : 3) + part : (lr.first ? 0 : 1) + 2 * part] + lr.off +
                               cb % kD + 16 * half;
                     }
-#ifdef LG_FR_ABL
-                    if (LG_FR_ABL == 2) dst = nullptr;
-#endif
                     if (dst) {
                         *reinterpret_cast<f16x8*>(dst) = v0;
                         *reinterpret_cast<f16x8*>(dst + 8) = v1;
@@ -728,8 +700,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
 #ifdef LG_FR_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     FR_SEG(5);  // (phase 3 and its epilogue; segment 4 then ends at phase 2's stores)
-#endif
-#ifdef LG_FR_STAMPS
     if (lane == 0 && blockIdx.x < 256) {
         unsigned long long* d = g_fr_stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
         for (int k = 0; k < 5; ++k) d[k] = fr_[k];
@@ -796,7 +766,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
 
     // ---- A tile (two 16-B units a thread: row f / 64, unit f % 64), the vectors; rows past m repeat
     // row m - 1 ----
-#if LG_FFN_AHALF
     // (row tid / 32: its x unit tid % 32 first, then its heads unit; phase 1's first half runs on x)
     f16x8 ax, ac;
     {
@@ -805,22 +774,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
         const LinRow lr = lin_row(p, grow, (tid & 31) >> 3);
         ac = *reinterpret_cast<const f16x8*>((lr.first ? p.ctx0 : p.ctx1) + lr.off + (tid & 7) * 8);
     }
-#else
-    f16x8 av[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int f = 512 * i + tid, row = f >> 6, u = f & 63;
-        const int grow = min(m0 + row, p.m - 1);
-        const f16* src;
-        if (u < 32) {
-            src = p.a + (size_t)grow * (K / 2) + u * 8;
-        } else {
-            const LinRow lr = lin_row(p, grow, (u - 32) >> 3);
-            src = (lr.first ? p.ctx0 : p.ctx1) + lr.off + ((u - 32) & 7) * 8;
-        }
-        av[i] = *reinterpret_cast<const f16x8*>(src);
-    }
-#endif
     f16x8 pv = {};
     if (tid < 224) {
         const f16* const pvs = tid < 64 ? p.bias : tid < 128 ? gamma : tid < 192 ? beta : b2;
@@ -859,15 +812,7 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
         if (i + R < NPS) w_[i % R] = piece(i + R);
         return w;
     };
-#if LG_FFN_AHALF
     *(lds_f16x8*)(lds + kA + tile_unit(tid >> 5, tid & 31)) = ax;
-#else
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int f = 512 * i + tid;
-        *(lds_f16x8*)(lds + kA + tile_unit(f >> 6, f & 63)) = av[i];
-    }
-#endif
     if (tid < 224) *(lds_f16x8*)(lds + kPar + tid * 16) = pv;
     if (tid < NVB) {
         *(lds_f16x8*)(lds + kB3 + tid * 16) = v3;
@@ -887,19 +832,16 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
         f16x8 w4[4];
 #pragma unroll
         for (int b = 0; b < 4; ++b) w4[b] = take(4 * s + b);
-#if LG_FFN_AHALF
         if (s + 1 == 8) {  // the heads half into LDS before step 8's fragments are read
             *(lds_f16x8*)(lds + kA + tile_unit(tid >> 5, 32 + (tid & 31))) = ac;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-#endif
         const f16x8 bn = s + 1 < 16 ? *(lds_f16x8*)(lds + kA + tile_unit(r, 4 * (s + 1) + q)) : bf;
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w4[b], bf, acc[b], 0, 0, 0);
         bf = bn;
         __builtin_amdgcn_sched_barrier(0);
-        FFN_SYNC(4 * (s + 1), 64);
     }
     FR_SEG(1);
 
@@ -972,7 +914,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
         o2[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb, hf, o2[1], 0, 0, 0);
         hf = hn;
         __builtin_amdgcn_sched_barrier(0);
-        FFN_SYNC(2 * (s + 1), 32);
     }
     FR_SEG(3);
     // ---- out = fp16(fp16(acc + b2) + x): fp16(acc + b2) into the x' tile, then one 16-B unit a thread
@@ -1027,7 +968,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
             for (int b = 0; b < NBP; ++b) a3[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w3[b], xf, a3[b], 0, 0, 0);
             xf = xn;
             __builtin_amdgcn_sched_barrier(0);
-            FFN_SYNC(NBP * (s + 1), 8 * NBP);
         }
         FR_SEG(5);  // (the projection's MFMA loop; its epilogue: segment 6)
         // epilogue: fp16(acc + b3) (+ rotary for q, k) into the staging rows, then one 16-B unit a thread
@@ -1038,12 +978,10 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
             const f16x4 b4 = *(__attribute__((address_space(3))) f16x4*)(lds + kB3 + c * 2);
             f16x4 v = f16x4{lin_val(a3[b][0], b4[0]), lin_val(a3[b][1], b4[1]), lin_val(a3[b][2], b4[2]),
                             lin_val(a3[b][3], b4[3])};
-#ifndef LG_FR_ABL
-            constexpr int kAbl = 0;
-#else
-            constexpr int kAbl = LG_FR_ABL;  // diagnostic builds: 1 no rotary, 2 no phase-3 stores
-#endif
-            if constexpr (E3 == E3_QKV && kAbl != 1) {
+            // (a declaration, not the bare test in the `if`: without one here the compiler swaps the operands
+            // of phase 2's v_pk_add_f16 in the SPLIT2 forms — same results, but not the recorded instructions)
+            constexpr bool ROT = E3 == E3_QKV;
+            if constexpr (ROT) {
                 if (c < 2 * NO) {  // q, k: rotary pairs (d, d + 1) from this row's tables
 #pragma unroll
                     for (int t = 0; t < 4; t += 2) rot_pair(v, t, rc[b][t], rs[b][t], rc[b][t + 1], rs[b][t + 1]);
@@ -1061,9 +999,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
 #pragma unroll
                     for (int j = 0; j < U3 / 32; ++j) {
                         const int u = t + 32 * j;
-#ifdef LG_FR_ABL
-                        if (LG_FR_ABL == 2) continue;
-#endif
                         if (SP > 1 && ((8 * u) % (16 * NB)) / (16 * NBP) != part) continue;  // (another part's)
                         if (8 * u < q3.n_store)
                             *reinterpret_cast<f16x8*>(q3.out[0] + (size_t)grow * q3.n_store + 8 * u) =
@@ -1078,9 +1013,6 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
                         if (SP > 1 && ((8 * u) % (16 * NB)) / (16 * NBP) != part) continue;  // (another part's)
                         const f16x8 v = *(lds_f16x8*)(lds + kS3 + row * (U3 * 16) + ((u ^ row) << 4));
                         f16* const dst = q3.out[E3 == E3_QKV ? (lr.first ? 0 : 3) + j : (lr.first ? 0 : 1) + 2 * j] + off;
-#ifdef LG_FR_ABL
-                        if (LG_FR_ABL == 2) continue;
-#endif
                         *reinterpret_cast<f16x8*>(dst) = v;
                     }
                 }

@@ -155,8 +155,8 @@ __global__ __launch_bounds__(256) void linear_kernel(LinArgs p) {
     }
 }
 
-// ---- the 256-row forms, for launches with many rows (several image pairs per forward) ----
-// Persistent tiles of MT rows x NT channels (256 x 128 or 256 x 256 on 8 waves, 128 x 128 on 4), NWV waves as WM (m) x
+// ---- the tile form, for launches with many rows (several image pairs per forward) ----
+// Persistent tiles of MT rows x NT channels (128 x 128 on 4 waves is the one instantiated), NWV waves as WM (m) x
 // WN (n) tiles of 64 rows x NT / WN channels (2 x NB MFMA blocks of 32 x 32), K in BK-deep steps through
 // an NST-stage LDS-DMA ring (16-B units XOR-swizzled on the source address: conflict-free
 // ds_read_b128), NST - 1 steps in flight; the ring runs on across tile seams, so the next tile's
@@ -414,8 +414,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void linear_tile_kernel
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// The tile form (tile_form below): lg_linear_set_wide(0..3) or LG_LINEAR_WIDE forces one (where n
-// allows), for tests and A/B timing; -1 (the default) chooses by size.
+// The tile form (tile_form below): lg_linear_set_wide or LG_LINEAR_WIDE, 0 = the 64 x 64 form, 1..5 = the
+// 128 x 128 form (where n allows), for tests and timing; -1 (the default) chooses by size.
 std::atomic<int> g_wide{-2};
 }  // namespace
 int lightglue::wide_mode() {
@@ -440,43 +440,28 @@ extern "C" int32_t lg_linear_set_wide(int32_t mode) {
 }
 
 namespace {
-// The 256-row tile forms (linear_tile_kernel): 1 = 256 x 128, 2 = 256 x 256 (32-deep K steps, 4
-// stages; plain EPI_BIAS only: the residual / rotary tables and the scatter addressing do not fit
-// beside its accumulators), 4 = 128 x 128 on 4 waves, two workgroups per CU (64-deep K steps through
-// 2 stages). (Round 5's A/B forms 3 = 128 x 256 and 5 = form 4 with 32-deep K steps through 4 stages,
-// both slower, were removed in round 6; 3 and 5 now select 1 and 4.) Form 4 against form 1 (profiles/r05/
-// tile_form4_ab.jsonl, us): qkv 18.5 / 26.6 / 48.8 -> 15.9 / 25.1 / 46.5 at P = 8 / 16 / 32, split2
-// 17.5 -> 17.0 and linear+res 12.2 / 16.9 / 30.7 -> 9.8 / 16.6 / 28.5 (form 1 leaves half the CUs idle
-// at P = 8), cat 14.5 / 24.6 / 45.1 -> 14.8 / 24.3 / 46.0; at P = 4 qkv 10.9 = 10.9, split2 8.6 -> 7.4,
-// linear+res 10.5 (64 x 64) -> 8.1, cat 11.5 -> 9.3; whole forwards P = 4 / 8 / 16 +2.3 / +2.9 / +0.8 %,
-// P = 32 -1.0 % (form_fwd_ab.jsonl): the default below; forms 1 and 2 (the round's earlier default was
-// form 1 from half a round of its tiles) stay for lg_linear_set_wide / LG_LINEAR_WIDE, which force a
-// form where n and the operand alignment allow.
-#ifndef LG_LINEAR_AB_FORMS
-#define LG_LINEAR_AB_FORMS 0  // 1: forms 1 and 2 built (A/B builds: tools/build_linear_variant.sh); the
-#endif                        // shipped library maps them to form 4 (no kernel that its default never runs)
-int tile_form(const LinArgs& p, int epi) {
+// The tile form (linear_tile_kernel): 128 x 128 on 4 waves, two workgroups per CU, 64-deep K steps through 2
+// stages. (Tried and dropped: 256 x 128 and 256 x 256 on 8 waves, 128 x 256, and 32-deep K steps through 4
+// stages; profiles/r05/tile_form4_ab.jsonl, form_fwd_ab.jsonl: qkv 18.5 / 26.6 / 48.8 -> 15.9 / 25.1 / 46.5 us
+// at P = 8 / 16 / 32 against 256 x 128, which leaves half the CUs idle at P = 8.)
+// True: the 128 x 128 form; false: the 64 x 64 form (linear_kernel).
+bool tile_form(const LinArgs& p, int epi) {
     bool al = aligned16(p.bias);
     const int nout = epi == EPI_BIAS ? 1 : epi == EPI_QKV_ROTARY ? 6 : 4;
     for (int i = 0; i < nout; ++i) al = al && aligned16(p.out[i]);
     if (p.res) al = al && aligned16(p.res);
     if (epi == EPI_QKV_ROTARY) al = al && aligned16(p.cosv) && aligned16(p.sinv);
-    if (!al) return 0;
+    if (!al) return false;
     // (the head-major epilogue's element offsets are 32-bit: every per-image output below 2^32 elements;
     // (and it steps through the rows of a tile with one wrap at most: pairs of more than 56 rows)
-    if (epi != EPI_BIAS && ((long long)p.m * p.heads * kD >= (1LL << 32) || p.n0 + p.n1 <= 56)) return 0;
+    if (epi != EPI_BIAS && ((long long)p.m * p.heads * kD >= (1LL << 32) || p.n0 + p.n1 <= 56)) return false;
+    // forced (wide_mode 0, or 1..5), else by size: from 128 of its tiles and 8,192 rows on
+    // (profiles/r05/tile_form4_ab.jsonl: at 128 tiles it wins linear+res at P = 4 and lg_linear_cat at
+    // P = 2, loses split2 at P = 2 by 1 us; from 192 tiles on it wins or ties every op the matcher calls.
+    // Whole forwards, form_fwd_ab_final.jsonl: P = 2 (4,096 rows) 2 % faster with the 64 x 64 form)
     const int w = lightglue::wide_mode();
-    // by size: the 4-wave 128 x 128 form (two workgroups per CU) from 128 of its tiles and 8,192 rows
-    // on, else the 64 x 64 form (profiles/r05/tile_form4_ab.jsonl: at 128 tiles form 4 wins
-    // linear+res at P = 4 and lg_linear_cat at P = 2, loses split2 at P = 2 by 1 us; from 192 tiles on
-    // it wins or ties every op but lg_linear_cat at P = 32, 2 % behind 256 x 128, which the matcher
-    // does not call there. Whole forwards (form_fwd_ab_final.jsonl): P = 2 (4,096 rows) 2 % faster
-    // with the 64 x 64 form everywhere, P = 4 / 8 / 16 7 / 3 / 1 % faster than form 1 with this rule)
-    int f = w >= 0 ? w : (p.m >= 8192 && (long)((p.m + 127) / 128) * (p.n / 128) >= 128 ? 4 : 0);
-    if (!LG_LINEAR_AB_FORMS && (f == 1 || f == 2 || f == 3)) f = 4;
-    if (f == 2 && p.n % 256 == 0) return (p.res || epi != EPI_BIAS) ? 1 : 2;
-    if (f >= 4 && p.n % 128 == 0) return 4;  // (5: round 5's 32-deep A/B variant of form 4, removed in round 6)
-    return f >= 1 && p.n % 128 == 0 ? 1 : 0;  // (3: round 5's 128 x 256 A/B form, removed in round 6)
+    const bool wide = w >= 0 ? w >= 1 : (p.m >= 8192 && (long)((p.m + 127) / 128) * (p.n / 128) >= 128);
+    return wide && p.n % 128 == 0;
 }
 
 template <int EPI, bool GATHER, bool RES, int MT, int NT, int BK, int NST, int NWV>
@@ -490,34 +475,25 @@ void launch_tile_r(LinArgs& p, hipStream_t stream) {
     else
         hipLaunchKernelGGL((linear_tile_kernel<EPI, GATHER, RES, 512 / BK, MT, NT, BK, NST, NWV>), dim3(grid), dim3(64 * NWV), 0, stream, p);
 }
-template <int EPI, bool GATHER, int MT, int NT, int BK, int NST, int NWV = 8>
+template <int EPI, bool GATHER, int MT, int NT, int BK, int NST, int NWV>
 void launch_tile(LinArgs& p, hipStream_t stream) {
-    constexpr bool WIDE_WAVE = NT * MT / 64 / NWV / 32 > 2;  // 64 x 128 wave tiles
-    if constexpr (EPI == EPI_BIAS && !GATHER && !WIDE_WAVE) {
+    if constexpr (EPI == EPI_BIAS && !GATHER) {
         if (p.res) return launch_tile_r<EPI, GATHER, true, MT, NT, BK, NST, NWV>(p, stream);
     }
-    if constexpr (!(WIDE_WAVE && EPI == EPI_QKV_ROTARY)) launch_tile_r<EPI, GATHER, false, MT, NT, BK, NST, NWV>(p, stream);
+    launch_tile_r<EPI, GATHER, false, MT, NT, BK, NST, NWV>(p, stream);
 }
 
 template <int EPI, bool GATHER>
 int32_t launch(LinArgs& p, hipStream_t stream, const char* what) {
-    int form = tile_form(p, EPI);
-    if (GATHER && form == 2) form = 1;  // (the gather's per-piece sources do not fit beside 64 x 128 wave tiles)
-    switch (form) {
-#if LG_LINEAR_AB_FORMS
-        case 1: launch_tile<EPI, GATHER, 256, 128, 64, 3>(p, stream); break;
-        case 2:
-            if constexpr (!GATHER && EPI == EPI_BIAS) launch_tile<EPI, GATHER, 256, 256, 32, 4>(p, stream);
-            break;
-#endif
-        case 4: launch_tile<EPI, GATHER, 128, 128, 64, 2, 4>(p, stream); break;
-        default:
-            p.mtiles = (p.m + kBM - 1) / kBM;
-            p.total = p.mtiles * (p.n / kBN);
-            if (p.k == 256)
-                hipLaunchKernelGGL((linear_kernel<EPI, GATHER, 2>), dim3(p.total), dim3(256), 0, stream, p);
-            else
-                hipLaunchKernelGGL((linear_kernel<EPI, GATHER, 4>), dim3(p.total), dim3(256), 0, stream, p);
+    if (tile_form(p, EPI)) {
+        launch_tile<EPI, GATHER, 128, 128, 64, 2, 4>(p, stream);
+    } else {
+        p.mtiles = (p.m + kBM - 1) / kBM;
+        p.total = p.mtiles * (p.n / kBN);
+        if (p.k == 256)
+            hipLaunchKernelGGL((linear_kernel<EPI, GATHER, 2>), dim3(p.total), dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL((linear_kernel<EPI, GATHER, 4>), dim3(p.total), dim3(256), 0, stream, p);
     }
     return launched(what);
 }

@@ -179,23 +179,6 @@ __device__ __forceinline__ f32x16 splat16(float x) {
     return f32x16{x, x, x, x, x, x, x, x, x, x, x, x, x, x, x, x};
 }
 
-// Diagnostic ablation switches (tools/ablate_build.sh builds each into lib/exp/; the shipped
-// library defines none of them). Results of an ablated build are wrong by construction.
-#ifndef MHA_ABL
-#define MHA_ABL 0
-#endif
-#define ABL_NO_BARRIER 1
-#define ABL_NO_REFILL 2
-#define ABL_NO_EXP 4
-#define ABL_NO_SOFTMAX 8
-#define ABL_NO_PV 16
-#define ABL_NO_QK 32
-#define ABL_NO_GLOAD 64   // no K/V/Q global loads (LDS and Q hold garbage)
-#define ABL_NO_STORE 128  // no output / partial stores
-#define ABL_K_CONST 256   // K fragments from registers (no K LDS reads)
-#define ABL_V_CONST 512   // V fragments from registers (no V LDS reads)
-__device__ __forceinline__ void keep_live(const f16x8& x) { asm volatile("" ::"v"(x)); }
-
 // In-kernel timestamps (diagnostic build -DMHA_STAMPS only): s_memtime after draining memory.
 #ifdef MHA_STAMPS
 #define STAMP(slot)                                                                                       \
@@ -212,13 +195,6 @@ __device__ __forceinline__ void keep_live(const f16x8& x) { asm volatile("" ::"v
     } while (0)
 #endif
 
-#ifndef MHA_ST_AUX
-#define MHA_ST_AUX 0    // cache policy bits of the output stores (2 = nt, 16 = sc1)
-#endif
-#ifndef MHA_PART_AUX
-#define MHA_PART_AUX 0  // cache policy bits of the split-partial stores
-#endif
-
 // Per-step phase clocks (diagnostic build -DMHA_STEPSTAMPS only): s_memtime at phase boundaries
 // of every full loop step, summed per wave, waited for only at the next step's barrier.
 #ifdef MHA_STEPSTAMPS
@@ -232,11 +208,6 @@ __device__ __forceinline__ void keep_live(const f16x8& x) { asm volatile("" ::"v
 #define TCLK(var) \
     do {          \
     } while (0)
-#endif
-
-#ifndef MHA_PINGPONG
-#define MHA_PINGPONG 0  // measured neutral on the steady loop (vector-issue bound), and it makes the
-                        // fp32-input 8-wave kernel spill: off by default, kept as a switch
 #endif
 
 constexpr float kMaskBias = -65504.f;  // fp16 lowest: a masked key's score, exp2 -> 0
@@ -333,13 +304,6 @@ __device__ __forceinline__ void lds_dma16_s(unsigned m0, unsigned voff, __amdgpu
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
-#ifndef MHA_DMA_ASM
-// 0: the LDS-DMA builtin in the single-pass kernels (A/B hook). 1: the asm DMA in every form of
-// the 16-row kernel (two-pass: lds_dma16; one-pass: lds_dma16_s, whose PVs run under counted waits)
-// and in the two-pass forms of the 32-row kernel, whose one-pass forms keep the builtin.
-#define MHA_DMA_ASM 1
-#endif
-
 // L2 prefetch for the single-pass kernels (issued by one wave per workgroup, before its own
 // loads). A workgroup's DMA requests K of its first tiles at entry but V tile by tile once K(t)
 // is in registers, and the later K tiles once K(0) has landed, so with inputs not already in the

@@ -73,10 +73,6 @@ __device__ __forceinline__ void wait_vm_groups(int groups) {
     }
 }
 
-#ifndef MHA_D2P_EARLY
-#define MHA_D2P_EARLY 1  // two-pass form: second-pass scores between the first pass's PVs (0: after them)
-#endif
-
 // KW waves (key slices) per workgroup x TPW 64-key tiles per wave. (16 waves x 1 tile, four per
 // SIMD, measured 7.7 us against 6.3 us for 8 x 2 at 1x4x1024x1024.)
 // PASSES = 2 (nkv in (1024, 2048], 4 waves): each wave's 2·TPW tiles go through its TPW slots twice;
@@ -160,13 +156,12 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
         // piece i of the wave's key slice (source) into piece li of its region (li = i except in
         // the second pass, whose tile TPW + t goes into slot t)
         auto dma_piece = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, int i, int li) {
-            if (MHA_ABL & ABL_NO_GLOAD) return;
             // asm DMA in the multi-pass forms (no compiler drain before the transposing reads:
             // 1x4x1024x2048 7.28 vs 7.64 us); the one-pass forms measured neutral (1024^2 5.02 vs
             // 5.00, 768^2 4.48 vs 4.28) and keep the builtin. (Their code has the compiler's
             // vmcnt(0) in front of the first transposing read, as the 16-row kernel's had. There,
             // PV under counted waits is worth about 1 % of a call, so this kernel's schedule stays.)
-            if (MHA_DMA_ASM && PASSES > 1) {
+            if (PASSES > 1) {
                 lds_dma16(lds_addr(smem + region + 1024 * li), voff, rs, 1024u * i);
             } else {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(smem + region + 1024 * li),
@@ -202,21 +197,15 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
         f16x8 qraw[4];
         // K(0) and K(1) first: the first tile's K is not queued behind the whole wave's K
         constexpr int KFIRST = TPW < 2 ? TPW : 2;
-#ifndef MHA_D_PREFETCH
-#define MHA_D_PREFETCH 1  // 0: no L2 prefetch (A/B hook)
-#endif
         // L2 prefetch of the rows requested late (mha_hd64_device.h; profiles/r02/prefetch_ab.txt)
         L2Prefetch pf;
-        if constexpr (MHA_D_PREFETCH != 0 && !(MHA_ABL & ABL_NO_GLOAD))
-            l2_prefetch<WAVE_KEYS, kTileKV * KFIRST>(pf, k_rs, v_rs, nkv, qtile,
-                                                     prefetch_group(a.total_blocks, ca.qtiles), lane, wave == 0);
+        l2_prefetch<WAVE_KEYS, kTileKV * KFIRST>(pf, k_rs, v_rs, nkv, qtile, prefetch_group(a.total_blocks, ca.qtiles),
+                                                 lane, wave == 0);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (MHA_ABL & ABL_NO_GLOAD) qraw[s] = f16x8{} + (f16)(lane * 0.01f);
-            else asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen"
-                              : "=v"(qraw[s])
-                              : "v"((unsigned)(q_row * kHeadDim + 16 * s + 8 * hh) * 2), "s"(q_rs));
-        }
+        for (int s = 0; s < 4; ++s)
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen"
+                         : "=v"(qraw[s])
+                         : "v"((unsigned)(q_row * kHeadDim + 16 * s + 8 * hh) * 2), "s"(q_rs));
         dma_k(0, KFIRST);
         // Q and K(0) have landed (issue order: Q, K(0), K(1), 8 pieces per tile)
         wait_vm<8 * (KFIRST - 1)>();
@@ -301,16 +290,6 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
 #pragma unroll
                 for (int ss = 0; ss < 2; ++ss) {
                     if (!refill) read_v(jj, ss);
-                    if (MHA_ABL & ABL_NO_PV) {
-                        keep_live(vfa[jj][ss]);
-                        keep_live(vfb[jj][ss]);
-                        keep_live(pt[jj][ss]);
-                        if (first && jj == 0 && ss == 0) {
-                            o0 = o1 = f32x16{};
-                            l_acc = f32x4{0.f, 0.f, 0.f, 0.f};
-                        }
-                        continue;
-                    }
                     const bool z = first && jj == 0 && ss == 0;  // accumulators start at inline 0
                     o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfa[jj][ss], pt[jj][ss], z ? f32x16{} : o0, 0, 0, 0);
                     o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfb[jj][ss], pt[jj][ss], z ? f32x16{} : o1, 0, 0, 0);
@@ -320,7 +299,6 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
         auto exp_pack = [&](f32x16 c0, f32x16 c1, f16x8(&pt)[2][2]) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                if (MHA_ABL & ABL_NO_EXP) continue;
                 c0[e] = __builtin_amdgcn_exp2f(c0[e]);
                 c1[e] = __builtin_amdgcn_exp2f(c1[e]);
             }
@@ -361,12 +339,6 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
                 }
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    if (MHA_ABL & ABL_NO_QK) {
-                        keep_live(kf[2 * s]);
-                        keep_live(kf[2 * s + 1]);
-                        if (!BF && s == 0) c0 = c1 = zero;
-                        continue;
-                    }
                     c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[2 * s], qf[s], (!BF && s == 0) ? zero : c0, 0, 0, 0);
                     c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[2 * s + 1], qf[s], (!BF && s == 0) ? zero : c1, 0, 0,
                                                                 0);
@@ -432,7 +404,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
             // Later passes: tiles ps·TPW + u through slot u, scored against the running max (bias
             // k-step first), ONE rescale decision per pass (rescaling O and the row sums),
             // exponentials, then PV as each V lands, each PV refilling its slot with the next pass's K.
-            constexpr bool EARLY2 = PASSES == 2 && MHA_D2P_EARLY;
+            constexpr bool EARLY2 = PASSES == 2;  // second-pass scores between the first pass's PVs
             set_bias();
             // scores of tile `tile` in slot u: its K landed (`younger` DMA groups after it), fragments
             // in registers, its V into the slot, then the MFMAs
@@ -563,11 +535,11 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct_kernel(FwdArgs a) 
         acc0 += w * *reinterpret_cast<const f32x4*>(src);
         if constexpr (DPT == 8) acc1 += w * *reinterpret_cast<const f32x4*>(src + 4);
     }
-    if (q < nq && !(MHA_ABL & ABL_NO_STORE)) {
+    if (q < nq) {
         const __amdgpu_buffer_rsrc_t o_rs = make_rsrc(reinterpret_cast<TOut*>(ca.o) + (size_t)bh * nq * kHeadDim,
                                                       (unsigned)(nq * kHeadDim * sizeof(TOut)));
         const float inv = inv_or_nan(L, *reinterpret_cast<const unsigned*>(mlb + KW * BLOCK_M * 2), row);
-        store_dims<TOut, DPT, MHA_ST_AUX>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)), acc0 * inv, acc1 * inv);
+        store_dims<TOut, DPT, 0>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)), acc0 * inv, acc1 * inv);
     }
 #ifdef MHA_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

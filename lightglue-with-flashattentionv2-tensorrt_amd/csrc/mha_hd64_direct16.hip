@@ -64,11 +64,6 @@
     } while (0)
 #endif
 
-#ifndef MHA_D16_WAVES
-#define MHA_D16_WAVES 4  // waves per workgroup for nkv in (512, 1024]; 8 (8 x 2 tiles, two waves per
-                         // SIMD) measured 5.23 against 4.89 us at 1x4x1024^2: an A/B hook only
-#endif
-
 namespace mha_hd64 {
 namespace {
 
@@ -120,15 +115,10 @@ template <typename TOut, int KW, int TPW, bool MULTI, int PASSES = 1, bool F32IN
 __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const void* q0, const void* k0, const void* v0,
                                                                         void* o0, int total_blocks, int nq0, int nkv0,
                                                                         int qtiles0, FwdArgs a) {
-    static_assert(TPW >= 2 && TPW <= 4 && (KW == 4 || KW == 8), "waves x tiles per wave");
-    static_assert(PASSES == 1 || (PASSES == 2 && TPW == 4 && KW == 4), "two passes: 4 waves x 2 x 4 tiles");
-    static_assert(!F32IN || KW == 4, "fp32 inputs: the 4-wave forms");
-#ifndef MHA_D16_STAGE16
-#define MHA_D16_STAGE16 0  // A/B hook: fp16 K/V through VGPRs + ds_write (the F32IN pipeline) instead of LDS-DMA
-#endif
-    // the VGPR-staged pipeline: fp32 inputs always; fp16 inputs under the A/B hook (4-wave forms)
-    constexpr bool STAGED = F32IN || (MHA_D16_STAGE16 && KW == 4);
-    using TIn = std::conditional_t<F32IN, float, f16>;
+    // (Tried and dropped: 8 waves x 2 tiles for nkv in (512, 1024], 5.23 against 4.89 us at 1x4x1024^2.)
+    static_assert(TPW >= 2 && TPW <= 4 && KW == 4, "waves x tiles per wave");
+    static_assert(PASSES == 1 || (PASSES == 2 && TPW == 4), "two passes: 4 waves x 2 x 4 tiles");
+    using TIn = float;  // the VGPR-staged pipeline's input type (F32IN forms only)
     constexpr unsigned ISZ = sizeof(TIn);
     constexpr int BLOCK_M = 16;                     // query rows per workgroup
     constexpr int WAVE_KEYS = kTileKV * TPW * PASSES;
@@ -197,7 +187,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
 #pragma unroll
         for (int db = 0; db < 4; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
         l_acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else if constexpr (STAGED) {
+    } else if constexpr (F32IN) {
         // ---- the Float boundary inside the kernel: fp32 Q/K/V through VGPRs ----
         // fp32 rows are 256 B. Lane L of piece i (rows 8i..8i+7 of a tile) loads the 8 floats of
         // chunk c = L & 7 of row 8i + L/8, rounds them to fp16 (RNE, as the reference's convert
@@ -323,15 +313,9 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
         // the pipeline: store item j, issue item j + NB, then the scores its store made possible;
         // V(t) for t >= 2 is stored just before its PV (its slot's K was read by then); pass 1's
         // K(t) goes into slot t once pass 0's PV(t) has read V(t)
-#ifndef MHA_F32_NB
-#define MHA_F32_NB 0  // fp32 tiles in flight per wave (A/B hook; 0 = per form)
-#endif
-        // 3 for the 2-tile form (1x4x512^2 5.00 vs 5.10 us), 2 for the 4-tile form (the third
-        // buffer lands in AGPRs: 1024^2 7.45-7.51 vs 7.11; tools/f32_probe.py over MHA_F32_NB builds)
-#ifndef MHA_D16_NB16
-#define MHA_D16_NB16 3  // fp16 tiles in flight per wave in the staged A/B form
-#endif
-        constexpr int NB = !F32IN ? MHA_D16_NB16 : MHA_F32_NB > 0 ? MHA_F32_NB : (TPW == 2 ? 3 : 2);
+        // fp32 tiles in flight per wave: 3 for the 2-tile form (1x4x512^2 5.00 vs 5.10 us), 2 for the
+        // 4-tile form (the third buffer lands in AGPRs: 1024^2 7.45-7.51 vs 7.11)
+        constexpr int NB = TPW == 2 ? 3 : 2;
         Tile buf[NB];
 #pragma unroll
         for (int j = 0; j < NB; ++j) ld_tile(j, buf[j]);
@@ -393,7 +377,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
             // counted wait (two-pass forms: 1x4x1024x2048 7.28 vs 7.64 us; one-pass forms, same
             // schedule, profiles/direct_overlap/ab_forced.jsonl `parent_asms` against `parent`:
             // 1024^2 5.07-5.23 vs 5.13-5.30 us, 320^2 3.31-3.39 vs 3.39-3.43, 768^2 and 512^2 equal).
-            if (MHA_DMA_ASM && PASSES == 1) {
+            if (PASSES == 1) {
                 // M0, the offset and the descriptor are SALU values here (region comes from the
                 // wave index read once at entry), so the one-wait-state form is enough;
                 // tools/check_dma_hazards.py audits every piece. The `s_nop 4` of lds_dma16 on
@@ -401,11 +385,8 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
                 // more than the drain did (768^2 4.58-4.73 vs 4.35-4.50 us with the builtin, 512^2
                 // 3.53-3.61 vs 3.46-3.50), which is why the one-pass forms had kept the builtin.
                 lds_dma16_s(lds_addr(smem + region + 1024 * li), voff, rs, 1024u * i);
-            } else if (MHA_DMA_ASM) {
-                lds_dma16(lds_addr(smem + region + 1024 * li), voff, rs, 1024u * i);
             } else {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(smem + region + 1024 * li),
-                                                         16, voff, 1024 * i, 0, 0);
+                lds_dma16(lds_addr(smem + region + 1024 * li), voff, rs, 1024u * i);
             }
         };
         auto dma_k = [&](int t0, int t1) {
@@ -431,22 +412,15 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
         // Q (B operand of Sᵀ = K·Qᵀ): Q[q_row][32s+8g..+7], by inline-asm loads (outside the
         // compiler's wait bookkeeping, which would drain every DMA at their use)
         f16x8 qraw[2], qf[2];
-#ifndef MHA_D16_K0_FIRST
-#define MHA_D16_K0_FIRST 0  // 1: K(0)'s DMA ahead of the Q loads for every form (A/B hook)
-#endif
         // K(0)'s DMA ahead of the Q loads (same wait counts) for the 2-tile form: 1x4x512^2 3.36-3.40
         // vs 3.42-3.52 us; the 4-tile form (the metric call) keeps Q first (4.97-5.04 vs 4.89-4.99)
-        constexpr bool K0F = MHA_D16_K0_FIRST || (TPW == 2 && PASSES == 1);
-#ifndef MHA_D16_PREFETCH
-#define MHA_D16_PREFETCH 1  // 0: no L2 prefetch (A/B hook)
-#endif
+        constexpr bool K0F = TPW == 2 && PASSES == 1;
         // L2 prefetch of the rows requested late (mha_hd64_device.h). Measured at 1x4x1024^2
         // (tools/cold_probe.py, profiles/r02/prefetch_ab.txt): inputs from HBM 6.72 -> 5.7 us,
         // L2-resident inputs +0.02 us (4.65); at 768^2 / 1024x2048 -15 / -22 % cold, +2 % warm.
         L2Prefetch pf;
-        if constexpr (MHA_D16_PREFETCH != 0)
-            l2_prefetch<WAVE_KEYS, 2 * kTileKV>(pf, k_rs, v_rs, nkv, qtile,  // K(0), K(1) at entry
-                                                prefetch_group(total_blocks, ca.qtiles), lane, wave == 0);
+        l2_prefetch<WAVE_KEYS, 2 * kTileKV>(pf, k_rs, v_rs, nkv, qtile,  // K(0), K(1) at entry
+                                            prefetch_group(total_blocks, ca.qtiles), lane, wave == 0);
         if constexpr (K0F) dma_k(0, 1);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
@@ -709,12 +683,8 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
     }
     __syncthreads();
     DSTAMP(5);
-#ifndef MHA_D16_EPI8
-#define MHA_D16_EPI8 0  // 1: 128 threads merge (row, 8 dims) with 16-B stores (A/B hook)
-#endif
-    constexpr int EDPT = MHA_D16_EPI8 ? 8 : 4;            // dims per merging thread
-    constexpr int EMERGE = BLOCK_M * kHeadDim / EDPT;     // merging threads
-    if (EMERGE < 64 * KW && tid >= EMERGE) return;
+    constexpr int EDPT = 4;  // every thread merges (row, 4 dims)
+    static_assert(BLOCK_M * kHeadDim / EDPT == 64 * KW, "one merge item per thread");
     const int row = tid / (kHeadDim / EDPT), c = (tid % (kHeadDim / EDPT)) * EDPT;
     const int q = qtile * BLOCK_M + row;
     float2 ml[KW];
@@ -724,7 +694,7 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
         ml[k] = *reinterpret_cast<const float2*>(mlb + (k * BLOCK_M + row) * 2);
         M = fmaxf(M, ml[k].x);
     }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float L = 0.f;
 #pragma unroll
     for (int k = 0; k < KW; ++k) {
@@ -732,14 +702,12 @@ __global__ __launch_bounds__(64 * KW, 1) void mha_hd64_direct16_kernel(const voi
         L += w * ml[k].y;
         const float* src = reinterpret_cast<const float*>(smem + k * RS) + row * OROW + c;
         acc += w * *reinterpret_cast<const f32x4*>(src);
-        if constexpr (EDPT == 8) acc1 += w * *reinterpret_cast<const f32x4*>(src + 4);
     }
     if (q < nq) {
         const __amdgpu_buffer_rsrc_t o_rs = make_rsrc(reinterpret_cast<TOut*>(ca.o) + (size_t)bh * nq * kHeadDim,
                                                       (unsigned)(nq * kHeadDim * sizeof(TOut)));
         const float inv = 1.f / L;
-        store_dims<TOut, EDPT, MHA_ST_AUX>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)), acc * inv,
-                                           acc1 * inv);
+        store4b<TOut, 0>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)), acc * inv);
     }
 #ifdef MHA_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -764,8 +732,8 @@ hipError_t launch16_t(const FwdArgs& a, int grid, hipStream_t stream) {
 
 hipError_t launch_direct16(const FwdArgs& a, int grid, int tiles_per_wave, bool out_f32, hipStream_t stream,
                            bool in_f32) {
-    // tiles_per_wave counts 64-key tiles per wave of the 8-wave form (1: nkv <= 512, 2: <= 1024);
-    // 4 waves take twice as many
+    // tiles_per_wave counts pairs of 64-key tiles per wave (1: nkv <= 512, 2: <= 1024); each of the
+    // 4 waves takes twice as many tiles
     if (in_f32) {  // fp32 Q/K/V rounded in the kernel: the one-pass forms (the planner's choice)
         if (tiles_per_wave > 2)  // two-pass forms: diagnostic only (MHA_HD64_F32_INKERNEL=2)
             return out_f32 ? launch16_t<float, 4, 4, 2, true>(a, grid, stream)
@@ -783,13 +751,8 @@ hipError_t launch_direct16(const FwdArgs& a, int grid, int tiles_per_wave, bool 
     switch (tiles_per_wave * 2 + (out_f32 ? 1 : 0)) {
         case 2: return launch16_t<f16, 4, 2>(a, grid, stream);
         case 3: return launch16_t<float, 4, 2>(a, grid, stream);
-#if MHA_D16_WAVES == 8
-        case 4: return launch16_t<f16, 8, 2>(a, grid, stream);
-        case 5: return launch16_t<float, 8, 2>(a, grid, stream);
-#else
         case 4: return launch16_t<f16, 4, 4>(a, grid, stream);
         case 5: return launch16_t<float, 4, 4>(a, grid, stream);
-#endif
         default: return hipErrorInvalidValue;
     }
 }

@@ -67,17 +67,14 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
     constexpr int BLOCK_M = 32 * QW * RB;           // query rows per workgroup
     constexpr int SUPER = kTileKV * KW;             // keys per iteration
     constexpr int STAGE_BYTES = KW * 2 * kTileBytes;
-    // LDS ring of super-tiles: step t reads K(t+1) and V(t) and refills super-tile t + NSTAGE-1.
-    // Ping-pong (8-wave workgroups, two waves per SIMD; cdna_hip_programming.md T16): every step is a
-    // load segment (all LDS reads / writes) and a compute segment (all MFMAs + softmax, from
-    // registers), separated by a barrier; waves 4-7 run one segment behind waves 0-3, so each
-    // SIMD pairs one wave's matrix work with its partner's memory work. 4-wave shapes keep one
-    // barrier per step with the LDS work spread over the step.
-    constexpr bool PINGPONG = (NT == 512) && (MHA_PINGPONG != 0);
-    // Offset halves read one segment apart, so the ping-pong ring needs a fourth stage.
+    // LDS ring of super-tiles: step t reads K(t+1) and V(t) and refills super-tile t + NSTAGE-1,
+    // one barrier per step with the LDS work spread over the step.
+    // (Tried and dropped: a ping-pong form of the 8-wave workgroups, load and compute segments of the
+    // two waves of a SIMD offset by a barrier and a fourth stage; neutral on the steady loop, which
+    // is vector-issue bound, and the fp32-input kernel spilled.)
     // KW = 4 workgroups are the single-super-tile shape: every split is one super-tile (the
     // planner guarantees it), so one stage suffices.
-    constexpr int NSTAGE = KW >= 4 ? 1 : (PINGPONG ? 4 : 3);
+    constexpr int NSTAGE = KW >= 4 ? 1 : 3;
     constexpr int NLOAD = (2 * KW * 512) / NT;      // 16-B chunks staged per thread per iteration
     constexpr unsigned SZ = sizeof(TIn);
     static_assert(NLOAD * NT == 2 * KW * 512, "staging must divide evenly");
@@ -145,11 +142,6 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
     // set holding super-tile t+NSTAGE-1 is written to LDS.
     Raw8<TIn> stgA[NLOAD], stgB[NLOAD];
     auto issue = [&](int it, Raw8<TIn>(&stg)[NLOAD]) {
-        if (MHA_ABL & ABL_NO_GLOAD) {
-#pragma unroll
-            for (int i = 0; i < NLOAD; ++i) stg[i] = Raw8<TIn>{};
-            return;
-        }
         const unsigned soff = (unsigned)(st_begin + it) * SUPER * kHeadDim * SZ;
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i) {
@@ -177,8 +169,7 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             Raw8<TIn> t;
-            if (MHA_ABL & ABL_NO_GLOAD) t = Raw8<TIn>{};
-            else bload8(t, q_rs, (unsigned)((q_row0 + 32 * rb) * kHeadDim + 16 * s + 8 * hh) * SZ, 0);
+            bload8(t, q_rs, (unsigned)((q_row0 + 32 * rb) * kHeadDim + 16 * s + 8 * hh) * SZ, 0);
             const f16x8 h = to_f16(t);
 #pragma unroll
             for (int e = 0; e < 8; ++e) qf[rb][s][e] = (f16)((float)h[e] * kScaleLog2);
@@ -250,11 +241,6 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
 
     // K fragments of the tile in stage kstage (A operand of Sᵀ = K·Qᵀ, 8 x ds_read_b128).
     auto read_k = [&](unsigned kstage, f16x8(&kf)[8]) {
-        if (MHA_ABL & ABL_K_CONST) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s) kf[s] = qf[0][s & 3];
-            return;
-        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const unsigned ka = k_addr[s] + kstage;
@@ -268,12 +254,6 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
     auto qk_step = [&](int i, const f16x8(&kf)[8], const f16x8& ab0, const f16x8& ab1, f32x16& s0, f32x16& s1,
                        int rb) {
         const f32x16 zero = {};
-        if (MHA_ABL & ABL_NO_QK) {
-            if (i == 0) s0 = zero;
-            if (i == 1) s1 = zero;
-            if (i >= 2) keep_live(kf[i - 2]);
-            return;
-        }
         if (i == 0) s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ab0, b_bias[rb], zero, 0, 0, 0);
         else if (i == 1) s1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ab1, b_bias[rb], zero, 0, 0, 0);
         else if ((i & 1) == 0)
@@ -316,7 +296,7 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
         // super-tile past this split's last one lands in a stage nobody reads, and past nkv the
         // buffer descriptor returns zeros. A conditional load would make the compiler's vmcnt
         // analysis drain every load at the next LDS write.
-        if (!(MHA_ABL & ABL_NO_REFILL) && may_issue) issue(it + NSTAGE, is);
+        if (may_issue) issue(it + NSTAGE, is);
         TCLK(ck[0]);
 
         // Fragment reads first: K of tile it+1 (phase A) and Vᵀ of tile it (phase B); both stages
@@ -327,16 +307,6 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
         constexpr bool kEarlyV = !(NT == 512 && SZ == 4);
         f16x8 vfa[2][2], vfb[2][2];
         auto read_v = [&]() {
-            if (MHA_ABL & ABL_V_CONST) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int ss = 0; ss < 2; ++ss) {
-                        vfa[j][ss] = qf[0][j + 2 * ss];
-                        vfb[j][ss] = qf[0][(j + 2 * ss + 1) & 3];
-                    }
-                return;
-            }
             const unsigned va0 = v_addr0 + (unsigned)st_cur * STAGE_BYTES;
             const unsigned va1 = v_addr1 + (unsigned)st_cur * STAGE_BYTES;
 #pragma unroll
@@ -348,16 +318,6 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
                     vfb[j][ss] = cat8(tr_read(lds, va1 + rowc), tr_read(lds, va1 + rowc + 8 * 128));
                 }
         };
-        if constexpr (PINGPONG) {
-            // Load segment (ping-pong): every LDS access of the step — K(it+1) and Vᵀ(it) fragments
-            // into registers, the refill of super-tile it+3 — while the partner wave on this SIMD
-            // runs its compute segment; the barrier's lgkmcnt(0) lands them all.
-            if constexpr (HAS_NEXT) read_k((unsigned)st_nxt * STAGE_BYTES, kf);
-            read_v();
-            if (!(MHA_ABL & ABL_NO_REFILL) && may_write) write(st_fill, wr);
-            if (!(MHA_ABL & ABL_NO_BARRIER)) __syncthreads();
-        }
-
         // online-softmax decision for tile `it` (first tile: set the max exactly; later tiles:
         // move it only when some query's tile max exceeds it by > kRescaleThr)
         const bool first = (it == 0);
@@ -377,15 +337,12 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
             }
         }
 
-        if constexpr (!PINGPONG) {
-            if constexpr (HAS_NEXT) read_k((unsigned)st_nxt * STAGE_BYTES, kf);
-            if constexpr (kEarlyV && !HAS_NEXT) read_v();
-        }
+        if constexpr (HAS_NEXT) read_k((unsigned)st_nxt * STAGE_BYTES, kf);
+        if constexpr (kEarlyV && !HAS_NEXT) read_v();
 
         // phase A: QKᵀ(it+1) on the matrix pipe ‖ exp(it) on the vector pipe, pinned as one MFMA
         // followed by three v_exp_f32 per gap (8 + 3·8 issue cycles fill the MFMA's 32).
         auto exp_at = [&](int e) {  // e in [0, 32*RB): query block e/32, score e%32
-            if (MHA_ABL & (ABL_NO_EXP | ABL_NO_SOFTMAX)) return;
             const int rb = e >> 5, i = e & 31;
             if (i < 16) c0[rb][i] = __builtin_amdgcn_exp2f(c0[rb][i]);
             else c1[rb][i - 16] = __builtin_amdgcn_exp2f(c1[rb][i - 16]);
@@ -400,7 +357,7 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
                 for (int rb = 0; rb < RB; ++rb) {
                     qk_step(i, kf, ab0, ab1, n0[rb], n1[rb], rb);
                     // Vᵀ reads queue behind the K reads (phase A carries all fragment reads).
-                    if (!PINGPONG && kEarlyV && i == 2 && rb == 0) read_v();
+                    if (kEarlyV && i == 2 && rb == 0) read_v();
                     const int g = i * RB + rb;
                     exp_at(3 * g);
                     exp_at(3 * g + 1);
@@ -425,35 +382,23 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
                 p[rb][1][1][e] = (f16)c1[rb][8 + e];
             }
 
-        // phase B: Oᵀ += Vᵀ·Pᵀ (it) and the row sums on the matrix pipe ‖ row max (it+1) (and, in
-        // the one-barrier form, the LDS refill of super-tile it+3: its stage held tile it-1).
-        if constexpr (!PINGPONG) {
-            if constexpr (!kEarlyV) read_v();
-            if (!(MHA_ABL & ABL_NO_REFILL) && may_write) write(st_fill, wr);
-        }
+        // phase B: Oᵀ += Vᵀ·Pᵀ (it) and the row sums on the matrix pipe ‖ row max (it+1) and the
+        // LDS refill of super-tile it+NSTAGE-1 (its stage held tile it-1).
+        if constexpr (!kEarlyV) read_v();
+        if (may_write) write(st_fill, wr);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int ss = 0; ss < 2; ++ss)
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
-                    if (MHA_ABL & ABL_NO_PV) {
-                        keep_live(vfa[j][ss]);
-                        keep_live(vfb[j][ss]);
-                        keep_live(p[rb][j][ss]);
-                    } else {
-                        o0[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfa[j][ss], p[rb][j][ss], o0[rb], 0, 0, 0);
-                        o1[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfb[j][ss], p[rb][j][ss], o1[rb], 0, 0, 0);
-                    }
-                    if (!(MHA_ABL & ABL_NO_SOFTMAX))
-                        l_acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_sum, p[rb][j][ss], l_acc[rb], 0, 0, 0);
+                    o0[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfa[j][ss], p[rb][j][ss], o0[rb], 0, 0, 0);
+                    o1[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfb[j][ss], p[rb][j][ss], o1[rb], 0, 0, 0);
+                    l_acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_sum, p[rb][j][ss], l_acc[rb], 0, 0, 0);
                 }
         if constexpr (HAS_NEXT) {
 #pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                if (MHA_ABL & ABL_NO_SOFTMAX) mxn[rb] = 0.f;
-                else mxn[rb] = xhalf_max(tree_max(n0[rb], n1[rb]));
-            }
+            for (int rb = 0; rb < RB; ++rb) mxn[rb] = xhalf_max(tree_max(n0[rb], n1[rb]));
         }
 
         TCLK(ck[2]);
@@ -465,7 +410,7 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
             ck_sum[3] += 1;
         }
 #endif
-        if (!(MHA_ABL & ABL_NO_BARRIER)) __syncthreads();
+        __syncthreads();
         TCLK(ck[3]);
 #ifdef MHA_STEPSTAMPS
         if (HAS_NEXT) {
@@ -494,34 +439,19 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
         if (n_iter > 0) step(0, sA0, sA1, mxA, sB0, sB1, mxB, F_{}, false, stgA, stgA, false, false);
     } else {
     if (n_iter > 1) write(1, stgB);
-    if constexpr (NSTAGE == 4) {
-        if (n_iter > 3) issue(3, stgB);
-        if (n_iter > 2) write(2, stgA);
-    }
     if (n_iter > 1) __syncthreads();
-    // The set the first step writes from (super-tile NSTAGE-1) and the one it issues into.
-    Raw8<TIn>(&stg0)[NLOAD] = NSTAGE == 4 ? stgB : stgA;
-    Raw8<TIn>(&stg1)[NLOAD] = NSTAGE == 4 ? stgA : stgB;
-#ifndef MHA_PRIO
-#define MHA_PRIO 0
-#endif
-    // (static priority for the second-dispatched half of an 8-wave workgroup: diagnostic switch)
-    if (MHA_PRIO && NT == 512 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-    // Ping-pong offset: the second half starts one phase late (one extra barrier before the loop,
-    // matched by one extra barrier of the first half after it).
-    const bool late_half = PINGPONG && wave >= 4;
-    if (late_half) __syncthreads();
+    // The first step writes super-tile NSTAGE-1 from stgA and issues into stgB.
     int it = 0;
     // Steady state: tiles it+1 and it+2 exist and neither is the (possibly partial) last one.
     // Refill issue / write are unconditional here (see step).
     for (; it + 3 < n_iter; it += 2) {
-        step(it, sA0, sA1, mxA, sB0, sB1, mxB, T_{}, false, stg0, stg1, true, true);
-        step(it + 1, sB0, sB1, mxB, sA0, sA1, mxA, T_{}, false, stg1, stg0, true, true);
+        step(it, sA0, sA1, mxA, sB0, sB1, mxB, T_{}, false, stgA, stgB, true, true);
+        step(it + 1, sB0, sB1, mxB, sA0, sA1, mxA, T_{}, false, stgB, stgA, true, true);
     }
     // Tail (at most 3 iterations): same step with the mask flag live; scores and the pending
     // staging set move back after each step.
     for (; it + 1 < n_iter; ++it) {
-        step(it, sA0, sA1, mxA, sB0, sB1, mxB, T_{}, tail && (it + 2 == n_iter), stg0, stg1, it + NSTAGE < n_iter,
+        step(it, sA0, sA1, mxA, sB0, sB1, mxB, T_{}, tail && (it + 2 == n_iter), stgA, stgB, it + NSTAGE < n_iter,
              it + NSTAGE - 1 < n_iter);
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -530,10 +460,9 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
             mxA[rb] = mxB[rb];
         }
 #pragma unroll
-        for (int i = 0; i < NLOAD; ++i) stg0[i] = stg1[i];
+        for (int i = 0; i < NLOAD; ++i) stgA[i] = stgB[i];
     }
-    if (it < n_iter) step(it, sA0, sA1, mxA, sB0, sB1, mxB, F_{}, false, stg0, stg1, false, false);
-    if (PINGPONG && !late_half) __syncthreads();
+    if (it < n_iter) step(it, sA0, sA1, mxA, sB0, sB1, mxB, F_{}, false, stgA, stgB, false, false);
     }  // NSTAGE > 1
     STAMP(2);
 
@@ -570,7 +499,7 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
     STAMP(3);
 
     // Thread -> (row, chunk of 8 dims); 8 threads per row, NT/8 rows per pass. Stores are 16-B
-    // buffer stores through per-head descriptors (cache policy MHA_ST_AUX / MHA_PART_AUX).
+    // buffer stores through per-head descriptors.
     const int q_base = qtile * BLOCK_M;
     const __amdgpu_buffer_rsrc_t o_rs =
         make_rsrc(reinterpret_cast<TOut*>(ca.o) + (size_t)bh * nq * kHeadDim, (unsigned)(nq * kHeadDim * sizeof(TOut)));
@@ -625,11 +554,10 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
         float M, L;
         f32x4 acc0, acc1;
         merge_waves(row, c, M, L, acc0, acc1);
-        if (q < nq && !(MHA_ABL & ABL_NO_STORE)) {
+        if (q < nq) {
             if (ca.splits == 1) {
                 const float inv = 1.f / L;
-                store_dims<TOut, DPT, MHA_ST_AUX>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)), acc0 * inv,
-                                                  acc1 * inv);
+                store_dims<TOut, DPT, 0>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)), acc0 * inv, acc1 * inv);
             } else {
                 // Partial O_s / l_s in the output precision (fp16 halves the partial traffic of
                 // the fp16 path; the fp32-output path keeps fp32), merged with weights l_s·2^(m_s-M).
@@ -642,7 +570,7 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(M, L)), pml_rs,
                                                               prow * (unsigned)sizeof(float2), 0, kSC1);
                 } else {
-                    store_dims<TOut, DPT, MHA_PART_AUX>(po_rs, poff, acc0 * inv, acc1 * inv);
+                    store_dims<TOut, DPT, 0>(po_rs, poff, acc0 * inv, acc1 * inv);
                     if (chunk == 0) ca.part_ml[((size_t)bh * ca.splits) * nq + prow] = make_float2(M, L);
                 }
             }
@@ -706,9 +634,8 @@ __global__ __launch_bounds__(64 * QW * KW, 1) void mha_hd64_fwd_kernel(FwdArgs a
                     }
                 }
                 const float inv = 1.f / L;
-                if (!(MHA_ABL & ABL_NO_STORE))
-                    store_dims<TOut, DPT, MHA_ST_AUX>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)),
-                                                      split_scale(acc0, inv), split_scale(acc1, inv));
+                store_dims<TOut, DPT, 0>(o_rs, (unsigned)((q * kHeadDim + c) * sizeof(TOut)), split_scale(acc0, inv),
+                                         split_scale(acc1, inv));
             }
         }
     }

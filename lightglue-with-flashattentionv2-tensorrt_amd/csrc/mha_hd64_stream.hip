@@ -194,23 +194,14 @@ __device__ __forceinline__ StreamItem stream_item(const FwdArgs& a, int j, bool 
     const int nq = MHA_SEL(nq), nkv = MHA_SEL(nkv), qtiles = MHA_SEL(qtiles);
     const int jl = j - MHA_SEL(block_begin);
     const int bh = jl / qtiles, qtile = jl - bh * qtiles;
-#ifdef MHA_STREAM_L2Q  // diagnostic: every item reads the first query block (L2-resident)
-    const int bhq = 0;
-#else
-    const int bhq = bh;
-#endif
-    const char* q = reinterpret_cast<const char*>(MHA_SEL(q)) + (size_t)bhq * nq * (kHeadDim * 2);
+    const char* q = reinterpret_cast<const char*>(MHA_SEL(q)) + (size_t)bh * nq * (kHeadDim * 2);
     char* o = reinterpret_cast<char*>(MHA_SEL(o)) + (size_t)bh * nq * (kHeadDim * OSZ);
     StreamItem it;
     // (a dead item — past the workgroup's last — gets an empty Q descriptor: its DMA reads zeros)
     it.q = stream_rsrc(q, live ? (unsigned)nq * kHeadDim * 2 : 0u);
     it.o = stream_rsrc(o, (unsigned)nq * kHeadDim * OSZ);
     it.nkv = nkv;
-#ifdef MHA_STREAM_L2Q
-    it.q0 = 0;
-#else
     it.q0 = qtile * stream_rows<NW>();
-#endif
     it.nt = stream_tiles(nkv);
     return it;
 }
@@ -247,13 +238,8 @@ __device__ __forceinline__ StreamLoader stream_kv(const FwdArgs& a, int j, bool 
     const int nkv = MHA_SEL(nkv), qtiles = MHA_SEL(qtiles);
     const int bh = (j - MHA_SEL(block_begin)) / qtiles;
     const int len = LENS ? stream_clamp(len_raw, nkv) : nkv;
-#ifdef MHA_STREAM_L2KV  // diagnostic: every item streams the first head's K/V (L2-resident)
-    const int bhk = 0;
-#else
-    const int bhk = bh;
-#endif
-    const char* k = reinterpret_cast<const char*>(MHA_SEL(k)) + (size_t)bhk * nkv * (kHeadDim * 2);
-    const char* v = reinterpret_cast<const char*>(MHA_SEL(v)) + (size_t)bhk * nkv * (kHeadDim * 2);
+    const char* k = reinterpret_cast<const char*>(MHA_SEL(k)) + (size_t)bh * nkv * (kHeadDim * 2);
+    const char* v = reinterpret_cast<const char*>(MHA_SEL(v)) + (size_t)bh * nkv * (kHeadDim * 2);
     StreamLoader ld;
     // (past the workgroup's last item: empty descriptors, zeros into the ring, forever)
     const unsigned kvb = live ? (unsigned)len * kHeadDim * 2 : 0u;
@@ -307,24 +293,9 @@ struct StreamScores {
     bool rs;        // some query of the wave exceeds the running max by > kRescaleThr (wave-uniform)
 };
 
-// Speculative running max (-DMHA_STREAM_SPEC=1: an A/B build, not shipped): an item's running max is
-// its tile 0's and never moves, so the middle and tail steps carry no row max of the next tile, no
-// rescale decision and no rescale (≈ 20 of the step's ≈ 44 non-exponential vector instructions).
-// Exact while no later score exceeds it by 2^16 (the fp16 P would overflow; below that fp16's
-// relative precision does not depend on magnitude and the row sums and O accumulate in fp32). An
-// overflow makes the row sum +Inf (NaN keys, or the partner row of the row-sum MFMA: NaN), which the
-// epilogue sees: the item is marked, and at the end of the kernel the wave recomputes its rows of
-// every marked item with an exact online softmax (exact_item below) through its own ring slot.
-// Round 6 measurements (profiles/r06/stream_spec_*.jsonl, lazy -> spec): random inputs 32 calls
-// 44.0 -> 41.3 us (tools/spec_rare_cost.py), but bench.py's 32 / 64-call lines 41.4 -> 41.2 and
-// 76.1 -> 75.4 us only; one spike key per head 44.3 -> 70.1 us (gain 3) and 45.0 -> 94.9 (gain 6:
-// secondary overflows mark nearly every item); and the seeded matcher's batched forwards, whose
-// attention rows do overflow (tools/matcher_nan_probe.py), 1.278 -> 1.361 ms at P = 8, 2.333 ->
-// 2.553 at P = 16. A re-run costs a whole item, so no rare path makes a marked fraction f cheaper
-// than ≈ 1 + 1.3 f; the lazy form below stays the default.
-#ifndef MHA_STREAM_SPEC
-#define MHA_STREAM_SPEC 0
-#endif
+// (Tried and dropped: a speculative running max, tile 0's kept for the whole item, with an exact
+// re-run of the items whose fp16 P overflowed; 32 random calls 44.0 -> 41.3 us, but the seeded
+// matcher's batched forwards 1.278 -> 1.361 ms at P = 8; profiles/r06/stream_spec_*.jsonl.)
 
 // LENS: per-item key counts from a.lens (a form of its own: the instantiations without it compile
 // to the instruction streams they had before it existed).
@@ -504,22 +475,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
             vfb[jj][ss] = cat8(tr_read(lds, v_addr1 + rowc), tr_read(lds, v_addr1 + rowc + 8 * 128));
         }
     };
-    // SPEC: the items (ordinal k of this workgroup's walk, bit min(k, 63)) with a row sum that
-    // overflowed (or a NaN key), recomputed exactly at the end
-    unsigned long long dirty = 0;
     // O = Oᵀ / l of an item (rows past nq: dropped by the descriptor)
-    auto epilogue = [&](__amdgpu_buffer_rsrc_t o_rs, int q0, unsigned qbad_it, int ord) {
-        if constexpr (MHA_STREAM_SPEC) {
-            // the bits behind an empty asm (-fno-honor-nans folds a float class test). Not an asm
-            // v_mov: the flush's epilogue follows the last row-sum MFMA directly, and the hazard
-            // recognizer puts no wait states before an instruction inside inline asm — such a move
-            // read the register before the MFMA had written it (an overflow missed, its rows left
-            // NaN; tools/check_mfma_hazards.py audits the library for it)
-            unsigned lb = __builtin_bit_cast(unsigned, l_acc[0]);
-            asm volatile("" : "+v"(lb));
-            const bool over = (lb & 0x7f800000u) == 0x7f800000u && !((qbad_it >> r) & 1u);
-            if (__builtin_amdgcn_ballot_w64(over) != 0) dirty |= 1ull << (ord < 63 ? ord : 63);
-        }
+    auto epilogue = [&](__amdgpu_buffer_rsrc_t o_rs, int q0, unsigned qbad_it) {
         const float inv = inv_or_nan(l_acc[0], qbad_it, r);  // a non-finite query row: NaN
         const unsigned row = (unsigned)(q0 + 32 * wave + r);
         if constexpr (OSZ == 2) {
@@ -543,8 +500,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
                     rk[k + 1][w] = sw[1];
                 }
                 const u32x4 v = u32x4{rk[k][0], rk[k][1], rk[k + 1][0], rk[k + 1][1]};
-                __builtin_amdgcn_raw_buffer_store_b128(v, o_rs, row * 128u + (unsigned)(8 * k + 8 * hh) * 2u, 0,
-                                                       MHA_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(v, o_rs, row * 128u + (unsigned)(8 * k + 8 * hh) * 2u, 0, 0);
             }
         } else {
 #pragma unroll
@@ -553,7 +509,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
                 const int b = 4 * (k & 3);
                 const f32x4 v = f32x4{o[b] * inv, o[b + 1] * inv, o[b + 2] * inv, o[b + 3] * inv};
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rs,
-                                                       row * 256u + (unsigned)(8 * k + 4 * hh) * 4u, 0, MHA_ST_AUX);
+                                                       row * 256u + (unsigned)(8 * k + 4 * hh) * 4u, 0, 0);
             }
         }
     };
@@ -563,7 +519,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
     __amdgpu_buffer_rsrc_t prv_o = cur.o;
     int prv_q0 = 0;
     unsigned qbad_prv = 0;
-    int item_no = 0, prv_no = 0;  // ordinal of the current / previous item in this workgroup's walk
 
     // One step of the current item — every step is a full step of the pipeline: tile t's
     // exponentials; QKᵀ of global tile g + 1 (LAST: the next item's tile 0, with the next item's Q
@@ -586,16 +541,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         constexpr bool LAST = KIND == 3;
         constexpr bool MASK = KIND != 1 && KIND != 4;  // tile t + 1 may hold keys past nkv
         constexpr bool BAR = NW == 4 || KIND == 1 || KIND == 2 || KIND == 3;  // (NW 8: odd t)
-        // the row max of tile t + 1: every step of the lazy-rescale form; SPEC: the LAST step only
-        // (the next item's tile 0 sets its running max)
-        constexpr bool NEEDMAX = !MHA_STREAM_SPEC || LAST;
         const unsigned g = gb + (unsigned)t;
-#ifdef MHA_STREAM_PRIO_BAL
-        // NW 8, between two barriers: the first step at raised priority, the second at normal, so
-        // the wave of a SIMD pair that finishes its first step ahead (the older one, on age) yields
-        // the issue to the other until it catches up (experiment)
-        if constexpr (NW == 8) __builtin_amdgcn_s_setprio(BAR ? 0 : 1);
-#endif
         const unsigned kbase = ((g + 1u) & kSM) * (unsigned)kSSlot;  // K of tile t + 1
         const unsigned vbase = ((g - 1u) & kSM) * (unsigned)kSSlot;  // V of tile t − 1
         // FIRST: tile 0's scores came from a C = 0 chain (the previous item's last step, or the
@@ -615,7 +561,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         // online-softmax decision for tile t (rare): the max moves now for tiles t, t + 1, ...;
         // O and l follow after tile t − 1's P·V (at the old max) is in
         float alpha = 1.f;
-        const bool rescale = !MHA_STREAM_SPEC && !FIRST && c.rs;
+        const bool rescale = !FIRST && c.rs;
         if (rescale) {
             asm volatile("" ::: "memory");  // (a real branch)
             const float d = fmaxf(c.mx, 0.f);
@@ -671,7 +617,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         auto fill = [&](int gi) {
             if (gi < 16) exp_pair(gi);
             if (gi >= 4 && gi < 20) cvt(gi - 4);
-            if (NEEDMAX && gi >= 14 && gi < 18) maxk(gi - 14);
+            if (gi >= 14 && gi < 18) maxk(gi - 14);
         };
 
         constexpr int SB = KIND == 0 ? 2 : (KIND == 1 || KIND == 4) ? 6 : KIND == 3 ? 16 : 10;  // (stamps)
@@ -731,11 +677,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
             if (lim < kTileKV) {  // (wave-uniform, rare: a partial or padding tile)
                 asm volatile("" ::: "memory");
                 mask_tile(n, lim);
-                if constexpr (NEEDMAX) mt[0] = mt[1] = mt[2] = mt[3] = tree_max(n.s0, n.s1);
+                mt[0] = mt[1] = mt[2] = mt[3] = tree_max(n.s0, n.s1);
             }
         }
-        if constexpr (NEEDMAX) n.mx = xhalf_max(fmaxf(max3f(mt[0], mt[1], mt[2]), mt[3]));
-        if constexpr (!LAST && !MHA_STREAM_SPEC) n.rs = __builtin_amdgcn_ballot_w64(n.mx > kRescaleThr) != 0;
+        n.mx = xhalf_max(fmaxf(max3f(mt[0], mt[1], mt[2]), mt[3]));
+        if constexpr (!LAST) n.rs = __builtin_amdgcn_ballot_w64(n.mx > kRescaleThr) != 0;
         if (rescale) {  // tile t − 1's P·V went in at the old max: O and l follow the new one
             asm volatile("" ::: "memory");
             o0 *= alpha;
@@ -743,7 +689,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
             l_acc *= alpha;
         }
         if constexpr (FIRST) {  // the previous item is complete: its output, then a fresh O and l
-            if (prev) epilogue(prv_o, prv_q0, qbad_prv, prv_no);
+            if (prev) epilogue(prv_o, prv_q0, qbad_prv);
             o0 = f32x16{};
             o1 = f32x16{};
             l_acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -865,7 +811,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
         prv_o = cur.o;
         prv_q0 = cur.q0;
         qbad_prv = qbad;
-        prv_no = item_no++;
         prev = true;
         // ---- next item ----
         j += G;
@@ -881,89 +826,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
             nxtL = stream_lens<MULTI>(a, more ? j + G : j);
         }
     }
-    // SPEC's rare path: this wave's 32 rows of item jj, exactly — a running max per 64-key tile (exact
-    // online softmax, rescale at every move) on the step's MFMA forms and fragment reads. Runs after
-    // the workgroup's last barrier, when the ring is idle: the wave streams each K / V tile by LDS-DMA
-    // into ring slot `wave` (its own: 16 KiB, the main loop's image layout and swizzles) and reads
-    // the fragments as the steps do (read_k, read_v: ds_read_b128 / ds_read_b64_tr_b16); the next
-    // tile's DMA is issued once the current one's fragments are in registers, so it lands under the
-    // current tile's arithmetic. (Round 5's form loaded K fragments with 16-B and Vᵀ with 2-byte
-    // global loads, one item ~90 us; profiles/r05/stream_spec_rare_cost.jsonl.)
-    const unsigned xs_base = (unsigned)wave * (unsigned)kSSlot;
-    const unsigned xs_m0 = (unsigned)__builtin_amdgcn_readfirstlane(lds0 + xs_base);
-    auto exact_item = [&](int jj) {
-        StreamItem it = stream_item<MULTI, OSZ, NW>(a, jj, true);
-        StreamLens itL = {};
-        if constexpr (LENS) {
-            itL = stream_lens<MULTI>(a, jj);
-            stream_settle(it, itL);
-        }
-        const StreamLoader kv = stream_kv<MULTI, LENS>(a, jj, true, it.nkv);
-        auto load_tile = [&](int t) {  // pieces p = rows 8p..8p+7 of K and V (swizzles as issue_tile)
-            const unsigned so = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(t * kTileBytes));
-#pragma unroll
-            for (int pc = 0; pc < 8; ++pc) {
-                lds_dma16(xs_m0 + (unsigned)(pc * 1024), dma_kq(pc & 1), kv.k, so + (unsigned)(pc * 1024));
-                lds_dma16(xs_m0 + (unsigned)(kTileBytes + pc * 1024), dma_v, kv.v, so + (unsigned)(pc * 1024));
-            }
-        };
-        load_tile(0);
-        const unsigned qrow = (unsigned)(it.q0 + 32 * wave + r);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            qf[s] = stream_scale_q(__builtin_bit_cast(
-                f16x8, __builtin_amdgcn_raw_buffer_load_b128(it.q, qrow * 128u + (unsigned)(2 * s + hh) * 16u, 0, 0)));
-        const unsigned qb = stream_pad_q<LENS>(qf, q_nonfinite_fix(qf), LENS ? itL.qlen - (it.q0 + 32 * wave) : 32);
-        float m = -INFINITY, l = 0.f;
-        o0 = f32x16{};
-        o1 = f32x16{};
-        const int ntl = (it.nkv + kTileKV - 1) / kTileKV;
-        for (int t = 0; t < ntl; ++t) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile t landed (this wave's own DMA)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) read_k(xs_base, s);
-            read_v(xs_base, 0);
-            read_v(xs_base, 1);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments in registers: the slot is free
-            if (t + 1 < ntl) load_tile(t + 1);
-            const unsigned kt = (unsigned)(t * kTileKV);
-            StreamScores sc;
-            const f32x16 zero = {};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                sc.s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[2 * s], qf[s], s == 0 ? zero : sc.s0, 0, 0, 0);
-                sc.s1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[2 * s + 1], qf[s], s == 0 ? zero : sc.s1, 0, 0, 0);
-            }
-            if (it.nkv - (int)kt < kTileKV) mask_tile(sc, it.nkv - (int)kt);
-            const float mn = fmaxf(m, xhalf_max(tree_max(sc.s0, sc.s1)));
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);  // (the first tile: exp2(-Inf) = 0)
-            m = mn;
-            float ls = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                sc.s0[i] = __builtin_amdgcn_exp2f(sc.s0[i] - m);
-                sc.s1[i] = __builtin_amdgcn_exp2f(sc.s1[i] - m);
-                ls += sc.s0[i] + sc.s1[i];
-            }
-            const auto lsw = __builtin_amdgcn_permlane32_swap(__float_as_uint(ls), __float_as_uint(ls), false, false);
-            l = l * alpha + (__uint_as_float(lsw[0]) + __uint_as_float(lsw[1]));  // (own half + the other)
-            o0 *= alpha;
-            o1 *= alpha;
-#pragma unroll
-            for (int pj = 0; pj < 2; ++pj)
-#pragma unroll
-                for (int ps = 0; ps < 2; ++ps) {
-                    const f32x16& x = pj ? sc.s1 : sc.s0;
-                    f16x8 pk;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) pk[e] = (f16)x[8 * ps + e];
-                    o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfa[pj][ps], pk, o0, 0, 0, 0);
-                    o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfb[pj][ps], pk, o1, 0, 0, 0);
-                }
-        }
-        l_acc = f32x4{l, l, l, l};
-        epilogue(it.o, it.q0, qb, 63);
-    };
     // flush: the last item's last tile (P in pB, V in its slot: no refill has reached it)
     {
         const unsigned vb_t = ((gb + (unsigned)cur.nt - 1u) & kSM) * (unsigned)kSSlot;
@@ -976,28 +838,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void mha_hd64_stream_kern
             o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfb[jj][ss], pB[jj][ss], o1, 0, 0, 0);
             l_acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_sum, pB[jj][ss], l_acc, 0, 0, 0);
         }
-        epilogue(prv_o, prv_q0, qbad_prv, prv_no);
+        epilogue(prv_o, prv_q0, qbad_prv);
     }
     // drain: the loader's trailing (empty) pieces and the output stores
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (MHA_STREAM_SPEC) {
-        // every wave is done with the ring (its flush read the last V image): slot w is wave w's
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-#ifdef MHA_STREAM_RARE_ALL  // diagnostic: every item down the rare path
-        dirty = ~0ull;
-#endif
-#ifdef MHA_STREAM_RARE_NONE  // diagnostic: the speculative output as it is
-        dirty = 0;
-#endif
-        if (dirty) {  // (wave-uniform, rare) the exact rows of the marked items, over their stores
-            asm volatile("" ::: "memory");
-            const int j_first = jb + loc;
-            for (int k = 0; j_first + k * G < je; ++k)
-                if ((dirty >> (k < 63 ? k : 63)) & 1ull) exact_item(j_first + k * G);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
 #ifdef MHA_STREAM_STAMPS
     unsigned long long ck_exit[2];
     asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(ck_exit[0]), "=s"(ck_exit[1])::"memory");

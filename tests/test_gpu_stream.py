@@ -128,15 +128,15 @@ def test_stream_kernel_running_max_moves(waves, dev, oracle_mod):
 @pytest.mark.parametrize("waves", [4, 8])
 @pytest.mark.parametrize("nkv", [200, 1100, 2048])
 def test_stream_kernel_every_item_recomputed(nkv, waves, dev, oracle_mod):
-    """The speculative running max's rare path on every item: each 128-row block of every head has
-    one query row whose spike key (gain 8, past tile 0) beats tile 0's max by far more than 2^16, so
-    every item's row sum overflows, every item is marked and every wave re-runs its rows of all of
-    them through its own ring slot after the workgroup's last barrier (csrc/mha_hd64_stream.hip,
-    exact_item). nkv 200 and 1100: a partial last tile; batch 40: 2-3 items per workgroup,
-    so the re-runs follow each other through the same slot. Every row of three heads is checked.
-    Both output types take the 1e-2 contract: on these peaked rows fp16 P's rounding alone puts the
-    fp32 output 6.1e-3 from the fp64 oracle, in the lazy-rescale form (no rare path) as in this one
-    (profiles/r06/stream_rare_path_errors.jsonl, tools/rare_path_errors.py)."""
+    """The running max moves far on every item: each 128-row block of every head has one query row
+    whose spike key (gain 8, past tile 0) beats tile 0's max by far more than 2^16, so every item's
+    lazy rescale fires at that tile and O and the row sums of all 32 rows of the wave follow the new
+    max (csrc/mha_hd64_stream.hip, `rescale` in the step). nkv 200 and 1100: a partial last tile;
+    batch 40: 2-3 items per workgroup, so the moves fall next to item seams too. Every row of three
+    heads is checked. Both output types take the 1e-2 contract: on these peaked rows fp16 P's
+    rounding alone puts the fp32 output 6.1e-3 from the fp64 oracle
+    (profiles/r06/stream_rare_path_errors.jsonl). The test was written for a speculative-max form of
+    the kernel that re-ran such items exactly; that form never shipped and is gone, the input stays."""
     from lightglue_amd import _lib, synth
 
     lib = _lib.load()
@@ -162,10 +162,11 @@ def test_stream_kernel_every_item_recomputed(nkv, waves, dev, oracle_mod):
 def test_stream_kernel_matcher_overflow_head(waves, dev, oracle_mod):
     """A head of the seeded fp16 matcher (P = 8 pairs, n = 1024; the layer-7 self-attention launch,
     tools/matcher_nan_probe.py) whose rows 131, 361 and 816 beat their tile-0 max by just past 2^16:
-    the speculative max overflows there and, through the row-sum MFMA, in the partner rows 147, 377
-    and 800. The overflow of an item whose epilogue is the flush's (the workgroup's last item) was
-    missed until round 6: the check read the row sums with an inline-asm move that the compiler gave
-    no MFMA wait states. Every row against the fp64 oracle (tests/golden/stream_spec_overflow_head.npz)."""
+    without a rescale their fp16 P would overflow and, through the row-sum MFMA, poison the partner
+    rows 147, 377 and 800; the shipped kernel's lazy rescale must move the max there, also in the
+    workgroup's last item, whose epilogue is the flush's. (The head was recorded when a
+    speculative-max form, since removed, missed exactly that overflow until round 6.) Every row
+    against the fp64 oracle (tests/golden/stream_spec_overflow_head.npz)."""
     import os
 
     from conftest import REPO

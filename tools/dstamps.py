@@ -1,5 +1,6 @@
 """Diagnostic: phase timestamps of the single-pass kernels from a -DMHA_STAMPS build
-(tools/build_direct_variant.sh stamps -DMHA_STAMPS; tools/build_direct16_variant.sh for plan 22).
+(make -C lightglue-with-flashattentionv2-tensorrt_amd variant SRC='mha_hd64_direct mha_hd64_direct16 mha_hd64_plugin'
+NAME=stamps DEFS=-DMHA_STAMPS).
     python tools/dstamps.py <lib.so> nq nkv [plan code: 21 (32-row kernel, default) | 22 (16-row)]
 Plan 21, 8 slots per workgroup (wave 0, s_memtime cycles): 0 entry, 1 Q + K(0) landed, 2 scores and
 probabilities of every tile done, 3 V(0) landed, 4 PV done, 5 after the epilogue barrier,

@@ -1,7 +1,7 @@
 """Diagnostic: where ffn_rows_kernel's time goes (stamps build, -DLG_FR_STAMPS: per wave, s_memtime
 cycles of chained segments; see csrc/lightglue_ffn.hip).
 
-    SRC=ffn tools/build_linear_variant.sh frstamps -DLG_FR_STAMPS
+    make -C lightglue-with-flashattentionv2-tensorrt_amd variant SRC=lightglue_ffn NAME=frstamps DEFS=-DLG_FR_STAMPS
 
     MHA_HD64_LIB=lib/ab/libmha_hd64_frstamps.so python tools/fr_stamps.py [P=1] [n=1024] [kind=0]
 

@@ -5,7 +5,7 @@
 # steps: tests[:<pytest -k expr>]  gpu  ffn_ab[:<args>]  bench[:<args>]  smoke  prof_fwd:<P>x<n>
 #        pmc_ffn:<P>:<n>:<mode>  "tool:<tools/NAME.py> [args...]" (one quoted word)
 #        "frstamps:<P> <n> <kind>" (FFN segment stamps; build lib/ab/libmha_hd64_frstamps.so first with
-#        SRC=ffn tools/build_linear_variant.sh frstamps -DLG_FR_STAMPS)
+#        make -C lightglue-with-flashattentionv2-tensorrt_amd variant SRC=lightglue_ffn NAME=frstamps DEFS=-DLG_FR_STAMPS)
 # (the round-start check: gpu smoke "bench:--full --steps 20 --warmup 5"; round 5's 50 tools/gpu/r05_*.sh
 # sessions were each one such list of steps, folded into this script in round 6)
 set -o pipefail

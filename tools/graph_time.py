@@ -2,7 +2,7 @@
 
     python tools/graph_time.py lib1.so [lib2.so ...]
 
-For each library (the shipped one or lib/exp/ ablation / experiment builds) and each case, K
+For each library (the shipped one or `make variant` builds under lib/ab/) and each case, K
 launches are captured back to back into one graph (stream-ordered, as bench.py does) and the
 graph is replayed; time per launch = replay time / K. Cases: the single 1x4x1024x1024 call
 (main kernel only, and main + combine) with the planned shape, and a batched launch. Also

@@ -1,7 +1,7 @@
 """Diagnostic: the first attention launch of the seeded fp16 matcher (P pairs stacked, n = 1024) whose
 output holds a non-finite value: which layer / call, whether its inputs are finite, which rows are
-bad, those rows' score move past tile 0's max (log2 units; > 16 overflows the speculative max's
-fp16 P), and whether the same call launched alone through the streaming kernel (forced plan 23,
+bad, those rows' score move past tile 0's max (log2 units; > 16 would overflow an fp16 P
+whose max stayed at tile 0's), and whether the same call launched alone through the streaming kernel (forced plan 23,
 both kv_waves, non-grouped) reproduces it, also for the failing head alone (whose q, k, v it saves
 under gpurun_out/nan_probe/ as .npy). Prints JSON lines.
 

@@ -1,5 +1,6 @@
 """Diagnostic: where a step of the persistent streaming kernel spends its cycles, from a
--DMHA_STREAM_STAMPS build (tools/build_stream_variant.sh stamps -DMHA_STREAM_STAMPS).
+-DMHA_STREAM_STAMPS build (make -C lightglue-with-flashattentionv2-tensorrt_amd variant SRC=mha_hd64_stream NAME=stamps
+DEFS=-DMHA_STREAM_STAMPS).
     [STREAM_WAVES=8] python tools/stream_stamps.py <lib.so> [batch] [nq] [nkv]
 Per wave: s_memtime cycles per step by segment (refill issue, decision/seam, phase A issue,
 phase B issue, DMA wait, barrier), medians and p90 over waves, steps per wave, the in-kernel clock
