@@ -374,6 +374,60 @@ int32_t lg_sp_conv3x3(const void* in, const void* w_packed, const void* bias, in
 int32_t lg_sp_heads(const void* in, const void* w_packed, const void* bias, int32_t hc, int32_t wc, int32_t batch,
                     void* logits, void* dense, hipStream_t stream);
 
+/* ---- image input (csrc/lightglue_image.hip) ----
+ * What the reference does on the host before its network sees a frame (demo/demo_mono.cpp:151-152, 232-233:
+ * resize to 640 x 480 with INTER_LINEAR, / 255; lightglue_pytorch_no_plugin/utils.py:30-76: resize, grey) and
+ * after it (utils.py:94-97: keypoints back to the source image): uint8 images of any size, channel count and
+ * strides -> the encoder's input [batch, ht, wt] (contiguous, grey, in [0, 1], fp16 or fp32) in one launch, and
+ * lg_kp_describe's pixel keypoints -> source pixels. New symbols only: LG_GLUE_ABI_VERSION stays 4. Every call
+ * checks its arguments before any device call, runs on `stream`, is a no-op for batch == 0, keeps no state,
+ * uses no atomics and clamps every index it forms; no workgroup reads what another wrote.
+ *
+ * A source image: element (y, x, c) is the byte at data + y stride_y + x stride_x + c stride_c (strides in bytes,
+ * >= 0: HWC, CHW and cropped views are read in place); h, w in [1, 16384]; channels 1 (grey, used as it is), 3
+ * or 4 (the fourth is ignored); bgr != 0: channel 0 is blue. grey = 0.299 R + 0.587 G + 0.114 B (utils.py:72-76).
+ *
+ * Resampling: out = Wy · grey · Wxᵀ / 255, the rule chosen per axis (shown for x, source w, target wt):
+ *   LG_IMG_LINEAR: output column o sits at source position ((2 o + 1) w - wt) / (2 wt) = i + f (i its floor):
+ *                  weights 1 - f and f on columns i and i + 1, both clamped into [0, w - 1] (INTER_LINEAR's and
+ *                  F.interpolate(bilinear, align_corners=False)'s convention);
+ *   LG_IMG_AREA:   where w > wt, output o covers [o w / wt, (o + 1) w / wt) and column i weighs its overlap with
+ *                  that interval divided by w / wt (INTER_AREA); on an axis that does not shrink, LG_IMG_LINEAR.
+ * Positions and overlaps are exact integer rationals, each weight one fp32 division; sums in fp32, one rounding
+ * to the output type. The result is the unrounded float (INTER_LINEAR's fixed-point rounding to uint8 is not
+ * reproduced). */
+typedef struct lg_img_src {
+    const void* data;
+    int32_t h, w;
+    int32_t channels;
+    int32_t bgr;
+    int64_t stride_y, stride_x, stride_c;
+} lg_img_src;
+#define LG_IMG_LINEAR 0
+#define LG_IMG_AREA 1
+/* sizeof(lg_img_src), for a host that builds the table without this header (48). */
+size_t lg_img_src_bytes(void);
+/* lg_img_prepare: table: DEVICE array of `batch` descriptors (8-B aligned), read when the kernel runs (a captured
+ * call replays on what the table and the images hold then). Its contents are the caller's contract: the kernel
+ * clamps h and w into [1, 16384] and takes a channel count other than 3 or 4 as 1, but cannot check a pointer or
+ * a stride. ht, wt in [1, 16384] (multiples of nothing); out [batch, ht, wt] of out_dtype (fp16 / fp32).
+ * batch <= 65,535. One launch: a lane per output pixel, a wave on 64 adjacent columns of one row. */
+int32_t lg_img_prepare(const lg_img_src* table, int32_t batch, int32_t ht, int32_t wt, int32_t interp, int32_t out_dtype,
+                       void* out, hipStream_t stream);
+/* lg_img_prepare_batch: the same kernel body on `batch` images of one size, image b at data + b stride_b (video
+ * frames, one [batch, ...] tensor): no table, every argument checked here (h, w in [1, 16384]; channels 1, 3 or 4;
+ * bgr 0 or 1; strides in [0, 2^40]). Bitwise lg_img_prepare's result on the same images. */
+int32_t lg_img_prepare_batch(const void* data, int32_t batch, int32_t h, int32_t w, int32_t channels, int32_t bgr,
+                             int64_t stride_b, int64_t stride_y, int64_t stride_x, int64_t stride_c, int32_t ht, int32_t wt,
+                             int32_t interp, int32_t out_dtype, void* out, hipStream_t stream);
+/* lg_kp_to_source: kpts_px [batch, k, 2] int32 (x, y) in the [ht, wt] image (lg_kp_describe's; clamped into it),
+ * counts [batch], src_sizes [batch, 2] int32 (h, w of image b's source, clamped into [1, 16384]) -> out
+ * [batch, k, 2] fp32 in source pixels: x = (2 px + 1) w / (2 wt) - 1/2, likewise y (utils.py:94-97 with scale =
+ * wt / w), the quotient and remainder of ((2 px + 1) w - wt) / (2 wt) exact (w == wt: exactly px). Rows past the
+ * count (clamped into [0, k]) are zeros. All pointers 4-B aligned; k >= 1, batch k <= 2^28. One launch. */
+int32_t lg_kp_to_source(const int32_t* kpts_px, const int32_t* counts, const int32_t* src_sizes, int32_t ht, int32_t wt,
+                        int32_t batch, int32_t k, float* out, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

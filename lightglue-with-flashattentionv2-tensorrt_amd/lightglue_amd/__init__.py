@@ -29,8 +29,24 @@ from .superpoint import (  # noqa: F401,E402
     seeded_superpoint_state_dict,
     superpoint_reference,
 )
+from .image import (  # noqa: F401,E402
+    ImageBatch,
+    ImageInput,
+    PreparedImages,
+    image_reference,
+    match_source_images,
+    resample_matrix,
+    target_size,
+)
 
 __all__ = [
+    "ImageBatch",
+    "ImageInput",
+    "PreparedImages",
+    "image_reference",
+    "match_source_images",
+    "resample_matrix",
+    "target_size",
     "Features",
     "KeypointFrontend",
     "frontend_reference",

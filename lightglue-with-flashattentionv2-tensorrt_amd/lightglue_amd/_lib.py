@@ -31,6 +31,9 @@ ADAPT_WIDTH1 = 4
 # include/lightglue_glue.h LG_SP_* (lg_sp_conv1 / lg_sp_conv3x3 flags)
 SP_RELU = 1
 SP_POOL2 = 2
+# include/lightglue_glue.h LG_IMG_* (lg_img_prepare's interpolation)
+IMG_LINEAR = 0
+IMG_AREA = 1
 
 BATCH = 1
 NUM_HEADS = 4
@@ -84,6 +87,13 @@ class CallDesc(ctypes.Structure):
     _fields_ = [("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("o", ctypes.c_void_p),
                 ("batch", ctypes.c_int32), ("heads", ctypes.c_int32), ("nq", ctypes.c_int32),
                 ("nkv", ctypes.c_int32)]
+
+
+class ImgSrc(ctypes.Structure):
+    """Mirrors lg_img_src (include/lightglue_glue.h, "image input"): one source image of lg_img_prepare's table."""
+    _fields_ = [("data", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("channels", ctypes.c_int32),
+                ("bgr", ctypes.c_int32), ("stride_y", ctypes.c_int64), ("stride_x", ctypes.c_int64),
+                ("stride_c", ctypes.c_int64)]
 
 
 # Every symbol include/mha_hd64.h declares, with its ctypes signature.
@@ -171,6 +181,12 @@ SIGNATURES.update({
     "lg_sp_conv1": ([_I, _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
     "lg_sp_conv3x3": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
     "lg_sp_heads": ([_P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
+    # image input (csrc/lightglue_image.hip)
+    "lg_img_src_bytes": ([], _S),
+    "lg_img_prepare": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "lg_img_prepare_batch": ([_P, _I, _I, _I, _I, _I, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I, _I,
+                              _I, _I, _P, _P], _I),
+    "lg_kp_to_source": ([_P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),
