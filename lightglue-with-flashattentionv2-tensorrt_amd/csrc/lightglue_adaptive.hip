@@ -291,8 +291,6 @@ __global__ __launch_bounds__(256) void matches_scatter_kernel(const ScArgs a) {
     }
 }
 
-bool aligned4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
-bool aligned2(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 1) == 0; }
 // pairs of (m + n) rows: grid y and 32-bit row counts
 bool rows_ok(int32_t m, int32_t n, int32_t pairs) {
     return m >= 1 && n >= 1 && pairs >= 0 && pairs <= 65535 && (int64_t)pairs * ((int64_t)m + n) <= (1 << 24);

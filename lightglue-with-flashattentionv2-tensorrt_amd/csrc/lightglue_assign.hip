@@ -500,7 +500,6 @@ int32_t assign_matches_run(const char* who, const void* v, int64_t pair_stride, 
                            int32_t batch, const int32_t* m_len, const int32_t* n_len, float threshold, int32_t* matches0,
                            int32_t* matches1, float* mscores0, float* mscores1, int32_t* matches, float* mscores,
                            int32_t* counts, void* workspace, hipStream_t stream) {
-    auto aligned4 = [](const void* p) { return ((uintptr_t)p & 3) == 0; };
     const bool work = m > 0 && n > 0 && batch > 0;
     if (m < 0 || n < 0 || batch < 0 || m > 2048 || n > 2048 || n % 8 != 0 || ld < 256 || ld % 8 != 0 || zc < 256 ||
         zc >= ld || pair_stride < (int64_t)(m + n) * ld || !(threshold >= 0.f) || !aligned4(counts) || !aligned4(m_len) ||

@@ -246,6 +246,15 @@ __device__ __forceinline__ void tile_issue(const TileSrc<NWP, NAP>& t, int ks, c
 constexpr int kTileGrid = 256;  // the 256-row forms: one workgroup per CU
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 bool aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; }
+bool aligned4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
+bool aligned2(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 1) == 0; }
+bool dtype_ok(int32_t dt) { return dt == MHA_HD64_DT_FLOAT || dt == MHA_HD64_DT_HALF; }
+// aligned for elements of a dtype that dtype_ok accepts
+bool aligned_as(int32_t dtype, const void* q) { return dtype == MHA_HD64_DT_HALF ? aligned2(q) : aligned4(q); }
+// batch images of h x w pixels: grid z / y and 32-bit pixel counts
+bool image_ok(int64_t h, int64_t w, int64_t batch) {
+    return h >= 1 && w >= 1 && batch >= 0 && batch <= 65535 && h * w <= (1 << 26) && h * w * (batch ? batch : 1) <= (1 << 30);
+}
 // (n: whole 64-channel tiles)
 bool shape_ok(int m, int n, int k) { return m >= 0 && n > 0 && n % 64 == 0 && (k == 256 || k == 512); }
 

@@ -396,13 +396,6 @@ SelWs sel_ws(int hw, int batch) {
     return ws;
 }
 
-bool aligned4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
-bool dtype_ok(int32_t dt) { return dt == MHA_HD64_DT_FLOAT || dt == MHA_HD64_DT_HALF; }
-// batch images of h x w pixels: grid z / y and 32-bit pixel counts
-bool image_ok(int64_t h, int64_t w, int64_t batch) {
-    return h >= 1 && w >= 1 && batch >= 0 && batch <= 65535 && h * w <= (1 << 26) && h * w * (batch ? batch : 1) <= (1 << 30);
-}
-
 }  // namespace
 
 extern "C" {
@@ -411,7 +404,7 @@ int32_t lg_kp_heatmap(int32_t dtype, const void* logits, int32_t hc, int32_t wc,
                       hipStream_t stream) {
     const char* who = "lg_kp_heatmap";
     if (!dtype_ok(dtype) || hc < 1 || wc < 1 || !image_ok((int64_t)hc * 8, (int64_t)wc * 8, batch) || !logits || !scores ||
-        !aligned16(scores) || (reinterpret_cast<uintptr_t>(logits) & (dtype == MHA_HD64_DT_HALF ? 1 : 3)))
+        !aligned16(scores) || !aligned_as(dtype, logits))
         return bad(who);
     if (batch == 0) return MHA_HD64_STATUS_SUCCESS;
     const int cells = batch * hc * wc;
@@ -477,7 +470,7 @@ int32_t lg_kp_describe(int32_t dense_dtype, const void* dense, int64_t stride_b,
         k < 1 || k > kSelMaxK || k % 8 != 0 || stride_b < 0 || stride_c < 0 || stride_y < 0 || stride_x < 0 || stride_b > lim ||
         stride_c > lim || stride_y > lim || stride_x > lim || (dense_normalized != 0 && dense_normalized != 1) || !dense ||
         !count || !pix || !desc || !kpts_px || !kpts || !aligned4(count) || !aligned4(pix) || !aligned4(kpts_px) ||
-        !aligned4(desc) || !aligned4(kpts) || (reinterpret_cast<uintptr_t>(dense) & (dense_dtype == MHA_HD64_DT_HALF ? 1 : 3)))
+        !aligned4(desc) || !aligned4(kpts) || !aligned_as(dense_dtype, dense))
         return bad(who);
     if (batch == 0) return MHA_HD64_STATUS_SUCCESS;
     DsArgs a{};

@@ -221,13 +221,11 @@ __global__ __launch_bounds__(kKpThreads) void kp_to_source_kernel(const int32_t*
     out[2 * (size_t)i + 1] = y;
 }
 
-bool aligned4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
 bool side_ok(int32_t n) { return n >= 1 && n <= kImgMaxSide; }
 // what both prepare calls share: the target, the interpolation, the output
 bool target_ok(int32_t batch, int32_t ht, int32_t wt, int32_t interp, int32_t out_dtype, const void* out) {
     return batch >= 0 && batch <= 65535 && side_ok(ht) && side_ok(wt) && (interp == LG_IMG_LINEAR || interp == LG_IMG_AREA) &&
-           (out_dtype == MHA_HD64_DT_FLOAT || out_dtype == MHA_HD64_DT_HALF) && out &&
-           (reinterpret_cast<uintptr_t>(out) & (out_dtype == MHA_HD64_DT_HALF ? 1 : 3)) == 0;
+           dtype_ok(out_dtype) && out && aligned_as(out_dtype, out);
 }
 dim3 prepare_grid(int batch, int ht, int wt) {
     return dim3((wt + kImgCols - 1) / kImgCols, (ht + kImgRows - 1) / kImgRows, batch);

@@ -305,10 +305,6 @@ __global__ __launch_bounds__(256) void sp_heads_kernel(const HeadArgs a) {
 
 bool cin_ok(int cin) { return cin == 64 || cin == 128; }
 bool cout_ok(int cout) { return cout == 64 || cout == 128 || cout == 256 || cout == 512; }
-// batch images of h x w pixels, as the keypoint front end's limits (grid z, 32-bit pixel counts)
-bool image_ok(int64_t h, int64_t w, int64_t batch) {
-    return h >= 1 && w >= 1 && batch >= 0 && batch <= 65535 && h * w <= (1 << 26) && h * w * (batch ? batch : 1) <= (1 << 30);
-}
 
 template <int CIN, int NCB>
 void launch_conv(const ConvArgs& a, int batch, hipStream_t stream) {
@@ -330,8 +326,8 @@ int32_t lg_sp_conv1(int32_t image_dtype, const void* image, const void* weight, 
                     int32_t batch, int32_t flags, void* out, hipStream_t stream) {
     const char* who = "lg_sp_conv1";
     const bool half = image_dtype == MHA_HD64_DT_HALF;
-    if ((!half && image_dtype != MHA_HD64_DT_FLOAT) || !image_ok(h, w, batch) || (flags & ~LG_SP_RELU) || !image || !weight ||
-        !bias || !out || (reinterpret_cast<uintptr_t>(image) & (half ? 1 : 3)) || !aligned16(weight) || !aligned16(bias) || !aligned16(out) || image == out)
+    if (!dtype_ok(image_dtype) || !image_ok(h, w, batch) || (flags & ~LG_SP_RELU) || !image || !weight || !bias || !out ||
+        !aligned_as(image_dtype, image) || !aligned16(weight) || !aligned16(bias) || !aligned16(out) || image == out)
         return bad(who);
     if (batch == 0) return MHA_HD64_STATUS_SUCCESS;
     const int runs = (w + 3) / 4;
@@ -376,7 +372,7 @@ int32_t lg_sp_heads(const void* in, const void* w_packed, const void* bias, int3
                     void* logits, void* dense, hipStream_t stream) {
     const char* who = "lg_sp_heads";
     if (hc < 1 || wc < 1 || !image_ok((int64_t)hc * 8, (int64_t)wc * 8, batch) || !in || !w_packed || !bias || !logits || !dense ||
-        !aligned16(in) || !aligned16(w_packed) || !aligned8(bias) || (reinterpret_cast<uintptr_t>(logits) & 1) ||
+        !aligned16(in) || !aligned16(w_packed) || !aligned8(bias) || !aligned2(logits) ||
         !aligned8(dense) || in == dense || in == logits || logits == dense)
         return bad(who);
     if (batch == 0) return MHA_HD64_STATUS_SUCCESS;

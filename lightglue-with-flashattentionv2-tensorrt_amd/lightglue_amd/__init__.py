@@ -25,6 +25,7 @@ from .matcher import (  # noqa: F401,E402
 from .frontend import Features, KeypointFrontend, frontend_reference  # noqa: F401,E402
 from .superpoint import (  # noqa: F401,E402
     SuperPointEncoder,
+    extract_pairs,
     match_images,
     seeded_superpoint_state_dict,
     superpoint_reference,
@@ -51,6 +52,7 @@ __all__ = [
     "KeypointFrontend",
     "frontend_reference",
     "SuperPointEncoder",
+    "extract_pairs",
     "match_images",
     "seeded_superpoint_state_dict",
     "superpoint_reference",

@@ -22,9 +22,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .plugin import PluginError, _check, _workspace
+from ._host import DT, _workspace, call, carve, require_gpu, stream_of
 
-_DT = {torch.float16: _lib.DT_HALF, torch.float32: _lib.DT_FLOAT}
+_STAGE = "the keypoint front end"
+_FLOATS = (torch.float16, torch.float32)
 MAX_KEYPOINTS = 2048  # the assignment head's limit (lg_assign_matches: m, n <= 2048, n % 8 == 0)
 MAX_RADIUS = 4
 
@@ -40,17 +41,9 @@ class Features(NamedTuple):
     scores: torch.Tensor
     counts: torch.Tensor
 
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _gpu(name: str, t: torch.Tensor, dtypes, dim: int) -> None:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise PluginError(f"{name}: the keypoint front end runs on the GPU only (no CPU fallback)")
-    if t.dtype not in dtypes or t.dim() != dim:
-        raise ValueError(f"{name}: expected a {dim}-d tensor of {' or '.join(str(d) for d in dtypes)}, got "
-                         f"{tuple(t.shape)} {t.dtype}")
+    def rows(self, sl) -> "Features":
+        """The same slice of the images of every field."""
+        return Features(*(t[sl] for t in self))
 
 
 def _check_k(k: int) -> int:
@@ -63,27 +56,25 @@ def _check_k(k: int) -> int:
 # ---- the four stages, one C entry point each ----------------------------------------------------------
 def heatmap(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """lg_kp_heatmap: logits [B, 65, Hc, Wc] (fp16 / fp32) -> scores [B, 8 Hc, 8 Wc] fp32."""
-    _gpu("logits", logits, (torch.float16, torch.float32), 4)
+    require_gpu("logits", logits, _STAGE, _FLOATS, 4)
     if logits.shape[1] != 65:
         raise ValueError(f"logits: expected [B, 65, Hc, Wc], got {tuple(logits.shape)}")
     logits = logits.contiguous()
     b, _, hc, wc = logits.shape
     if out is None:
         out = torch.empty((b, hc * 8, wc * 8), dtype=torch.float32, device=logits.device)
-    st = _lib.load().lg_kp_heatmap(_DT[logits.dtype], logits.data_ptr(), hc, wc, b, out.data_ptr(), _stream(logits))
-    _check(st, "lg_kp_heatmap")
+    call("lg_kp_heatmap", DT[logits.dtype], logits.data_ptr(), hc, wc, b, out.data_ptr(), stream_of(logits))
     return out
 
 
 def nms(scores: torch.Tensor, radius: int = 4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """lg_kp_nms: simple_nms on scores [B, H, W] fp32, bitwise the reference's result."""
-    _gpu("scores", scores, (torch.float32,), 3)
+    require_gpu("scores", scores, _STAGE, (torch.float32,), 3)
     scores = scores.contiguous()
     b, h, w = scores.shape
     if out is None:
         out = torch.empty_like(scores)
-    st = _lib.load().lg_kp_nms(scores.data_ptr(), h, w, b, int(radius), out.data_ptr(), _stream(scores))
-    _check(st, "lg_kp_nms")
+    call("lg_kp_nms", scores.data_ptr(), h, w, b, int(radius), out.data_ptr(), stream_of(scores))
     return out
 
 
@@ -91,20 +82,18 @@ def select(nms_map: torch.Tensor, k: int, threshold: float = 0.0005, border: int
            workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """lg_kp_select on the NMS map [B, H, W]: (count [B] int32, pix [B, k] int32, score [B, k] fp32), the k
     best candidates in descending score, ties by ascending pixel index; -1 / 0 past the count."""
-    _gpu("nms_map", nms_map, (torch.float32,), 3)
+    require_gpu("nms_map", nms_map, _STAGE, (torch.float32,), 3)
     nms_map = nms_map.contiguous()
     b, h, w = nms_map.shape
     dev = nms_map.device
-    lib = _lib.load()
     count = torch.empty((b,), dtype=torch.int32, device=dev)
     pix = torch.empty((b, int(k)), dtype=torch.int32, device=dev)
     score = torch.empty((b, int(k)), dtype=torch.float32, device=dev)
-    stream = _stream(nms_map)
+    stream = stream_of(nms_map)
     if workspace is None:
-        workspace = _workspace(dev, stream, lib.lg_kp_select_workspace(h, w, b))
-    st = lib.lg_kp_select(nms_map.data_ptr(), h, w, b, int(border), float(threshold), int(k), count.data_ptr(),
-                          pix.data_ptr(), score.data_ptr(), workspace.data_ptr(), stream)
-    _check(st, "lg_kp_select")
+        workspace = _workspace(dev, stream, _lib.load().lg_kp_select_workspace(h, w, b))
+    call("lg_kp_select", nms_map.data_ptr(), h, w, b, int(border), float(threshold), int(k), count.data_ptr(),
+         pix.data_ptr(), score.data_ptr(), workspace.data_ptr(), stream)
     return count, pix, score
 
 
@@ -112,10 +101,10 @@ def describe(dense: torch.Tensor, count: torch.Tensor, pix: torch.Tensor, dense_
              dtype: torch.dtype = torch.float16) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """lg_kp_describe: dense [B, 256, Hc, Wc] (fp16 / fp32, any strides: NCHW and channels_last are read in
     place) sampled at the selected pixels -> (desc [B, K, 256], kpts_px [B, K, 2] int32, kpts [B, K, 2])."""
-    _gpu("dense", dense, (torch.float16, torch.float32), 4)
+    require_gpu("dense", dense, _STAGE, _FLOATS, 4)
     if dense.shape[1] != 256:
         raise ValueError(f"dense: expected [B, 256, Hc, Wc], got {tuple(dense.shape)}")
-    if dtype not in _DT:
+    if dtype not in DT:
         raise ValueError(f"dtype must be torch.float16 or torch.float32, got {dtype}")
     b, _, hc, wc = dense.shape
     k = pix.shape[1]
@@ -128,10 +117,9 @@ def describe(dense: torch.Tensor, count: torch.Tensor, pix: torch.Tensor, dense_
     kpx = torch.empty((b, k, 2), dtype=torch.int32, device=dev)
     kpts = torch.empty((b, k, 2), dtype=dtype, device=dev)
     sb, sc, sy, sx = dense.stride()
-    st = _lib.load().lg_kp_describe(_DT[dense.dtype], dense.data_ptr(), sb, sc, sy, sx, hc, wc, b, k,
-                                    count.contiguous().data_ptr(), pix.contiguous().data_ptr(), int(bool(dense_normalized)),
-                                    _DT[dtype], desc.data_ptr(), kpx.data_ptr(), kpts.data_ptr(), _stream(dense))
-    _check(st, "lg_kp_describe")
+    call("lg_kp_describe", DT[dense.dtype], dense.data_ptr(), sb, sc, sy, sx, hc, wc, b, k, count.contiguous().data_ptr(),
+         pix.contiguous().data_ptr(), int(bool(dense_normalized)), DT[dtype], desc.data_ptr(), kpx.data_ptr(),
+         kpts.data_ptr(), stream_of(dense))
     return desc, kpx, kpts
 
 
@@ -147,19 +135,16 @@ class KeypointFrontend:
             raise ValueError(f"threshold must be >= 0, got {threshold}")
         if int(remove_borders) < 0:
             raise ValueError(f"remove_borders must be >= 0, got {remove_borders}")
-        if dtype not in _DT:
+        if dtype not in DT:
             raise ValueError(f"dtype must be torch.float16 or torch.float32, got {dtype}")
         self.nms_radius, self.threshold = int(nms_radius), float(threshold)
         self.max_keypoints, self.remove_borders, self.dtype = _check_k(max_keypoints), int(remove_borders), dtype
 
     def _buffers(self, like: torch.Tensor, b: int, h: int, w: int):
         """The two [B, H, W] fp32 maps and lg_kp_select's workspace, carved from the stream's workspace."""
-        lib = _lib.load()
-        plane = (b * h * w * 4 + 255) // 256 * 256
-        sel = lib.lg_kp_select_workspace(h, w, b)
-        ws = _workspace(like.device, _stream(like), 2 * plane + sel)
-        maps = [ws[i * plane:i * plane + b * h * w * 4].view(torch.float32).view(b, h, w) for i in range(2)]
-        return maps[0], maps[1], ws[2 * plane:]
+        plane = b * h * w * 4
+        m0, m1, sel = carve(like.device, stream_of(like), [plane, plane, _lib.load().lg_kp_select_workspace(h, w, b)])
+        return m0.view(torch.float32).view(b, h, w), m1.view(torch.float32).view(b, h, w), sel
 
     def _finish(self, nms_map, ws, dense, dense_normalized) -> Features:
         count, pix, score = select(nms_map, self.max_keypoints, self.threshold, self.remove_borders, workspace=ws)
@@ -173,7 +158,7 @@ class KeypointFrontend:
     def extract(self, logits: torch.Tensor, dense: torch.Tensor, dense_normalized: bool = False) -> Features:
         """logits [B, 65, Hc, Wc] (convPb's output) and dense [B, 256, Hc, Wc] (convDb's output, or with
         dense_normalized=True the L2-normalised map SuperPoint.forward returns) -> Features. Five launches."""
-        _gpu("logits", logits, (torch.float16, torch.float32), 4)
+        require_gpu("logits", logits, _STAGE, _FLOATS, 4)
         b, _, hc, wc = logits.shape
         self._check_dense(dense, b, hc, wc)
         heat, nmap, ws = self._buffers(logits, b, hc * 8, wc * 8)
@@ -186,7 +171,7 @@ class KeypointFrontend:
         """The same from a heatmap [B, H, W] fp32 a caller's SuperPoint already produced (H, W multiples of
         8). nms_done=True: the map is already simple_nms' output (what the reference's SuperPoint.forward
         returns), and the NMS launch is skipped."""
-        _gpu("scores", scores, (torch.float32,), 3)
+        require_gpu("scores", scores, _STAGE, (torch.float32,), 3)
         b, h, w = scores.shape
         if h % 8 or w % 8:
             raise ValueError(f"scores: H and W must be multiples of 8, got {h} x {w}")

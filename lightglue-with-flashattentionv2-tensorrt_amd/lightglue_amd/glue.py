@@ -7,10 +7,8 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._host import DT, _workspace, call, stream_of
 from .matches import MatchResult
-from .plugin import _check, _workspace
-
-_DT = {torch.float16: _lib.DT_HALF, torch.float32: _lib.DT_FLOAT}
 
 
 def _sp(splits):
@@ -27,34 +25,25 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
-def _call(name: str, *args) -> None:
-    """The entry point `name` of the library; any status but success raises (plugin._check)."""
-    _check(getattr(_lib.load(), name)(*args), name)
-
-
 class _Hip:
     """Thin wrappers of the gfx950 glue kernels (current stream, fail loudly on error). Row-major
     tensors hold P image pairs stacked pair-major ([1, P*(n0+n1), C]); per-image head-major
     tensors are [P, heads, ni, 64] (include/lightglue_glue.h)."""
 
     @staticmethod
-    def _stream(t):
-        return torch.cuda.current_stream(t.device).cuda_stream
-
-    @staticmethod
     def qkv_rotary_split(qkv, cos, sin, heads, splits):
         n0, n1, pr = _sp(splits)
         out = [tuple(_mk(qkv, pr, heads, n) for _ in range(3)) for n in (n0, n1)]
-        _call("lg_qkv_rotary_split", _DT[qkv.dtype], qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), heads, n0, n1, pr,
-              *(t.data_ptr() for t in out[0]), *(t.data_ptr() for t in out[1]), _Hip._stream(qkv))
+        call("lg_qkv_rotary_split", DT[qkv.dtype], qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), heads, n0, n1, pr,
+             *(t.data_ptr() for t in out[0]), *(t.data_ptr() for t in out[1]), stream_of(qkv))
         return out
 
     @staticmethod
     def split_heads2(a, b, heads, splits):
         n0, n1, pr = _sp(splits)
         a0, a1, b0, b1 = (_mk(a, pr, heads, n) for n in (n0, n1, n0, n1))
-        _call("lg_split_heads2", _DT[a.dtype], a.data_ptr(), b.data_ptr(), heads, n0, n1, pr, a0.data_ptr(), a1.data_ptr(),
-              b0.data_ptr(), b1.data_ptr(), _Hip._stream(a))
+        call("lg_split_heads2", DT[a.dtype], a.data_ptr(), b.data_ptr(), heads, n0, n1, pr, a0.data_ptr(), a1.data_ptr(),
+             b0.data_ptr(), b1.data_ptr(), stream_of(a))
         return (a0, a1), (b0, b1)
 
     @staticmethod
@@ -63,8 +52,8 @@ class _Hip:
         n0, n1, pr = _sp(splits)
         a0, a1, b0, b1 = (_mk(ab, pr, heads, n) for n in (n0, n1, n0, n1))
         half = heads * 64
-        _call("lg_split_heads2_ld", _DT[ab.dtype], ab.data_ptr(), ab.data_ptr() + half * ab.element_size(), 2 * half, heads,
-              n0, n1, pr, a0.data_ptr(), a1.data_ptr(), b0.data_ptr(), b1.data_ptr(), _Hip._stream(ab))
+        call("lg_split_heads2_ld", DT[ab.dtype], ab.data_ptr(), ab.data_ptr() + half * ab.element_size(), 2 * half, heads,
+             n0, n1, pr, a0.data_ptr(), a1.data_ptr(), b0.data_ptr(), b1.data_ptr(), stream_of(ab))
         return (a0, a1), (b0, b1)
 
     @staticmethod
@@ -72,8 +61,8 @@ class _Hip:
         """[x | merge_heads(x0, x1)] -> [1, P*(N0+N1), 2*heads*64] (the FFN input)."""
         pr, heads, n0, n1 = x0.shape[0], x0.shape[1], x0.shape[2], x1.shape[2]
         out = torch.empty((1, pr * (n0 + n1), 2 * heads * 64), dtype=x.dtype, device=x.device)
-        _call("lg_merge_heads_cat", _DT[x.dtype], x.data_ptr(), x0.data_ptr(), x1.data_ptr(), heads, n0, n1, pr,
-              out.data_ptr(), _Hip._stream(x))
+        call("lg_merge_heads_cat", DT[x.dtype], x.data_ptr(), x0.data_ptr(), x1.data_ptr(), heads, n0, n1, pr,
+             out.data_ptr(), stream_of(x))
         return out
 
     # ---- projections with their neighbours fused (fp16; csrc/lightglue_linear.hip, lightglue_ffn.hip) ----
@@ -82,8 +71,8 @@ class _Hip:
         """a [1, M, K] -> a·wᵀ + b (+ res) [1, M, N]."""
         m, k = a.shape[1], a.shape[2]
         out = torch.empty((1, m, w.shape[0]), dtype=a.dtype, device=a.device)
-        _call("lg_linear", a.data_ptr(), w.data_ptr(), b.data_ptr(), _ptr(res), m, w.shape[0], k, out.data_ptr(),
-              _Hip._stream(a))
+        call("lg_linear", a.data_ptr(), w.data_ptr(), b.data_ptr(), _ptr(res), m, w.shape[0], k, out.data_ptr(),
+             stream_of(a))
         return out
 
     @staticmethod
@@ -91,8 +80,8 @@ class _Hip:
         """[x | merge_heads(c0, c1)]·wᵀ + b."""
         pr, heads, n0, n1 = c0.shape[0], c0.shape[1], c0.shape[2], c1.shape[2]
         out = torch.empty((1, pr * (n0 + n1), w.shape[0]), dtype=x.dtype, device=x.device)
-        _call("lg_linear_cat", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, w.data_ptr(), b.data_ptr(),
-              w.shape[0], out.data_ptr(), _Hip._stream(x))
+        call("lg_linear_cat", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, w.data_ptr(), b.data_ptr(),
+             w.shape[0], out.data_ptr(), stream_of(x))
         return out
 
     @staticmethod
@@ -104,9 +93,9 @@ class _Hip:
         m = pr * (n0 + n1)
         h = torch.empty((1, m, w.shape[0]), dtype=x.dtype, device=x.device)
         out = torch.empty((1, m, w2.shape[0]), dtype=x.dtype, device=x.device)
-        _call("lg_linear_cat_ffn", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, w.data_ptr(), b.data_ptr(),
-              ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w2.data_ptr(), b2.data_ptr(), _ptr(packed),
-              h.data_ptr(), out.data_ptr(), _Hip._stream(x))
+        call("lg_linear_cat_ffn", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, w.data_ptr(), b.data_ptr(),
+             ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w2.data_ptr(), b2.data_ptr(), _ptr(packed),
+             h.data_ptr(), out.data_ptr(), stream_of(x))
         return out
 
     @staticmethod
@@ -125,9 +114,9 @@ class _Hip:
         else:
             outs = [torch.empty((1, m, n_store), dtype=x.dtype, device=x.device)]
         ptrs = (ctypes.c_void_p * 6)(*([t.data_ptr() for t in outs] + [None] * (6 - len(outs))))
-        _call("lg_linear_cat_ffn_proj", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, b.data_ptr(),
-              ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), b2.data_ptr(), packed.data_ptr(), kind, b3.data_ptr(),
-              _ptr(cos), _ptr(sin), n_store, ptrs, out.data_ptr(), _Hip._stream(x))
+        call("lg_linear_cat_ffn_proj", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, b.data_ptr(),
+             ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), b2.data_ptr(), packed.data_ptr(), kind, b3.data_ptr(),
+             _ptr(cos), _ptr(sin), n_store, ptrs, out.data_ptr(), stream_of(x))
         if kind == 1:
             return out, ((outs[0], outs[1]), (outs[2], outs[3]))
         if kind == 2:
@@ -139,41 +128,41 @@ class _Hip:
         """GELU(LayerNorm([x | merge_heads(c0, c1)]·wᵀ + b)) in one launch (P pairs of equal sizes)."""
         pr, heads, n0, n1 = c0.shape[0], c0.shape[1], c0.shape[2], c1.shape[2]
         out = torch.empty((1, pr * (n0 + n1), w.shape[0]), dtype=x.dtype, device=x.device)
-        _call("lg_linear_cat_ln_gelu", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, w.data_ptr(),
-              b.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), out.data_ptr(), _Hip._stream(x))
+        call("lg_linear_cat_ln_gelu", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, w.data_ptr(),
+             b.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), out.data_ptr(), stream_of(x))
         return out
 
     @staticmethod
     def linear_qkv_rotary(x, w_perm, b_perm, cos, sin, heads, splits):
         n0, n1, pr = _sp(splits)
         out = [tuple(_mk(x, pr, heads, n) for _ in range(3)) for n in (n0, n1)]
-        _call("lg_linear_qkv_rotary", x.data_ptr(), w_perm.data_ptr(), b_perm.data_ptr(), cos.data_ptr(), sin.data_ptr(),
-              heads, n0, n1, pr, x.shape[2], *(t.data_ptr() for t in out[0]), *(t.data_ptr() for t in out[1]),
-              _Hip._stream(x))
+        call("lg_linear_qkv_rotary", x.data_ptr(), w_perm.data_ptr(), b_perm.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+             heads, n0, n1, pr, x.shape[2], *(t.data_ptr() for t in out[0]), *(t.data_ptr() for t in out[1]),
+             stream_of(x))
         return out
 
     @staticmethod
     def linear_split2(x, w, b, heads, splits):
         n0, n1, pr = _sp(splits)
         a0, a1, b0, b1 = (_mk(x, pr, heads, n) for n in (n0, n1, n0, n1))
-        _call("lg_linear_split2", x.data_ptr(), w.data_ptr(), b.data_ptr(), heads, n0, n1, pr, x.shape[2], a0.data_ptr(),
-              a1.data_ptr(), b0.data_ptr(), b1.data_ptr(), _Hip._stream(x))
+        call("lg_linear_split2", x.data_ptr(), w.data_ptr(), b.data_ptr(), heads, n0, n1, pr, x.shape[2], a0.data_ptr(),
+             a1.data_ptr(), b0.data_ptr(), b1.data_ptr(), stream_of(x))
         return (a0, a1), (b0, b1)
 
     @staticmethod
     def merge_heads(x0, x1):
         pr, heads, n0, n1 = x0.shape[0], x0.shape[1], x0.shape[2], x1.shape[2]
         out = torch.empty((1, pr * (n0 + n1), heads * 64), dtype=x0.dtype, device=x0.device)
-        _call("lg_merge_heads", _DT[x0.dtype], x0.data_ptr(), x1.data_ptr(), heads, n0, n1, pr, out.data_ptr(),
-              _Hip._stream(x0))
+        call("lg_merge_heads", DT[x0.dtype], x0.data_ptr(), x1.data_ptr(), heads, n0, n1, pr, out.data_ptr(),
+             stream_of(x0))
         return out
 
     @staticmethod
     def layernorm_gelu(x, ln: nn.LayerNorm):
         y = torch.empty_like(x)
         rows, dim = x.numel() // x.shape[-1], x.shape[-1]
-        _call("lg_layernorm_gelu", _DT[x.dtype], x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), rows, dim,
-              float(ln.eps), y.data_ptr(), _Hip._stream(x))
+        call("lg_layernorm_gelu", DT[x.dtype], x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), rows, dim,
+             float(ln.eps), y.data_ptr(), stream_of(x))
         return y
 
     @staticmethod
@@ -182,10 +171,10 @@ class _Hip:
         pr, m, n = sim.shape[0], sim.shape[1], sim.shape[2]
         lib = _lib.load()
         out = torch.empty_like(sim)
-        stream = _Hip._stream(sim)
+        stream = stream_of(sim)
         ws = _workspace(sim.device, stream, lib.lg_log_double_softmax_workspace(m, n, pr))
-        _call("lg_log_double_softmax", sim.data_ptr(), z0.data_ptr(), z1.data_ptr(), m, n, pr, out.data_ptr(), ws.data_ptr(),
-              stream)
+        call("lg_log_double_softmax", sim.data_ptr(), z0.data_ptr(), z1.data_ptr(), m, n, pr, out.data_ptr(), ws.data_ptr(),
+             stream)
         return out
 
     @staticmethod
@@ -195,11 +184,11 @@ class _Hip:
         pr, n, ch = sim.shape[0], sim.shape[2], v.shape[2]
         lib = _lib.load()
         out = torch.empty(sim.shape, dtype=torch.float32, device=sim.device)
-        stream = _Hip._stream(sim)
+        stream = stream_of(sim)
         ws = _workspace(sim.device, stream, lib.lg_log_double_softmax_f16_workspace(m, n, pr))
         base = v.data_ptr() + zc * v.element_size()
-        _call("lg_log_double_softmax_f16", sim.data_ptr(), base, base + m * ch * v.element_size(), (m + n) * ch, ch, m, n, pr,
-              out.data_ptr(), ws.data_ptr(), stream)
+        call("lg_log_double_softmax_f16", sim.data_ptr(), base, base + m * ch * v.element_size(), (m + n) * ch, ch, m, n, pr,
+             out.data_ptr(), ws.data_ptr(), stream)
         return out
 
     _last_assign_ws = None  # (tests read the similarity copy the kernel leaves in its workspace)
@@ -213,11 +202,11 @@ class _Hip:
         pr, n, ch = v.shape[0], v.shape[1] - m, v.shape[2]
         lib = _lib.load()
         out = torch.empty((pr, m, n), dtype=torch.float32, device=v.device)
-        stream = _Hip._stream(v)
+        stream = stream_of(v)
         ws = _workspace(v.device, stream, lib.lg_assign_scores_workspace(m, n, pr))
         _Hip._last_assign_ws = ws
         name, tables = ("lg_assign_scores", ()) if lens is None else ("lg_assign_scores_lens", [t.data_ptr() for t in lens])
-        _call(name, v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, *tables, out.data_ptr(), ws.data_ptr(), stream)
+        call(name, v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, *tables, out.data_ptr(), ws.data_ptr(), stream)
         return out
 
     @staticmethod
@@ -228,11 +217,11 @@ class _Hip:
         pr, n, ch = v.shape[0], v.shape[1] - m, v.shape[2]
         lib = _lib.load()
         out = MatchResult.empty(pr, m, n, v.device)
-        stream = _Hip._stream(v)
+        stream = stream_of(v)
         ws = _workspace(v.device, stream, lib.lg_assign_matches_workspace(m, n, pr))
         name, tables = ("lg_assign_matches", ()) if lens is None else ("lg_assign_matches_lens", [t.data_ptr() for t in lens])
-        _call(name, v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, *tables, float(threshold), *(t.data_ptr() for t in out),
-              ws.data_ptr(), stream)
+        call(name, v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, *tables, float(threshold), *(t.data_ptr() for t in out),
+             ws.data_ptr(), stream)
         return out
 
     # ---- adaptive depth / width (csrc/lightglue_adaptive.hip) ----
@@ -246,9 +235,9 @@ class _Hip:
         keep = torch.empty((pr, m + n), dtype=torch.uint8, device=dev)
         stats = torch.empty((pr, 4), dtype=torch.int32, device=dev)
         lens = lens if lens is not None else (None, None)
-        _call("lg_token_scores", x.data_ptr(), m, n, pr, _ptr(lens[0]), _ptr(lens[1]), w_tok.data_ptr(), b_tok.data_ptr(),
-              w_match.data_ptr(), b_match.data_ptr(), float(t_conf), float(t_keep), int(flags), conf.data_ptr(),
-              mtch.data_ptr(), keep.data_ptr(), stats.data_ptr(), _Hip._stream(x))
+        call("lg_token_scores", x.data_ptr(), m, n, pr, _ptr(lens[0]), _ptr(lens[1]), w_tok.data_ptr(), b_tok.data_ptr(),
+             w_match.data_ptr(), b_match.data_ptr(), float(t_conf), float(t_keep), int(flags), conf.data_ptr(),
+             mtch.data_ptr(), keep.data_ptr(), stats.data_ptr(), stream_of(x))
         return conf, mtch, keep, stats
 
     @staticmethod
@@ -264,10 +253,10 @@ class _Hip:
         i0, i1, l0, l1 = (torch.empty(s, dtype=torch.int32, device=dev) for s in ((pr, m_out), (pr, n_out), (pr,), (pr,)))
         lens = lens if lens is not None else (None, None)
         p0, p1 = prune if prune is not None else (None, None)
-        _call("lg_compact_rows", x.data_ptr(), cos.data_ptr(), sin.data_ptr(), keep.data_ptr(), _ptr(ind[0]), _ptr(ind[1]),
-              m, n, pr, _ptr(lens[0]), _ptr(lens[1]), m_out, n_out, xo.data_ptr(), co.data_ptr(), so.data_ptr(),
-              i0.data_ptr(), i1.data_ptr(), l0.data_ptr(), l1.data_ptr(), _ptr(p0), _ptr(p1),
-              p0.shape[1] if p0 is not None else 0, p1.shape[1] if p1 is not None else 0, int(layers), _Hip._stream(x))
+        call("lg_compact_rows", x.data_ptr(), cos.data_ptr(), sin.data_ptr(), keep.data_ptr(), _ptr(ind[0]), _ptr(ind[1]),
+             m, n, pr, _ptr(lens[0]), _ptr(lens[1]), m_out, n_out, xo.data_ptr(), co.data_ptr(), so.data_ptr(),
+             i0.data_ptr(), i1.data_ptr(), l0.data_ptr(), l1.data_ptr(), _ptr(p0), _ptr(p1),
+             p0.shape[1] if p0 is not None else 0, p1.shape[1] if p1 is not None else 0, int(layers), stream_of(x))
         return xo, co, so, (i0, i1), (l0, l1)
 
     @staticmethod
@@ -279,8 +268,8 @@ class _Hip:
         ind = ind if ind is not None else (None, None)
         lens = lens if lens is not None else (None, None)
         p0, p1 = prune if prune is not None else (None, None)
-        _call("lg_matches_scatter", *(t.data_ptr() for t in r), _ptr(ind[0]), _ptr(ind[1]), _ptr(lens[0]), _ptr(lens[1]),
-              mc, nc, m, n, pr, int(stop), *(t.data_ptr() for t in out), _ptr(p0), _ptr(p1), _Hip._stream(r.matches0))
+        call("lg_matches_scatter", *(t.data_ptr() for t in r), _ptr(ind[0]), _ptr(ind[1]), _ptr(lens[0]), _ptr(lens[1]),
+             mc, nc, m, n, pr, int(stop), *(t.data_ptr() for t in out), _ptr(p0), _ptr(p1), stream_of(r.matches0))
         return out
 
     @staticmethod
@@ -292,6 +281,6 @@ class _Hip:
         cos = torch.empty((1, rows, 64), dtype=desc0.dtype, device=desc0.device)
         sin = torch.empty_like(cos)
         t = [u.contiguous() for u in (desc0, desc1, kpts0, kpts1, wr)]
-        _call("lg_pair_inputs", *(u.data_ptr() for u in t), m, n, pr, d, x.data_ptr(), cos.data_ptr(), sin.data_ptr(),
-              _Hip._stream(desc0))
+        call("lg_pair_inputs", *(u.data_ptr() for u in t), m, n, pr, d, x.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+             stream_of(desc0))
         return x, cos, sin

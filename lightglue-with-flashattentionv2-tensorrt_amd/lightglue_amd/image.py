@@ -24,18 +24,14 @@ from typing import NamedTuple, Sequence, Tuple, Union
 import torch
 
 from . import _lib
+from ._host import DT, PluginError, call, require_gpu, stream_of
 from .frontend import Features, KeypointFrontend
-from .plugin import PluginError, _check
-from .superpoint import SuperPointEncoder, match_images
+from .superpoint import SuperPointEncoder, extract_pairs
 
-_DT = {torch.float16: _lib.DT_HALF, torch.float32: _lib.DT_FLOAT}
+_STAGE = "the image input"
 _INTERP = {"linear": _lib.IMG_LINEAR, "area": _lib.IMG_AREA}
 MAX_SIDE = 16384  # source and target sides: (2 o + 1) w stays in int32
 GREY = (0.299, 0.587, 0.114)  # utils.py:72-76
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _check_interp(interp: str) -> str:
@@ -132,11 +128,6 @@ def _check_layout(layout: str) -> str:
     return layout
 
 
-def _on_gpu(t: torch.Tensor, what: str) -> None:
-    if not t.is_cuda:
-        raise PluginError(f"{what}: the image input runs on the GPU only (no CPU fallback); got a CPU tensor")
-
-
 class ImageBatch(NamedTuple):
     """B source images as lg_img_prepare reads them: table, the device array of B descriptors (uint8
     [B * lg_img_src_bytes()]); src_sizes [B, 2] int32 (h, w) on the device; sources, the tensors the
@@ -160,7 +151,7 @@ class ImageInput:
     def __init__(self, size, interp: str = "linear", dtype: torch.dtype = torch.float16) -> None:
         self.size = _check_target(tuple(size) if isinstance(size, list) else size)
         self.interp = _check_interp(interp)
-        if dtype not in _DT:
+        if dtype not in DT:
             raise ValueError(f"dtype must be torch.float16 or torch.float32, got {dtype}")
         self.dtype = dtype
         self._sizes = {}  # (device, B, h, w) -> src_sizes of a [B, ...] tensor's frames
@@ -177,7 +168,7 @@ class ImageInput:
             raise ValueError("images: no images")
         desc = [_describe(img, layout, f"images[{i}]") for i, img in enumerate(images)]
         for i, img in enumerate(images):
-            _on_gpu(img, f"images[{i}]")
+            require_gpu(f"images[{i}]", img, _STAGE)
         dev = images[0].device
         if any(img.device != dev for img in images):
             raise ValueError("images: all sources must be on one device")
@@ -210,7 +201,6 @@ class ImageInput:
         equal-sized frames ([B, H, W], [B, H, W, C] or [B, C, H, W], any strides; lg_img_prepare_batch, no
         table) -> PreparedImages. One launch."""
         ht, wt = self.size
-        lib = _lib.load()
         if isinstance(images, torch.Tensor):
             _check_layout(layout)
             if images.dim() not in (3, 4):
@@ -218,23 +208,21 @@ class ImageInput:
             if images.shape[0] == 0:
                 raise ValueError("images: no images")
             h, w, c, sy, sx, sc = _describe(images[0], layout, "images")
-            _on_gpu(images, "images")
+            require_gpu("images", images, _STAGE)
             b, dev = images.shape[0], images.device
             out = torch.empty((b, ht, wt), dtype=self.dtype, device=dev)
-            st = lib.lg_img_prepare_batch(images.data_ptr(), b, h, w, c, int(bool(bgr)), images.stride(0), sy, sx, sc, ht, wt,
-                                          _INTERP[self.interp], _DT[self.dtype], out.data_ptr(), _stream(images))
-            _check(st, "lg_img_prepare_batch")
+            call("lg_img_prepare_batch", images.data_ptr(), b, h, w, c, int(bool(bgr)), images.stride(0), sy, sx, sc, ht, wt,
+                 _INTERP[self.interp], DT[self.dtype], out.data_ptr(), stream_of(images))
             return PreparedImages(out, self._frame_sizes(dev, b, h, w))
         batch = images if isinstance(images, ImageBatch) else self.table(images, layout, bgr)
         b, dev = batch.src_sizes.shape[0], batch.table.device
-        _on_gpu(batch.table, "table")
+        require_gpu("table", batch.table, _STAGE)
         if batch.table.dtype != torch.uint8 or batch.table.numel() != b * ctypes.sizeof(_lib.ImgSrc) or b < 1:
             raise ValueError(f"table: expected table()'s uint8 [{b} * {ctypes.sizeof(_lib.ImgSrc)}], got "
                              f"{tuple(batch.table.shape)} {batch.table.dtype}")
         out = torch.empty((b, ht, wt), dtype=self.dtype, device=dev)
-        st = lib.lg_img_prepare(batch.table.data_ptr(), b, ht, wt, _INTERP[self.interp], _DT[self.dtype], out.data_ptr(),
-                                _stream(out))
-        _check(st, "lg_img_prepare")
+        call("lg_img_prepare", batch.table.data_ptr(), b, ht, wt, _INTERP[self.interp], DT[self.dtype], out.data_ptr(),
+             stream_of(out))
         return PreparedImages(out, batch.src_sizes)
 
     def keypoints(self, features: Features, prepared: PreparedImages) -> torch.Tensor:
@@ -242,10 +230,7 @@ class ImageInput:
         image's own pixels: (2 px + 1) w / (2 Wt) - 1/2 (utils.py:94-97); rows past features.counts are zero."""
         kpx, counts, sizes = features.kpts_px, features.counts, prepared.src_sizes
         for name, t in (("kpts_px", kpx), ("counts", counts), ("src_sizes", sizes)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise PluginError(f"{name}: the image input runs on the GPU only (no CPU fallback)")
-            if t.dtype != torch.int32:
-                raise ValueError(f"{name}: expected torch.int32, got {t.dtype}")
+            require_gpu(name, t, _STAGE, (torch.int32,))
         if kpx.dim() != 3 or kpx.shape[2] != 2 or kpx.shape[1] < 1:
             raise ValueError(f"kpts_px: expected [B, K, 2], got {tuple(kpx.shape)}")
         b, k, _ = kpx.shape
@@ -254,38 +239,22 @@ class ImageInput:
                              f"{tuple(sizes.shape)}")
         out = torch.empty((b, k, 2), dtype=torch.float32, device=kpx.device)
         if b:
-            st = _lib.load().lg_kp_to_source(kpx.contiguous().data_ptr(), counts.contiguous().data_ptr(),
-                                             sizes.contiguous().data_ptr(), self.size[0], self.size[1], b, k, out.data_ptr(),
-                                             _stream(kpx))
-            _check(st, "lg_kp_to_source")
+            call("lg_kp_to_source", kpx.contiguous().data_ptr(), counts.contiguous().data_ptr(), sizes.contiguous().data_ptr(),
+                 self.size[0], self.size[1], b, k, out.data_ptr(), stream_of(kpx))
         return out
-
-
-class _Recording:
-    """A front end that remembers the Features its extract returned (match_images keeps them to itself)."""
-
-    def __init__(self, frontend: KeypointFrontend) -> None:
-        self._frontend, self.features = frontend, None
-
-    def extract(self, *args, **kwargs) -> Features:
-        self.features = self._frontend.extract(*args, **kwargs)
-        return self.features
 
 
 def match_source_images(image_input: ImageInput, encoder: SuperPointEncoder, frontend: KeypointFrontend, matcher, images0,
                         images1):
     """The matches of P pairs of source images and the keypoints in each source's own pixels: (MatchResult,
     kpts0_src [P, K, 2], kpts1_src [P, K, 2]). images0 / images1: what ImageInput.prepare takes (the two sides
-    may differ in every source size; the target is shared). prepare on each side, match_images on the prepared
-    tensors as it stands, keypoints on the features it extracted. Nothing is read back: with an ImageBatch or a
-    tensor per side the whole enqueues, or is captured, as one piece."""
+    may differ in every source size; the target is shared). prepare on each side, extract_pairs on the prepared
+    tensors, matcher.match_features and keypoints on its two Features. Nothing is read back: with an ImageBatch
+    or a tensor per side the whole enqueues, or is captured, as one piece."""
     p0, p1 = image_input.prepare(images0), image_input.prepare(images1)
-    rec = _Recording(frontend)
-    result = match_images(encoder, rec, matcher, p0.image, p1.image)
-    pairs, f = p0.image.shape[0], rec.features
-    kp0 = image_input.keypoints(Features(*(t[:pairs] for t in f)), p0)
-    kp1 = image_input.keypoints(Features(*(t[pairs:] for t in f)), p1)
-    return result, kp0, kp1
+    f0, f1 = extract_pairs(encoder, frontend, p0.image, p1.image)
+    result = matcher.match_features(f0, f1)
+    return result, image_input.keypoints(f0, p0), image_input.keypoints(f1, p1)
 
 
 # ---- the same contract in framework ops (the tests' oracle, the A/B's other arm) ----------------------------
@@ -310,18 +279,16 @@ def image_reference(images, size, interp: str = "linear", dtype: torch.dtype = t
     ht, wt = int(size[0]), int(size[1])
     _check_interp(interp), _check_layout(layout)
 
-    def one(img: torch.Tensor) -> torch.Tensor:
-        h, w = _describe(img, layout)[:2]
-        wy = _matrix_on(h, ht, interp, str(img.device), compute)
-        wx = _matrix_on(w, wt, interp, str(img.device), compute)
-        return (wy @ _grey(img, layout, bgr, compute) @ wx.t()) / 255.0
+    def resample(frames: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+        """One frame (`like` itself) or a batch of frames that `like` is one of -> [..., Ht, Wt]."""
+        h, w = _describe(like, layout)[:2]
+        wy = _matrix_on(h, ht, interp, str(like.device), compute)
+        wx = _matrix_on(w, wt, interp, str(like.device), compute)
+        grey = frames.to(compute).contiguous() if like.dim() == 2 else _grey(frames, layout, bgr, compute)
+        return (wy @ grey @ wx.t()) / 255.0
 
     if isinstance(images, torch.Tensor):
         if images.dim() not in (3, 4) or images.shape[0] == 0:
             raise ValueError(f"images: expected a non-empty [B, H, W], [B, H, W, C] or [B, C, H, W], got {tuple(images.shape)}")
-        h, w = _describe(images[0], layout)[:2]
-        wy = _matrix_on(h, ht, interp, str(images.device), compute)
-        wx = _matrix_on(w, wt, interp, str(images.device), compute)
-        grey = images.to(compute).contiguous() if images.dim() == 3 else _grey(images, layout, bgr, compute)
-        return ((wy @ grey @ wx.t()) / 255.0).to(dtype)
-    return torch.stack([one(img) for img in images]).to(dtype)
+        return resample(images, images[0]).to(dtype)
+    return torch.stack([resample(img, img) for img in images]).to(dtype)

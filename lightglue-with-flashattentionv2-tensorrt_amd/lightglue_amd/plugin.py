@@ -18,22 +18,14 @@ There is no CPU fallback: CPU tensors raise, and a missing shared library raises
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Sequence, Tuple
+from typing import Sequence, Tuple
 
 import torch
 from torch import nn
 
 from . import _lib
-from ._lib import DT_FLOAT, DT_HALF, FMT_LINEAR, Dims, DynamicTensorDesc, TensorDesc
-
-
-class PluginError(RuntimeError):
-    """A contract violation the reference would have turned into PLUGIN_ASSERT -> abort()."""
-
-
-def _check(status: int, what: str) -> None:
-    if status != _lib.STATUS_SUCCESS:
-        raise PluginError(f"{what} failed (status {status}): {_lib.last_error()}")
+from ._host import DT, PluginError, _check, _workspace, stream_of  # noqa: F401
+from ._lib import FMT_LINEAR, Dims, DynamicTensorDesc, TensorDesc
 
 
 def _desc_array(descs: Sequence[TensorDesc]):
@@ -51,10 +43,8 @@ def _dyn_array(descs: Sequence[DynamicTensorDesc]):
 
 
 def torch_dtype_code(t: torch.Tensor) -> int:
-    if t.dtype == torch.float16:
-        return DT_HALF
-    if t.dtype == torch.float32:
-        return DT_FLOAT
+    if t.dtype in DT:
+        return DT[t.dtype]
     raise PluginError(f"unsupported dtype {t.dtype}: MHAHeadDim64 takes float16 or float32")
 
 
@@ -202,11 +192,10 @@ class LightGlueAttentionPluginCreator:
 
 
 # ---------------------------------------------------------------------------------------
-# Torch glue: one plugin object per process, one workspace per (device, stream), as the
-# TensorRT execution context would own (the plugin itself owns nothing, .cpp:114-175).
+# Torch glue: one plugin object per process, one workspace per (device, stream) (_host._workspace),
+# as the TensorRT execution context would own (the plugin itself owns nothing, .cpp:114-175).
 # ---------------------------------------------------------------------------------------
 _plugin = None
-_workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
 
 
 def get_plugin() -> LightGlueAttentionPlugin:
@@ -214,15 +203,6 @@ def get_plugin() -> LightGlueAttentionPlugin:
     if _plugin is None:
         _plugin = LightGlueAttentionPlugin()
     return _plugin
-
-
-def _workspace(device: torch.device, stream: int, nbytes: int) -> torch.Tensor:
-    key = (device.index if device.index is not None else torch.cuda.current_device(), stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws
 
 
 def set_concurrency_hint(streams: int) -> int:
@@ -258,7 +238,7 @@ def mha_hd64(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, out: t
     plugin = get_plugin()
     in_desc = [tensor_desc(query), tensor_desc(key), tensor_desc(value)]
     out_desc = [tensor_desc(out)]
-    stream = torch.cuda.current_stream(query.device).cuda_stream
+    stream = stream_of(query)
     nbytes = plugin.get_workspace_size(in_desc, out_desc)
     ws = _workspace(query.device, stream, nbytes)
     plugin.enqueue(in_desc, out_desc, [query.data_ptr(), key.data_ptr(), value.data_ptr()], [out.data_ptr()],
@@ -278,7 +258,7 @@ def bound_enqueue(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, o
     plugin = get_plugin()
     in_desc = [tensor_desc(query), tensor_desc(key), tensor_desc(value)]
     out_desc = [tensor_desc(out)]
-    stream = torch.cuda.current_stream(query.device).cuda_stream
+    stream = stream_of(query)
     ws = _workspace(query.device, stream, plugin.get_workspace_size(in_desc, out_desc))
     args = (plugin._h, _desc_array(in_desc), _desc_array(out_desc),
             (ctypes.c_void_p * 3)(query.data_ptr(), key.data_ptr(), value.data_ptr()),
@@ -321,17 +301,14 @@ def mha_hd64_batched(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor
     if out is None:
         out = torch.empty(query.shape, dtype=out_dtype, device=query.device)
     lib = _lib.load()
-    stream = torch.cuda.current_stream(query.device).cuda_stream
+    stream = stream_of(query)
     # (fp32 inputs: room for the fp16 copies when the planner converts before a single-pass kernel)
-    nbytes = lib.mha_hd64_launch_workspace_bytes_typed(b, h, nq, nkv, _DT[query.dtype])
+    nbytes = lib.mha_hd64_launch_workspace_bytes_typed(b, h, nq, nkv, DT[query.dtype])
     ws = _workspace(query.device, stream, nbytes) if nbytes else None
     status = getattr(lib, fn_name)(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(), b, h, nq,
                                    nkv, ws.data_ptr() if ws is not None else None, nbytes, stream)
     _check(status, fn_name)
     return out
-
-
-_DT = {torch.float16: _lib.DT_HALF, torch.float32: _lib.DT_FLOAT}
 
 
 def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None):
@@ -351,7 +328,7 @@ def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None
         return []
     in_dtype = calls[0][0].dtype
     out_dtype = out_dtype or in_dtype
-    if in_dtype not in _DT or out_dtype not in _DT:
+    if in_dtype not in DT or out_dtype not in DT:
         raise PluginError(f"unsupported dtypes {in_dtype} -> {out_dtype}")
     if outs is None:
         outs = [torch.empty(q.shape, dtype=out_dtype, device=q.device) for q, _, _ in calls]
@@ -367,7 +344,7 @@ def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None
                                  q.shape[2], k.shape[2])
     lib = _lib.load()
     device = calls[0][0].device
-    stream = torch.cuda.current_stream(device).cuda_stream
+    stream = stream_of(calls[0][0])
     if q_lens is not None and kv_lens is None:
         kv_lens = [None] * len(calls)
     if kv_lens is not None:
@@ -389,17 +366,17 @@ def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None
 
         kp = table(kv_lens, "kv_lens")
         if q_lens is None:
-            status = lib.mha_hd64_launch_grouped_lens(descs, kp, len(calls), _DT[in_dtype], _DT[out_dtype], None, 0, stream)
+            status = lib.mha_hd64_launch_grouped_lens(descs, kp, len(calls), DT[in_dtype], DT[out_dtype], None, 0, stream)
         else:
-            status = lib.mha_hd64_launch_grouped_qkv_lens(descs, table(q_lens, "q_lens"), kp, len(calls), _DT[in_dtype],
-                                                          _DT[out_dtype], None, 0, stream)
+            status = lib.mha_hd64_launch_grouped_qkv_lens(descs, table(q_lens, "q_lens"), kp, len(calls), DT[in_dtype],
+                                                          DT[out_dtype], None, 0, stream)
         _check(status, "mha_hd64_launch_grouped_lens")
         return outs
     # (fp32 groups: includes the fp16 copies of Q/K/V the convert launch writes when a single-pass
     # kernel that does not round fp32 inputs itself runs them; largest chunk of 4 calls)
-    nbytes = lib.mha_hd64_grouped_workspace_bytes_typed(descs, len(calls), _DT[in_dtype])
+    nbytes = lib.mha_hd64_grouped_workspace_bytes_typed(descs, len(calls), DT[in_dtype])
     ws = _workspace(device, stream, nbytes) if nbytes else None
-    status = lib.mha_hd64_launch_grouped(descs, len(calls), _DT[in_dtype], _DT[out_dtype],
+    status = lib.mha_hd64_launch_grouped(descs, len(calls), DT[in_dtype], DT[out_dtype],
                                          ws.data_ptr() if ws is not None else None, nbytes, stream)
     _check(status, "mha_hd64_launch_grouped")
     return outs

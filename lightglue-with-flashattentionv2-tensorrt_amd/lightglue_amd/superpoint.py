@@ -24,10 +24,11 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, synth
+from ._host import DT, call, carve, require_gpu, stream_of
 from .frontend import Features, KeypointFrontend
-from .plugin import PluginError, _check, _workspace
 
-_DT = {torch.float16: _lib.DT_HALF, torch.float32: _lib.DT_FLOAT}
+_STAGE = "the SuperPoint encoder"
+_HALF = (torch.float16,)
 
 # name -> (cout, cin, kernel), in forward order (superpoint.py:115-130)
 LAYERS = {
@@ -39,10 +40,6 @@ _POOLED = ("conv1b", "conv2b", "conv3b")  # the layers a 2 x 2 max-pool follows
 CONV_CIN = (64, 128)                     # lg_sp_conv3x3's channel counts
 CONV_COUT = (64, 128, 256, 512)
 HEAD_ROWS = 96 + 256                     # lg_sp_heads' weight rows: convPb's 65 padded to 96, then convDb's
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 # ---- packed weights ---------------------------------------------------------------------------------------
@@ -63,18 +60,11 @@ def unpack_conv(p: torch.Tensor, cout: int, cin: int, kh: int, kw: int) -> torch
 
 
 # ---- the four entry points ----------------------------------------------------------------------------------
-def _gpu16(name: str, t: torch.Tensor, dtypes=(torch.float16,)) -> None:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise PluginError(f"{name}: the SuperPoint encoder runs on the GPU only (no CPU fallback)")
-    if t.dtype not in dtypes:
-        raise ValueError(f"{name}: expected {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-
-
 def conv1(image: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool = True,
           out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """lg_sp_conv1: image [B, H, W] (fp16 / fp32), weight [64, 1, 3, 3] and bias [64] fp16 -> [B, H, W, 64] fp16."""
-    _gpu16("image", image, (torch.float16, torch.float32))
-    _gpu16("weight", weight), _gpu16("bias", bias)
+    require_gpu("image", image, _STAGE, tuple(DT))
+    require_gpu("weight", weight, _STAGE, _HALF), require_gpu("bias", bias, _STAGE, _HALF)
     if image.dim() != 3 or tuple(weight.shape) != (64, 1, 3, 3) or tuple(bias.shape) != (64,):
         raise ValueError(f"conv1: expected image [B, H, W], weight [64, 1, 3, 3], bias [64]; got {tuple(image.shape)}, "
                          f"{tuple(weight.shape)}, {tuple(bias.shape)}")
@@ -82,9 +72,8 @@ def conv1(image: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: b
     b, h, w = image.shape
     if out is None:
         out = torch.empty((b, h, w, 64), dtype=torch.float16, device=image.device)
-    st = _lib.load().lg_sp_conv1(_DT[image.dtype], image.data_ptr(), weight.data_ptr(), bias.data_ptr(), h, w, b,
-                                 _lib.SP_RELU if relu else 0, out.data_ptr(), _stream(image))
-    _check(st, "lg_sp_conv1")
+    call("lg_sp_conv1", DT[image.dtype], image.data_ptr(), weight.data_ptr(), bias.data_ptr(), h, w, b,
+         _lib.SP_RELU if relu else 0, out.data_ptr(), stream_of(image))
     return out
 
 
@@ -93,14 +82,13 @@ def conv3x3(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, relu: b
     """lg_sp_conv3x3: x [B, H, W, cin] fp16 contiguous, w_packed = pack_conv(weight [cout, cin, 3, 3]), bias
     [cout] -> [B, H, W, cout], or [B, H / 2, W / 2, cout] with pool (ReLU, then the 2 x 2 maximum)."""
     for name, t in (("x", x), ("w_packed", w_packed), ("bias", bias)):
-        _gpu16(name, t)
+        require_gpu(name, t, _STAGE, _HALF)
     if x.dim() != 4 or bias.dim() != 1 or w_packed.dim() != 1:
         raise ValueError("conv3x3: expected x [B, H, W, cin], a flat w_packed and bias [cout]")
     x, w_packed, bias = x.contiguous(), w_packed.contiguous(), bias.contiguous()
     b, h, w, cin = x.shape
     cout = bias.shape[0]
-    lib = _lib.load()
-    need = lib.lg_sp_packed_bytes(9, cin, cout)
+    need = _lib.load().lg_sp_packed_bytes(9, cin, cout)
     if need == 0 or w_packed.numel() * 2 != need:
         raise ValueError(f"conv3x3: cin {cin} / cout {cout} unsupported, or w_packed has {w_packed.numel()} elements, "
                          f"not {need // 2}")
@@ -110,9 +98,8 @@ def conv3x3(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, relu: b
     if out is None:
         out = torch.empty((b, oh, ow, cout), dtype=torch.float16, device=x.device)
     flags = (_lib.SP_RELU if relu else 0) | (_lib.SP_POOL2 if pool else 0)
-    st = lib.lg_sp_conv3x3(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), cin, cout, h, w, b, flags, out.data_ptr(),
-                           _stream(x))
-    _check(st, "lg_sp_conv3x3")
+    call("lg_sp_conv3x3", x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), cin, cout, h, w, b, flags, out.data_ptr(),
+         stream_of(x))
     return out
 
 
@@ -130,16 +117,15 @@ def heads(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor) -> Tuple[
     """lg_sp_heads: x [B, Hc, Wc, 512] (cPa | cDa) fp16 -> (logits [B, 65, Hc, Wc] contiguous, dense: a
     [B, 256, Hc, Wc] view of the [B, Hc, Wc, 256] tensor the kernel wrote)."""
     for name, t in (("x", x), ("w_packed", w_packed), ("bias", bias)):
-        _gpu16(name, t)
+        require_gpu(name, t, _STAGE, _HALF)
     if x.dim() != 4 or x.shape[3] != 512 or w_packed.numel() != HEAD_ROWS * 256 or tuple(bias.shape) != (HEAD_ROWS,):
         raise ValueError(f"heads: expected x [B, Hc, Wc, 512], pack_heads' weights and bias; got {tuple(x.shape)}")
     x, w_packed, bias = x.contiguous(), w_packed.contiguous(), bias.contiguous()
     b, hc, wc, _ = x.shape
     logits = torch.empty((b, 65, hc, wc), dtype=torch.float16, device=x.device)
     dense = torch.empty((b, hc, wc, 256), dtype=torch.float16, device=x.device)
-    st = _lib.load().lg_sp_heads(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), hc, wc, b, logits.data_ptr(),
-                                 dense.data_ptr(), _stream(x))
-    _check(st, "lg_sp_heads")
+    call("lg_sp_heads", x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), hc, wc, b, logits.data_ptr(), dense.data_ptr(),
+         stream_of(x))
     return logits, dense.permute(0, 3, 1, 2)
 
 
@@ -186,11 +172,10 @@ class SuperPointEncoder:
 
     @staticmethod
     def _image(image: torch.Tensor) -> torch.Tensor:
-        if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise PluginError("SuperPointEncoder runs on the GPU only (no CPU fallback); got a CPU tensor")
+        require_gpu("image", image, _STAGE)
         if image.dim() == 4 and image.shape[1] == 1:
             image = image[:, 0]
-        if image.dim() != 3 or image.dtype not in _DT:
+        if image.dim() != 3 or image.dtype not in DT:
             raise ValueError(f"image: expected [B, 1, H, W] or [B, H, W] in fp16 or fp32, got {tuple(image.shape)} {image.dtype}")
         if image.shape[1] % 8 or image.shape[2] % 8 or image.shape[1] == 0 or image.shape[2] == 0:
             raise ValueError(f"image: H and W must be positive multiples of 8, got {image.shape[1]} x {image.shape[2]}")
@@ -203,13 +188,11 @@ class SuperPointEncoder:
         image = self._image(image)
         b, h, w = image.shape
         p = self._weights(image.device)
-        big = (b * h * w * 64 * 2 + 255) // 256 * 256   # conv1a's output, the largest
-        small = (b * h * w * 16 * 2 + 255) // 256 * 256  # conv1b's pooled output, the largest of the others
-        ws = _workspace(image.device, _stream(image), big + small)
+        # conv1a's output, the largest, and conv1b's pooled output, the largest of the others
+        regions = carve(image.device, stream_of(image), [b * h * w * 64 * 2, b * h * w * 16 * 2])
 
         def buf(which: int, hh: int, ww: int, c: int) -> torch.Tensor:
-            base = ws[:big] if which == 0 else ws[big:big + small]
-            return base[:b * hh * ww * c * 2].view(torch.float16).view(b, hh, ww, c)
+            return regions[which][:b * hh * ww * c * 2].view(torch.float16).view(b, hh, ww, c)
 
         x = conv1(image, *p["conv1a"], out=buf(0, h, w, 64))
         which = 1
@@ -225,17 +208,23 @@ class SuperPointEncoder:
         return frontend.extract(*self.heads(image))
 
 
-def match_images(encoder: SuperPointEncoder, frontend: KeypointFrontend, matcher, images0: torch.Tensor,
-                 images1: torch.Tensor):
-    """The matches of P image pairs (images0[p], images1[p]; both [P, 1, H, W] or [P, H, W], one size): one
-    encoder pass and one extract over the 2 P images, then matcher.match_features on the two halves. Nothing
-    is read back, so the whole enqueues, or is captured, as one piece."""
+def extract_pairs(encoder: SuperPointEncoder, frontend: KeypointFrontend, images0: torch.Tensor,
+                  images1: torch.Tensor) -> Tuple[Features, Features]:
+    """The Features of both sides of P image pairs (images0[p], images1[p]; both [P, 1, H, W] or [P, H, W], one
+    size): one encoder pass and one extract over the 2 P images, then the two halves."""
     if images0.shape != images1.shape or images0.dtype != images1.dtype:
         raise ValueError(f"match_images: the two image batches must agree in shape and dtype, got {tuple(images0.shape)} "
                          f"{images0.dtype} and {tuple(images1.shape)} {images1.dtype}")
     pairs = images0.shape[0]
     f = encoder.extract(torch.cat([images0, images1]), frontend)
-    return matcher.match_features(Features(*(t[:pairs] for t in f)), Features(*(t[pairs:] for t in f)))
+    return f.rows(slice(0, pairs)), f.rows(slice(pairs, None))
+
+
+def match_images(encoder: SuperPointEncoder, frontend: KeypointFrontend, matcher, images0: torch.Tensor,
+                 images1: torch.Tensor):
+    """The matches of P image pairs: matcher.match_features on extract_pairs' two halves. Nothing is read
+    back, so the whole enqueues, or is captured, as one piece."""
+    return matcher.match_features(*extract_pairs(encoder, frontend, images0, images1))
 
 
 # ---- the same forward in framework ops (the tests' oracle) ------------------------------------------------

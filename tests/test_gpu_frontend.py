@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN_DIR
+from gpu_common import capture_on_side_stream, equal_results, same_bits, seeded_matcher
 
 pytestmark = pytest.mark.gpu
 
@@ -41,10 +42,6 @@ def g(request):
 def t(a, dev=None):
     x = torch.from_numpy(np.ascontiguousarray(a))
     return x.to(dev) if dev is not None else x
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
 
 
 # ---- heatmap ------------------------------------------------------------------------------------------
@@ -205,11 +202,7 @@ def test_extract_end_to_end(g, dev):
 
 @pytest.fixture(scope="module")
 def model(dev):
-    from lightglue_amd import matcher
-
-    m = matcher.LightGlueMatcher(n_layers=9).eval()
-    m.load_state_dict(matcher.seeded_state_dict(7, 9), strict=True)
-    return m.to(dev, torch.float16)
+    return seeded_matcher(dev, n_layers=9)
 
 
 def pair_inputs(dev, variant=0):
@@ -223,11 +216,6 @@ def pair_inputs(dev, variant=0):
     da = torch.stack([dn[0], dn[1], dn[0]])
     db = torch.stack([dn[1], dn[0], dn[1]])
     return la.contiguous(), lb.contiguous(), da.contiguous(), db.contiguous()
-
-
-def equal_results(a, b, what):
-    for name, x, y in zip(a._fields, a, b):
-        assert same_bits(x, y), (what, name)
 
 
 def expected_match(model, f0, f1):
@@ -271,15 +259,7 @@ def test_captured_extract_and_match_replays_on_new_logits(model, dev):
         f0, f1 = fe.extract(la, da), fe.extract(lb, db)
         return f0, f1, model.match_features(f0, f1)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.no_grad(), torch.cuda.stream(side):  # warm-up off the capture: caches, workspaces
-        run()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph):
-        c0, c1, captured = run()
+    graph, (c0, c1, captured) = capture_on_side_stream(run, on_side=False)
     with torch.no_grad():
         graph.replay()
         torch.cuda.synchronize()

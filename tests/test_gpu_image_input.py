@@ -16,6 +16,8 @@ import functools
 import pytest
 import torch
 
+from gpu_common import capture_on_side_stream, equal_results, same_bits, seeded_matcher
+
 pytestmark = pytest.mark.gpu
 
 TARGET_PAIRS = (((1, 1), (8, 8)), ((3, 5), (8, 8)), ((37, 53), (16, 24)), ((100, 7), (8, 16)), ((481, 641), (16, 24)),
@@ -28,10 +30,6 @@ DTYPES = (torch.float16, torch.float32)
 def dev():
     assert torch.cuda.is_available(), "the gpu tests need the MI355X"
     return torch.device("cuda:0")
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
 
 
 def rand_u8(seed, *shape, high=256):
@@ -209,16 +207,7 @@ def encoder():
 
 @pytest.fixture(scope="module")
 def model(dev):
-    from lightglue_amd import matcher
-
-    m = matcher.LightGlueMatcher(n_layers=3).eval()
-    m.load_state_dict(matcher.seeded_state_dict(7, 3), strict=True)
-    return m.to(dev, torch.float16)
-
-
-def equal_results(a, b, what):
-    for name, x, y in zip(a._fields, a, b):
-        assert same_bits(x, y), (what, name)
+    return seeded_matcher(dev)
 
 
 TARGET = (40, 72)  # the size tests/test_gpu_superpoint.py's match_images test uses
@@ -280,15 +269,7 @@ def test_captured_source_images_to_matches_replay_on_new_pixels(dev, encoder, mo
         equal_results(x[0], y[0], what)
         assert same_bits(x[1], y[1]) and same_bits(x[2], y[2]), what
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.no_grad(), torch.cuda.stream(side):  # warm-up off the capture: packed weights, workspaces
-        run(t0, t1)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph, stream=side):
-        captured = run(t0, t1)
+    graph, captured = capture_on_side_stream(lambda: run(t0, t1))
     with torch.no_grad():
         graph.replay()
         torch.cuda.synchronize()

@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_common import capture_on_side_stream, equal_results, same_bits, seeded_matcher
+
 pytestmark = pytest.mark.gpu
 
 SIZES = ((1, 1), (3, 5), (8, 8), (9, 17), (18, 34))
@@ -26,10 +28,6 @@ CHANNELS = ((64, 64), (64, 128), (128, 128), (128, 512))
 def dev():
     assert torch.cuda.is_available(), "the gpu tests need the MI355X"
     return torch.device("cuda:0")
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
 
 
 def normal16(seed, shape, std=1.0):
@@ -192,16 +190,7 @@ def test_encoder_within_twice_the_storage_models_error(dev, sd, encoder, h, w, d
 # ---- plumbing, capture, repeatability -------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(dev):
-    from lightglue_amd import matcher
-
-    m = matcher.LightGlueMatcher(n_layers=3).eval()
-    m.load_state_dict(matcher.seeded_state_dict(7, 3), strict=True)
-    return m.to(dev, torch.float16)
-
-
-def equal_results(a, b, what):
-    for name, x, y in zip(a._fields, a, b):
-        assert same_bits(x, y), (what, name)
+    return seeded_matcher(dev)
 
 
 def test_extract_and_match_images_are_their_parts(dev, encoder, model):
@@ -225,6 +214,28 @@ def test_extract_and_match_images_are_their_parts(dev, encoder, model):
         assert same_bits(l0, l1) and same_bits(d0, d1)
 
 
+def test_extract_pairs_is_one_extract_split_in_two(dev, encoder, model):
+    """40 x 72: 5 x 9 cells, a non-square map and a ragged last tile in lg_sp_conv3x3. Both halves equal one
+    extract over the concatenated batch split by hand, bitwise on every field; batches that disagree in shape
+    raise what match_images raises."""
+    from lightglue_amd import Features, KeypointFrontend, extract_pairs, match_images
+
+    fe = KeypointFrontend(max_keypoints=64)
+    i0, i1 = images(21, 2, 40, 72).to(dev), images(22, 2, 40, 72).to(dev)
+    with torch.no_grad():
+        f0, f1 = extract_pairs(encoder, fe, i0, i1)
+        both = fe.extract(*encoder.heads(torch.cat([i0, i1])))
+    assert isinstance(f0, Features) and isinstance(f1, Features) and int(both.counts.min()) > 0
+    equal_results(f0, Features(*(t[:2] for t in both)), "side 0")
+    equal_results(f1, Features(*(t[2:] for t in both)), "side 1")
+    errors = []
+    for fn in (lambda: extract_pairs(encoder, fe, i0, i1[:1]), lambda: match_images(encoder, fe, model, i0, i1[:1])):
+        with pytest.raises(ValueError, match="must agree in shape and dtype") as e:
+            fn()
+        errors.append(str(e.value))
+    assert errors[0] == errors[1]
+
+
 def test_captured_images_to_matches_replays_on_a_new_pair(dev, encoder, model):
     """heads + extract + match_features captured once on a side stream; a second image pair copied into the
     captured input buffers; the replay equals the eager result on that pair bitwise (features and matches) and
@@ -240,15 +251,7 @@ def test_captured_images_to_matches_replays_on_a_new_pair(dev, encoder, model):
         f = fe.extract(*encoder.heads(torch.cat([i0, i1])))
         return f, model.match_features(Features(*(t[:1] for t in f)), Features(*(t[1:] for t in f)))
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.no_grad(), torch.cuda.stream(side):  # warm-up off the capture: packed weights, workspaces
-        run(in0, in1)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph, stream=side):
-        cf, cm = run(in0, in1)
+    graph, (cf, cm) = capture_on_side_stream(lambda: run(in0, in1))
     with torch.no_grad():
         graph.replay()
         torch.cuda.synchronize()
