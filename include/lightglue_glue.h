@@ -69,8 +69,9 @@ int32_t lg_merge_heads_cat(int32_t dtype, const void* x, const void* x0, const v
                            int32_t n1, int32_t pairs, void* out, hipStream_t stream);
 
 /* FFN middle (lightglue.py:101-106): y = GELU(LayerNorm(x) * gamma + beta), exact (erf) GELU,
- * x, y [rows, dim], dim a multiple of 64 and <= 1024; y == x (in place) is allowed: each row is read
- * whole before any of it is written. */
+ * x, y [rows, dim], dim 64, 128, 256, 512 or 1024 (any other: bad parameter); y == x (in place) is
+ * allowed: each row is read whole before any of it is written. Mean and variance in fp32, the variance
+ * from the squares about the mean (two passes over the row in registers) in every form. */
 int32_t lg_layernorm_gelu(int32_t dtype, const void* x, const void* gamma, const void* beta, int32_t rows,
                           int32_t dim, float eps, void* y, hipStream_t stream);
 
@@ -447,7 +448,8 @@ int32_t lg_linear_set_wide(int32_t mode);
 
 /* Test and benchmark hook for lg_linear_cat_ln_gelu's forms: 1 (the default) one launch from a full
  * round of its tiles on, 0 always two launches, 2 always one launch (A/B). The forms agree within fp16
- * rounding, not in every bit (the one-launch variance is two-pass). Returns the previous setting. */
+ * rounding, not in every bit (h rounded once against twice, another summation order). Returns the
+ * previous setting. */
 int32_t lg_linear_set_ln_fused(int32_t on);
 /* Test and benchmark hook for lg_linear_cat_ffn's (and lg_linear_cat_ffn_proj's) forms: 1 (the
  * default) the one-launch form when w_packed is given, its kernel by size (16-row tiles up to 4,096

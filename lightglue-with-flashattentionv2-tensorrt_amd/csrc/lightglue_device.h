@@ -161,12 +161,10 @@ __device__ __forceinline__ float mixn(unsigned h2, float a, float c) {
     else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h2), "v"(a), "v"(c));
     return r;
 }
-// the row sums of one packed pair: s1 += h.lo + h.hi, s2 += h.lo^2 + h.hi^2 (v_dot2_f32_f16: the f16
-// products exact in fp32)
-__device__ __forceinline__ void row_sums2(unsigned h2, float& s1, float& s2) {
+// the row sum of one packed pair: s1 += h.lo + h.hi (v_dot2_f32_f16)
+__device__ __forceinline__ void row_sum2(unsigned h2, float& s1) {
     const f16x2 h = __builtin_bit_cast(f16x2, h2);
     s1 = __builtin_amdgcn_fdot2(h, f16x2{(f16)1.f, (f16)1.f}, s1, false);
-    s2 = __builtin_amdgcn_fdot2(h, h, s2, false);
 }
 template <int HI>
 __device__ __forceinline__ float mixh(float acc, unsigned b2) {

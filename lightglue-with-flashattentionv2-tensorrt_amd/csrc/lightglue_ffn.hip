@@ -20,7 +20,7 @@ namespace {
 // tiles of 64 x 128; K in 32-deep steps through a 3-stage LDS-DMA ring of 40 KiB stages, the A-gather
 // of lg_linear_cat), so the row statistics close inside the workgroup: h = fp16(acc + bias) as the
 // unfused path rounds it, row sums per wave -> LDS -> mean; sums of (h - mean)^2 -> LDS -> variance
-// (two passes over registers: the unfused kernel's E[h^2] - mean^2 cancels less well), then
+// (two passes over registers, as the unfused kernel: E[h^2] - mean^2 cancels in fp32), then
 // GELU(LN(h)) (the erf of A&S 7.1.26, as the unfused fp16 kernel) rounded to fp16, staged and
 // stored as in linear_tile_kernel. bias, gamma and beta sit in LDS for the whole launch.
 // Diagnostic build (-DLG_LN_STAMPS, tools/ln_stamps.py; never shipped): per wave, s_memtime cycles
@@ -276,7 +276,8 @@ constexpr int kFfnOut = 256;  // the FFN's output channels (d)
 // halves the weight bytes per row where there are rows enough for several rounds (its MFMA work,
 // 12 k cycles per SIMD, then matches the stream).
 // Arithmetic: the k16 blocks in the 64 x 64 form's order; h = fp16(acc + b1) in one rounding, the
-// LayerNorm statistics as lg_layernorm_gelu forms them (sum and sum of squares, fixed reduction order),
+// LayerNorm statistics from each wave's (sum, sum of squares about its own mean) of its 64 channels,
+// merged over the 8 waves in a fixed order (ln_merge: no E[h^2] - mean^2 cancellation),
 // normalisation and GELU as linear_ln_kernel, the output fp16(fp16(acc + b2) + x) as lin_val / res_add.
 // phase 3 (lg_linear_cat_ffn_proj): the next attention's projection of the FFN output x'
 enum { E3_NONE = 0, E3_SPLIT2 = 1, E3_QKV = 2, E3_PLAIN = 3 };
@@ -307,6 +308,27 @@ __device__ unsigned long long g_fr_stamps[256 * 8 * 8];
     do {          \
     } while (0)
 #endif
+// The squares of one packed pair about c: q += ((h.lo - c)^2, (h.hi - c)^2), the differences one fp32
+// rounding each (v_fma_mix_f32 reads the halves in place), both squares in one v_pk_fma_f32
+__device__ __forceinline__ void row_dev2(unsigned h2, float c, f32x2& q) {
+    const f32x2 d = f32x2{mixn<0>(h2, 1.f, -c), mixn<1>(h2, 1.f, -c)};
+    q = d * d + q;
+}
+// A row's mean and 1 / sqrt(variance + eps) over its 512 channels from the 8 waves' partials: s[w] the
+// sum of wave w's 64 channels, q[w] their squares about that wave's own mean s[w] / 64. The variance is
+// (sum q + 64 sum (s[w] / 64 - mean)^2) / 512 — the pairwise merge of (mean, M2), every term a square —
+// so a row mean far from zero costs no bits (the one-pass E[h^2] - mean^2 lost log2((mean / sigma)^2)).
+struct RowStats {
+    float mean, rstd;
+};
+__device__ __forceinline__ RowStats ln_merge(f32x4 sa, f32x4 sc, f32x4 qa, f32x4 qc, float eps) {
+    const float mean = (((sa[0] + sa[1]) + (sa[2] + sa[3])) + ((sc[0] + sc[1]) + (sc[2] + sc[3]))) * (1.f / 512);
+    const f32x4 da = sa * (1.f / 64) - mean, dc = sc * (1.f / 64) - mean;
+    const f32x4 ba = da * da, bc = dc * dc;
+    const float within = ((qa[0] + qa[1]) + (qa[2] + qa[3])) + ((qc[0] + qc[1]) + (qc[2] + qc[3]));
+    const float between = ((ba[0] + ba[1]) + (ba[2] + ba[3])) + ((bc[0] + bc[1]) + (bc[2] + bc[3]));
+    return {mean, __builtin_amdgcn_rsqf(fmaf(between, 64.f, within) * (1.f / 512) + eps)};
+}
 template <int MB, int D, int E3, int NB3>
 __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* __restrict__ gamma,
                                                           const f16* __restrict__ beta, float eps,
@@ -490,15 +512,17 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
     // ---- LayerNorm over each row's 512 h values: the wave's 64 are in lanes r and r + 32 ----
     // lane (r, hh): acc[b][mb][4 g + t] = hidden channel 64 w + 32 b + 8 g + 4 hh + t of row 32 mb + r.
     // h = fp16(acc + b1) in one rounding (v_fma_mixlo_f16; the two calls' lin_val rounds through fp32
-    // first: the same value but for a rare double rounding), then the row's sum and sum of squares
-    // in one pass and mean / variance as lg_layernorm_gelu forms them (E[h^2] - mean^2, fp32): one
-    // exchange through LDS (vector issue bounds this phase: ~19 VALU per value, two waves a SIMD)
+    // first: the same value but for a rare double rounding), then the wave's sum of the row's 64
+    // values and their squares about the wave's own mean (a second pass over the packed registers),
+    // merged over the waves by ln_merge: one exchange through LDS (vector issue bounds this phase:
+    // ~20 VALU per value, two waves a SIMD)
     float* const red = (float*)(void*)(smem + kRed);  // [pass][row][wave]
-    float sm[MB], sq[MB];
+    float sm[MB], sq[MB];  // the wave's sum of a row, its squares about sm / 64
     unsigned hp[2][MB][8];  // h as packed fp16 pairs: block b, rows mb, (g, pair u) at 2 g + u
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
-        float s1 = 0.f, s2 = 0.f;
+        float s1 = 0.f;
+        f32x2 s2 = {0.f, 0.f};
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -507,11 +531,17 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     hp[b][mb][2 * g + u] = mixh2(acc[b][mb][4 * g + 2 * u], acc[b][mb][4 * g + 2 * u + 1], b4[u]);
-                    row_sums2(hp[b][mb][2 * g + u], s1, s2);
+                    row_sum2(hp[b][mb][2 * g + u], s1);
                 }
             }
         sm[mb] = s1 + __shfl_xor(s1, 32, 64);
-        sq[mb] = s2 + __shfl_xor(s2, 32, 64);
+        const float c = sm[mb] * (1.f / 64);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) row_dev2(hp[b][mb][i], c, s2);
+        const float sl = s2[0] + s2[1];
+        sq[mb] = sl + __shfl_xor(sl, 32, 64);
     }
     if (hh == 0) {
 #pragma unroll
@@ -522,18 +552,16 @@ __global__ __launch_bounds__(512, 1) void ffn_rows_kernel(LinArgs p, const f16* 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    auto row_sum = [&](int off, int row) {  // the 8 waves' partials of a row, in a fixed order
-        const f32x4 a = *(__attribute__((address_space(3))) f32x4*)(lds + kRed + (off + row * 8) * 4);
-        const f32x4 c = *(__attribute__((address_space(3))) f32x4*)(lds + kRed + (off + row * 8 + 4) * 4);
-        return ((a[0] + a[1]) + (a[2] + a[3])) + ((c[0] + c[1]) + (c[2] + c[3]));
+    auto row_stats = [&](int row) {  // from the 8 waves' partials of a row, in a fixed order
+        auto part = [&](int i) { return *(__attribute__((address_space(3))) f32x4*)(lds + kRed + (i + row * 8) * 4); };
+        return ln_merge(part(0), part(4), part(MT * 8), part(MT * 8 + 4), eps);
     };
     // GELU(LN(h)) -> fp16 into the h tile (unit 8 w + 4 b + g of the row, half hh)
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
         const int row = 32 * mb + r;
-        const float mean = row_sum(0, row) * (1.f / K);
-        const float rstd = __builtin_amdgcn_rsqf(fmaxf(row_sum(MT * 8, row) * (1.f / K) - mean * mean, 0.f) + eps);
-        const float nmr = -mean * rstd;
+        const RowStats st = row_stats(row);
+        const float rstd = st.rstd, nmr = -st.mean * rstd;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -846,9 +874,11 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
     FR_SEG(1);
 
     // ---- LayerNorm: lane (r, q) holds channels 64 w + 16 b + 4 q + t of row r; h = fp16(acc + b1) in
-    // one rounding, the row's sum and sum of squares over the 4 q lanes, then the 8 waves via LDS ----
+    // one rounding, the row's sum over the 4 q lanes, the squares about the wave's own mean over them, then
+    // the 8 waves via LDS (ln_merge) ----
     float* const red = (float*)(void*)(smem + kRed);
-    float s1 = 0.f, s2 = 0.f;
+    float s1 = 0.f;
+    f32x2 sd = {0.f, 0.f};
     unsigned hp[4][2];  // h as packed fp16 pairs: block b, channels 4 q + 2 u, + 1
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -856,7 +886,7 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             hp[b][u] = mixh2(acc[b][2 * u], acc[b][2 * u + 1], b4[u]);
-            row_sums2(hp[b][u], s1, s2);
+            row_sum2(hp[b][u], s1);
         }
     }
     // over the row's 4 lanes (l, l ^ 16, l ^ 32, l ^ 48) by lane-group swaps (VALU, no LDS trip)
@@ -867,22 +897,24 @@ __global__ __launch_bounds__(512, 1) void ffn_rows16_kernel(LinArgs p, const f16
         return __uint_as_float(c[0]) + __uint_as_float(c[1]);
     };
     s1 = xsum(s1);
-    s2 = xsum(s2);
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) row_dev2(hp[b][u], s1 * (1.f / 64), sd);
+    const float s2 = xsum(sd[0] + sd[1]);
     if (q == 0) {
         red[r * 8 + wave] = s1;
         red[MT * 8 + r * 8 + wave] = s2;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    auto row_sum = [&](int off, int row) {  // the 8 waves' partials of a row, in a fixed order
-        const f32x4 a = *(__attribute__((address_space(3))) f32x4*)(lds + kRed + (off + row * 8) * 4);
-        const f32x4 c = *(__attribute__((address_space(3))) f32x4*)(lds + kRed + (off + row * 8 + 4) * 4);
-        return ((a[0] + a[1]) + (a[2] + a[3])) + ((c[0] + c[1]) + (c[2] + c[3]));
+    auto row_stats = [&](int row) {  // from the 8 waves' partials of a row, in a fixed order
+        auto part = [&](int i) { return *(__attribute__((address_space(3))) f32x4*)(lds + kRed + (i + row * 8) * 4); };
+        return ln_merge(part(0), part(4), part(MT * 8), part(MT * 8 + 4), eps);
     };
     {
-        const float mean = row_sum(0, r) * (1.f / K);
-        const float rstd = __builtin_amdgcn_rsqf(fmaxf(row_sum(MT * 8, r) * (1.f / K) - mean * mean, 0.f) + eps);
-        const float nmr = -mean * rstd;
+        const RowStats st = row_stats(r);
+        const float rstd = st.rstd, nmr = -st.mean * rstd;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int n = 64 * wave + 16 * b + 4 * q;

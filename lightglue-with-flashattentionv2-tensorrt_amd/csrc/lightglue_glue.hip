@@ -160,7 +160,8 @@ __global__ __launch_bounds__(256) void ln_gelu_kernel(const T* x, const T* __res
 }
 
 // fp16, dim 512 (the matcher's FFN width): a lane owns 8 contiguous columns (one 16-B load of x,
-// gamma and beta), sum and sum of squares reduced together (fp32, E[x^2] - mean^2).
+// gamma and beta); two passes over the registers as ln_gelu_kernel makes them: the sum, then the sum
+// of (x - mean)^2 (E[x^2] - mean^2 cancels in fp32 once |mean| is a few tens of the spread).
 __global__ __launch_bounds__(256) void ln_gelu_512_f16_kernel(const f16* x, const f16* __restrict__ g,
                                                               const f16* __restrict__ bta, int rows, float eps,
                                                               f16* y) {
@@ -176,19 +177,18 @@ __global__ __launch_bounds__(256) void ln_gelu_512_f16_kernel(const f16* x, cons
     for (int e = 0; e < 8; ++e) {
         v[e] = (float)xv[e];
         s += v[e];
+    }
+    const float mean = wave_sum(s) * (1.f / 512);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        v[e] -= mean;
         q += v[e] * v[e];
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {  // two independent shuffle chains
-        s += __shfl_xor(s, m, 64);
-        q += __shfl_xor(q, m, 64);
-    }
-    const float mean = s * (1.f / 512);
-    const float rstd = rsqrtf(fmaxf(q * (1.f / 512) - mean * mean, 0.f) + eps);
+    const float rstd = rsqrtf(wave_sum(q) * (1.f / 512) + eps);
     f16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
-        const f32x2 t = (f32x2{v[e], v[e + 1]} - mean) * rstd * f32x2{(float)gv[e], (float)gv[e + 1]} +
+        const f32x2 t = f32x2{v[e], v[e + 1]} * rstd * f32x2{(float)gv[e], (float)gv[e + 1]} +
                         f32x2{(float)bv[e], (float)bv[e + 1]};
         const f32x2 gl = gelu_as2(t);
         o[e] = (f16)gl[0];
@@ -632,8 +632,10 @@ int32_t lg_merge_heads_cat(int32_t dtype, const void* x, const void* x0, const v
 
 int32_t lg_layernorm_gelu(int32_t dtype, const void* x, const void* gamma, const void* beta, int32_t rows,
                           int32_t dim, float eps, void* y, hipStream_t stream) {
-    if (bad_dtype(dtype) || rows < 0 || dim <= 0 || dim % 64 != 0 || dim > 1024 || !x || !gamma || !beta || !y)
-        return mha_hd64::report_error(MHA_HD64_STATUS_BAD_PARAM, "lg_layernorm_gelu", "bad arguments");
+    const bool dim_ok = dim == 64 || dim == 128 || dim == 256 || dim == 512 || dim == 1024;  // (the instantiations)
+    if (bad_dtype(dtype) || rows < 0 || !dim_ok || !x || !gamma || !beta || !y)
+        return mha_hd64::report_error(MHA_HD64_STATUS_BAD_PARAM, "lg_layernorm_gelu",
+                                      dim_ok ? "bad arguments" : "dim must be 64, 128, 256, 512 or 1024");
     if (rows == 0) return MHA_HD64_STATUS_SUCCESS;
     const dim3 grid((rows + 3) / 4);
     if (dtype == MHA_HD64_DT_HALF && dim == 512 &&
@@ -654,9 +656,7 @@ int32_t lg_layernorm_gelu(int32_t dtype, const void* x, const void* gamma, const
         break;
     switch (dim / 64) {
         LG_LN(1) LG_LN(2) LG_LN(4) LG_LN(8) LG_LN(16)
-        default:
-            return mha_hd64::report_error(MHA_HD64_STATUS_BAD_PARAM, "lg_layernorm_gelu",
-                                          "dim must be 64, 128, 256, 512 or 1024");
+        default: break;  // (dim_ok above)
     }
 #undef LG_LN
     return launched("lg_layernorm_gelu");

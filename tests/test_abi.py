@@ -544,6 +544,18 @@ def test_ffn_and_form_hooks_validate_before_touching_the_device(lib):
 A = 4096  # a fake 16-B aligned address: never dereferenced on the paths below
 
 
+def test_layernorm_gelu_rejects_dims_without_a_kernel(lib):
+    """lg_layernorm_gelu takes dim 64, 128, 256, 512 and 1024: any other multiple of 64 (192) is a bad
+    parameter, not a silent no-op, with rows or without; the dims it takes pass an empty launch."""
+    for dtype in (0, 1):
+        for rows in (0, 4):
+            assert lib.lg_layernorm_gelu(dtype, A, A, A, rows, 192, 1e-5, A, None) == 1, (dtype, rows)
+        for dim in (0, 32, 2048):
+            assert lib.lg_layernorm_gelu(dtype, A, A, A, 0, dim, 1e-5, A, None) == 1, (dtype, dim)
+        for dim in (64, 128, 256, 512, 1024):
+            assert lib.lg_layernorm_gelu(dtype, A, A, A, 0, dim, 1e-5, A, None) == 0, (dtype, dim)
+
+
 def _rejects(call, bads):
     """Every bad case returns BAD_PARAM (1), on an otherwise empty launch wherever its own arguments
     allow one: the check comes before the empty-launch return, and nothing reaches the device."""

@@ -725,9 +725,11 @@ def _ffn_torch(x, c0, c1, w, b, ln, w2, b2):
 
 
 # |ffn_rows_kernel - two calls|: h before the LayerNorm is bitwise the two-call path's; the statistics
-# are two-pass where lg_layernorm_gelu takes E[h^2] - mean^2, so a GELU output can move by one fp16 ulp,
-# and with it the rounding of v = fp16(W2 g + b2) and of x + v. Bound: 2 ulp of the larger of |out|
-# and |v| = |out - x| (and 2^-11 near 0).
+# differ in the order of their fp32 sums only (lg_layernorm_gelu: two passes over the row in one wave;
+# the rows kernels: each wave's sum and squares about its own mean, merged over 8 waves; neither forms
+# E[h^2] - mean^2), so a GELU output can move by one fp16 ulp, and with it the rounding of
+# v = fp16(W2 g + b2) and of x + v. Bound: 2 ulp of the larger of |out| and |v| = |out - x| (and 2^-11
+# near 0).
 def _ulp_bound(out, x, k=2.0):
     mag = torch.maximum(out.float().abs(), (out.float() - x.float()).abs())
     return k * torch.clamp(mag, min=2.0 ** -2) * 2.0 ** -10
