@@ -159,7 +159,12 @@ int32_t lg_linear_split2(const void* x, const void* w, const void* bias, int32_t
 /* sigmoid_log_double_softmax (lightglue.py:197-205), fp32: scores[i][j] = 2 sim[i][j]
  * - logsumexp_j' sim[i][j'] - logsumexp_i' sim[i'][j] + logsigmoid(z0[i]) + logsigmoid(z1[j]).
  * sim, scores [batch, m, n]; z0 [batch, m], z1 [batch, n] (batch image pairs, one launch);
- * workspace >= lg_log_double_softmax_workspace(m, n, batch) bytes. */
+ * workspace >= lg_log_double_softmax_workspace(m, n, batch) bytes.
+ * Non-finite operands follow IEEE arithmetic on the formula above: a -inf entry of sim adds 0 to its row's and its
+ * column's sum and is -inf itself (a row or column of -inf only is outside the contract); a NaN entry makes every
+ * score of its row and of its column NaN, and a NaN z its row (column); a finite z of any magnitude gives the
+ * log-sigmoid's limit (0 / z) without overflow.
+ * (tests/test_gpu_assignment.py holds both this entry point and the fp16 one below to that.) */
 size_t lg_log_double_softmax_workspace(int32_t m, int32_t n, int32_t batch);
 int32_t lg_log_double_softmax(const float* sim, const float* z0, const float* z1, int32_t m, int32_t n, int32_t batch,
                               float* scores, void* workspace, hipStream_t stream);
@@ -168,7 +173,8 @@ int32_t lg_log_double_softmax(const float* sim, const float* z0, const float* z1
  * n <= 2048) read directly, the matchability logits fp16 and strided — z0 of pair p, row i at
  * z0[p * z_pair_stride + i * z_row_stride], z1 of pair p, column j at z1[p * z_pair_stride + j *
  * z_row_stride] (one channel of the final projection's output) — scores fp32 (16-B aligned). Two
- * launches; workspace >= lg_log_double_softmax_f16_workspace(m, n, batch) bytes. */
+ * launches; workspace >= lg_log_double_softmax_f16_workspace(m, n, batch) bytes. Non-finite operands: as
+ * lg_log_double_softmax. */
 size_t lg_log_double_softmax_f16_workspace(int32_t m, int32_t n, int32_t batch);
 int32_t lg_log_double_softmax_f16(const void* sim, const void* z0, const void* z1, int64_t z_pair_stride,
                                   int64_t z_row_stride, int32_t m, int32_t n, int32_t batch, float* scores,
@@ -184,7 +190,11 @@ int32_t lg_log_double_softmax_f16(const void* sim, const void* z0, const void* z
  * workgroup owns 32 rows of one image), then the combine, which closes its rows' and columns'
  * logsumexps from those partials.
  * m, n <= 2048, n % 8 == 0, ld % 8 == 0; v, scores, workspace 16-B aligned; workspace >=
- * lg_assign_scores_workspace(m, n, batch) bytes (its first batch * m * n * 2 bytes: sim, fp16). */
+ * lg_assign_scores_workspace(m, n, batch) bytes (its first batch * m * n * 2 bytes: sim, fp16).
+ * Operands are assumed finite (the file is built without NaN semantics: -fno-honor-nans). What the tests pin beyond
+ * that: matchability logits up to +-65504 give the exact log-sigmoid (0 / z); a row of v that is NaN in every
+ * channel gives NaN in every score of its row and, where its share of the other image's split holds a finite row as
+ * well (always, below 257 rows), of every column; a similarity that overflows fp16 is outside the contract. */
 size_t lg_assign_scores_workspace(int32_t m, int32_t n, int32_t batch);
 int32_t lg_assign_scores(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
                          float* scores, void* workspace, hipStream_t stream);

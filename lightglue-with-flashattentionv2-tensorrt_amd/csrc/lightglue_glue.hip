@@ -2,6 +2,7 @@
 //
 // Memory-bound layout/normalisation kernels: one pass over the data each, 16-B accesses where the
 // layout allows, one wave64 per row for row statistics (shuffle-xor reductions), fp32 math.
+#include <float.h>
 #include <math.h>
 
 #include "lightglue_device.h"  // (f16, kD, gelu_as2, launched)
@@ -246,7 +247,10 @@ __global__ __launch_bounds__(256) void lse_kernel(const float* __restrict__ sim,
     const int chunk = b / cgroups, col = (b % cgroups) * 64 + (threadIdx.x & 63);
     const int r4 = threadIdx.x >> 6;
     const int i0 = chunk * kColChunk, i1 = min(m, i0 + kColChunk);
-    float mx = -INFINITY, s = 0.f;
+    // The running max starts at -FLT_MAX, not -inf: a leading -inf element then adds exp(-inf) = 0 (from -inf it added
+    // exp(-inf - -inf) = NaN to the whole column), a walk of NaN only ends as (-FLT_MAX, NaN), which no merge skips as
+    // empty, and a first finite element still rescales a sum of 0 by exp(-inf) = 0: the same bits as before.
+    float mx = -FLT_MAX, s = 0.f;
     if (col < n) {
 #pragma unroll 4
         for (int i = i0 + r4; i < i1; i += 4) {
@@ -346,7 +350,7 @@ __global__ __launch_bounds__(64 * W) void lse16_kernel(DsArgs a) {
 #pragma unroll
     for (int c = 0; c < CPL; ++c)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) cm[c][e] = -INFINITY, cs[c][e] = 0.f;
+        for (int e = 0; e < 8; ++e) cm[c][e] = -FLT_MAX, cs[c][e] = 0.f;  // (-FLT_MAX: as lse_kernel's walk)
     const int r0 = (rb * W + wave) * kDsBatch;
     const int r1 = min(r0 + kDsBatch, a.m);
     for (int i0 = r0; i0 < r1; i0 += kDsBatch) {
@@ -391,21 +395,23 @@ __global__ __launch_bounds__(64 * W) void lse16_kernel(DsArgs a) {
                 if (lane == b) l = mx[b] + __logf(s[b]);
             if (i0 + lane < r1) a.lse_row[(size_t)p * a.m + i0 + lane] = l;
         }
-        // per column: the batch's max, then one exponential per element
+        // per column: the batch's max, then one exponential per element. (fmaxf drops a NaN, the sum keeps it: a batch
+        // of NaN and -inf only ends as (-FLT_MAX, NaN), which lse_merge does not skip.)
 #pragma unroll
-        for (int c = 0; c < CPL; ++c)
+        for (int c = 0; c < CPL; ++c) {
+            if ((c * 64 + lane) * 8 >= a.n) continue;  // (columns past n)
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float bm = (float)x[0][c][e];
 #pragma unroll
                 for (int b = 1; b < kDsBatch; ++b) bm = fmaxf(bm, (float)x[b][c][e]);
                 const float nm = fmaxf(cm[c][e], bm);
-                if (nm == -INFINITY) continue;  // (columns past n)
                 float t = cs[c][e] * __expf(cm[c][e] - nm);
 #pragma unroll
                 for (int b = 0; b < kDsBatch; ++b) t += __expf((float)x[b][c][e] - nm);
                 cm[c][e] = nm, cs[c][e] = t;
             }
+        }
     }
     // the waves' column partials -> one per (block, column)
     __shared__ float2 part[W][64 * 8];

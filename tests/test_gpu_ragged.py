@@ -9,7 +9,9 @@ the form without; a uniform count equals the same call on the truncated tensors)
 (NaN in every padded row changes no bit of any valid result).
 
 Bounds: attention, tests/test_gpu_stream.py's TOL / TOL_F32OUT (the project's contract); the scores,
-test_assign_scores_kernel's 2e-5 * scale * 4 against the restatement on the kernel's own similarity;
+test_assign_scores_kernel's 2e-5 * scale * 4 against the restatement on the kernel's own similarity (empirical;
+tests/test_gpu_assignment.py holds both _lens heads to a float64 reference under the derived bound of
+tests/assignment_refs.py);
 the matches, tests/test_gpu_match_head.py's _check (indices, counts and padding exact, non-zero
 scores within 2^-22 (4 + |s|) relative, at most 0.5 % of rows in the threshold's band) applied to the
 scores lg_assign_scores_lens wrote for the same input; the matcher, BATCHED_VS_SINGLE["float16"] and
