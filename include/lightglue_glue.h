@@ -439,6 +439,69 @@ int32_t lg_img_prepare_batch(const void* data, int32_t batch, int32_t h, int32_t
 int32_t lg_kp_to_source(const int32_t* kpts_px, const int32_t* counts, const int32_t* src_sizes, int32_t ht, int32_t wt,
                         int32_t batch, int32_t k, float* out, hipStream_t stream);
 
+/* ---- geometric verification (csrc/lightglue_geometry.hip) ----
+ * What the reference's demo does on the host after PostProcess (demo/demo_mono.cpp:326-366):
+ * cv::findFundamentalMat(points0, points1, cv::FM_RANSAC, 3, 0.99, inliers), here per pair of a batch on the
+ * device, from the matcher's outputs as they are. New symbols only: LG_GLUE_ABI_VERSION stays 4. Every call
+ * checks its arguments before any device call, runs on `stream`, is a no-op for pairs == 0, keeps no state, uses
+ * no atomics and allocates nothing; no workgroup reads what another wrote within a launch; every output entry is
+ * written on every call. lightglue_amd/geometry.py restates the contract in float64 (ransac_reference).
+ *
+ * Inputs (shared by the four calls): matches [pairs, kmax, 2] int32 and counts [pairs] int32 (MatchResult's),
+ * kpts0 [pairs, k0, 2], kpts1 [pairs, k1, 2] fp32 (x, y) in any pixel frame (lg_kp_to_source's output is the
+ * intended one). Correspondence k < counts[p] of pair p is (kpts0[p, matches[p, k, 0]], kpts1[p, matches[p, k, 1]]);
+ * counts are clamped into [0, kmax] and indices into range, neither is trusted. 1 <= kmax <= 2048, k0, k1 >= 1,
+ * pairs <= 65,535, pairs * kmax, pairs * k0, pairs * k1 <= 2^28; matches, kpts0, kpts1 8-B aligned, every other
+ * pointer 4-B.
+ *
+ * Model: x1ᵀ F x0 = 0 with x = (x, y, 1), F row-major. Error of a correspondence (OpenCV's for FM_RANSAC):
+ * l1 = F x0, l0 = Fᵀ x1, d = x1 · l1, err = max(d² / (l1x² + l1y²), d² / (l0x² + l0y²)); an inlier iff
+ * err <= threshold² (a non-finite err is none). Per pair, independently:
+ *   1. Hartley normalisation per image over all `count` correspondences (centroid to 0, mean distance sqrt 2;
+ *      sums in fp64 in a fixed order).
+ *   2. Hypothesis h samples 7 distinct indices: draw j = hash32(seed, h, j) % (count - j), moved past the earlier
+ *      draws in ascending order (ransac_samples in geometry.py is the definition; the pair is not in the key).
+ *   3. The 7-point solve in normalised coordinates, fp64 (an fp32 solve leaves its own sample points up to 0.5 px
+ *      off their lines): Gauss-Jordan with row pivoting on the 7 x 9 system (a pivot below 1e-6: no
+ *      candidate), the canonical null vectors f1 = (.., 1, 0), f2 = (.., 0, 1), the real roots l of
+ *      det(l f1 + (1 - l) f2) = 0 in ascending order, each candidate de-normalised to pixels at unit Frobenius
+ *      norm and rounded to fp32 (a non-finite one is dropped): 0 to 3 candidates.
+ *   4. Every candidate is scored against all correspondences in pixels, fp32. The winner: the highest inlier
+ *      count, then the lowest hypothesis, then the lowest root.
+ *   5. `refits` rounds of a normalised 8-point least squares over the current inliers in fp64 (Hartley over the
+ *      inliers, the eigenvector of the smallest eigenvalue of the 9 x 9 normal matrix by Jacobi, rank 2 by
+ *      F <- F (I - v vᵀ) with v the smallest right-singular direction), then the inliers again. A round with fewer
+ *      than 8 inliers, or a refit that is not finite, keeps the previous F and mask.
+ * A pair with count < 8, with no candidate or with a winner of fewer than 8 inliers: valid = 0, F = 0, no inlier,
+ * best = -1. The number of hypotheses is fixed (no early termination by a confidence): the launches do not
+ * depend on the data and a call can be captured. */
+/* Bytes of lg_ransac_fundamental's workspace (0 for an empty call). */
+size_t lg_ransac_workspace(int32_t pairs, int32_t kmax, int32_t hypotheses);
+/* lg_ransac_fundamental: two launches (hypotheses: grid (hypotheses / 64, pairs), four lanes per hypothesis over
+ * the pair's correspondences in LDS; then one workgroup per pair: winner, refits, outputs). threshold in (0, 1e6]
+ * pixels, 1 <= hypotheses <= 4096, 0 <= refits <= 8, any seed; workspace 16-B aligned, at least
+ * lg_ransac_workspace bytes. Outputs: f [pairs, 3, 3] fp32 (unit Frobenius norm, the entry of the largest
+ * magnitude positive, the lowest index among equals), inliers [pairs, kmax] uint8 (aligned with the rows of
+ * matches, 0 past the count), num_inliers, valid, best [pairs] int32 (best: the winning hypothesis or -1). */
+int32_t lg_ransac_fundamental(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                              int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold, int32_t hypotheses,
+                              int32_t refits, int32_t seed, void* workspace, size_t workspace_bytes, float* f,
+                              uint8_t* inliers, int32_t* num_inliers, int32_t* valid, int32_t* best, hipStream_t stream);
+/* Stage hooks over the same device code (tests). lg_ransac_samples: step 2 for one count in [7, 2048] ->
+ * samples [hypotheses, 7] int32 in draw order. */
+int32_t lg_ransac_samples(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream);
+/* lg_ransac_solve7: steps 1 and 3 on given samples [hypotheses, 7] int32 (device; clamped into [0, count), shared
+ * by the pairs) -> candidates [pairs, hypotheses, 3, 9] fp32 (those that exist first, the rest zeros) and
+ * num_roots [pairs, hypotheses] int32. A pair with count < 8: zeros. */
+int32_t lg_ransac_solve7(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                         int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses, float* candidates,
+                         int32_t* num_roots, hipStream_t stream);
+/* lg_ransac_score: step 4's count for given candidates [pairs, num_candidates, 9] fp32 (1 <= num_candidates <=
+ * 4096) -> inlier_counts [pairs, num_candidates] int32. */
+int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                        int32_t kmax, int32_t k0, int32_t k1, const float* candidates, int32_t num_candidates, float threshold,
+                        int32_t* inlier_counts, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

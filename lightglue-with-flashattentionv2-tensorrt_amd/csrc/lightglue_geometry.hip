@@ -1,0 +1,420 @@
+// lightglue_geometry.hip — geometric verification (include/lightglue_glue.h, "geometric verification"): a
+// fundamental matrix per image pair by RANSAC over the matcher's matches, what the reference's demo does on the
+// host with cv::findFundamentalMat(points0, points1, cv::FM_RANSAC, 3, 0.99, inliers) after PostProcess
+// (demo/demo_mono.cpp:326-366). The contract is restated in float64 in lightglue_amd/geometry.py.
+//
+// Two launches. ransac_hypothesis_kernel: grid (hypothesis blocks, pairs), 64 hypotheses a workgroup; the
+// workgroup gathers the pair's correspondences into LDS once (2048 x 16 B) and computes the Hartley
+// normalisation; then a lane is a hypothesis: it hashes its 7 indices, solves the 7-point system in registers in
+// fp64 (selects, no run-time register index) and counts the inliers of its up-to-3 candidates in one pass over the
+// LDS copy. Four adjacent lanes share a hypothesis: they solve it alike (the wave executes the statements once
+// either way) and each takes every fourth correspondence of the pass, the four integer counts added across the
+// lanes. (F, count, root) of the best candidate goes to the workspace.
+// ransac_finalize_kernel: one workgroup per pair reduces the hypotheses to the winner in index order, marks its
+// inliers, runs the refits in fp64 (normal matrix, a round-robin Jacobi on the 9 x 9, rank 2, de-normalise) and
+// writes every output. No atomics, no allocation, no host synchronisation; no workgroup reads what another
+// wrote within a launch. The arithmetic is in lightglue_geometry_math.h.
+#include "lightglue_device.h"
+#include "lightglue_geometry_math.h"
+
+namespace {
+
+using namespace lg_geom;
+
+constexpr int kHypLanes = 64;    // hypotheses a workgroup
+constexpr int kHypSplit = 4;     // adjacent lanes that share a hypothesis' scoring pass (every fourth correspondence each)
+constexpr int kHypThreads = kHypLanes * kHypSplit;
+constexpr int kFinThreads = 256;
+constexpr int kHypRecord = 12;   // floats per hypothesis in the workspace: F[9], count, root, pad
+
+struct PairArgs {
+    const int32_t* matches;  // [pairs, kmax, 2]
+    const int32_t* counts;   // [pairs]
+    const float* kpts0;      // [pairs, k0, 2]
+    const float* kpts1;      // [pairs, k1, 2]
+    int kmax, k0, k1;
+};
+
+__device__ __forceinline__ int pair_count(const PairArgs& a, int p) { return min(max(a.counts[p], 0), a.kmax); }
+
+// The pair's correspondences (x0, y0, x1, y1) into LDS, indices clamped into range.
+__device__ __forceinline__ void stage_pair(const PairArgs& a, int p, int count, float4* pts, int tid, int nthreads) {
+    for (int k = tid; k < count; k += nthreads) {
+        const size_t m = ((size_t)p * a.kmax + k) * 2;
+        const int i0 = min(max(a.matches[m], 0), a.k0 - 1), i1 = min(max(a.matches[m + 1], 0), a.k1 - 1);
+        const float2 u = *reinterpret_cast<const float2*>(a.kpts0 + ((size_t)p * a.k0 + i0) * 2);
+        const float2 v = *reinterpret_cast<const float2*>(a.kpts1 + ((size_t)p * a.k1 + i1) * 2);
+        pts[k] = make_float4(u.x, u.y, v.x, v.y);
+    }
+}
+
+// The sum over the workgroup of one double per thread, in a fixed order (a tree over the thread index); every
+// thread gets it. buf: NT doubles.
+template <int NT>
+__device__ __forceinline__ double block_sum(double v, double* buf, int tid) {
+    __syncthreads();
+    buf[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s) buf[tid] += buf[tid + s];
+        __syncthreads();
+    }
+    return buf[0];
+}
+
+// Hartley normalisation over the correspondences k < count with use[k] != 0 (use == nullptr: all): centroid
+// and sqrt(2) / mean distance per image, each thread's share summed in ascending k, the shares by block_sum.
+// n: the number of correspondences used (> 0).
+template <int NT>
+__device__ __forceinline__ void hartley(const float4* pts, const uint8_t* use, int count, double n, double* buf, int tid,
+                                        double c[4], double s[2]) {
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = tid; k < count; k += NT) {
+        if (use && !use[k]) continue;
+        const float4 q = pts[k];
+        sum[0] += (double)q.x, sum[1] += (double)q.y, sum[2] += (double)q.z, sum[3] += (double)q.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = block_sum<NT>(sum[i], buf, tid) / n;
+    double dist[2] = {0.0, 0.0};
+    for (int k = tid; k < count; k += NT) {
+        if (use && !use[k]) continue;
+        const float4 q = pts[k];
+        const double ax = (double)q.x - c[0], ay = (double)q.y - c[1], bx = (double)q.z - c[2], by = (double)q.w - c[3];
+        dist[0] += sqrt(ax * ax + ay * ay), dist[1] += sqrt(bx * bx + by * by);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) s[i] = 1.4142135623730951 / (block_sum<NT>(dist[i], buf, tid) / n);
+}
+
+// GIVEN: the samples are an input and every candidate an output (lg_ransac_solve7); else the samples are
+// hashed and the best candidate's record goes to the workspace.
+template <bool GIVEN>
+__global__ __launch_bounds__(kHypThreads) void ransac_hypothesis_kernel(PairArgs a, int hypotheses, uint32_t seed, float thr2,
+                                                                         const int32_t* __restrict__ samples,
+                                                                         float* __restrict__ hyp, float* __restrict__ cand_out,
+                                                                         int32_t* __restrict__ nroots_out) {
+    __shared__ float4 pts[kMaxPoints];
+    __shared__ double buf[kHypThreads];
+    const int p = blockIdx.y, tid = threadIdx.x, sub = tid % kHypSplit;
+    const int h = blockIdx.x * kHypLanes + tid / kHypSplit;
+    const bool live = h < hypotheses;
+    const int count = pair_count(a, p);
+    float cand[3][9];
+    int nc = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) cand[i][k] = 0.f;
+    if (count >= kMinInliers) {  // (the same for the whole workgroup)
+        stage_pair(a, p, count, pts, tid, kHypThreads);
+        double c[4], s[2];
+        hartley<kHypThreads>(pts, nullptr, count, (double)count, buf, tid, c, s);
+        const NormT<double> t{c[0], c[1], s[0], c[2], c[3], s[1]};
+        if (live) {  // (the lanes of a hypothesis solve it alike: the same statements on the same values)
+            int idx[7];
+            if constexpr (GIVEN) {
+#pragma unroll
+                for (int j = 0; j < 7; ++j) idx[j] = min(max(samples[(size_t)h * 7 + j], 0), count - 1);
+            } else {
+                sample7(seed, h, count, idx);
+            }
+            double x0[7], y0[7], x1[7], y1[7];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                const float4 q = pts[idx[j]];
+                x0[j] = ((double)q.x - t.cx0) * t.s0, y0[j] = ((double)q.y - t.cy0) * t.s0;
+                x1[j] = ((double)q.z - t.cx1) * t.s1, y1[j] = ((double)q.w - t.cy1) * t.s1;
+            }
+            nc = solve7(x0, y0, x1, y1, t, cand);
+        }
+    }
+    if constexpr (GIVEN) {
+        if (!live || sub != 0) return;
+        float* out = cand_out + ((size_t)p * hypotheses + h) * 27;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) out[9 * i + k] = cand[i][k];
+        nroots_out[(size_t)p * hypotheses + h] = nc;
+    } else {
+        int n0 = 0, n1 = 0, n2 = 0;
+        if (nc > 0) {
+#pragma unroll 2
+            for (int k = sub; k < count; k += kHypSplit) {
+                const float4 q = pts[k];
+                n0 += is_inlier(cand[0], q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+                n1 += is_inlier(cand[1], q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+                n2 += is_inlier(cand[2], q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+            }
+        }
+#pragma unroll
+        for (int d = 1; d < kHypSplit; d <<= 1) {  // (integers: the order of the sum does not matter)
+            n0 += __shfl_xor(n0, d), n1 += __shfl_xor(n1, d), n2 += __shfl_xor(n2, d);
+        }
+        if (!live || sub != 0) return;
+        // the highest count, the lowest root among equals (a zero candidate counts nothing)
+        const int root = n2 > max(n0, n1) ? 2 : (n1 > n0 ? 1 : 0);
+        const int best = max(n0, max(n1, n2));
+        float* rec = hyp + ((size_t)p * hypotheses + h) * kHypRecord;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) rec[k] = root == 2 ? cand[2][k] : (root == 1 ? cand[1][k] : cand[0][k]);
+        rec[9] = __int_as_float(best), rec[10] = __int_as_float(root), rec[11] = 0.f;
+    }
+}
+
+// lg_ransac_score: a lane is one given candidate.
+__global__ __launch_bounds__(kHypLanes) void ransac_score_kernel(PairArgs a, const float* __restrict__ cands, int ncand,
+                                                                  float thr2, int32_t* __restrict__ out) {
+    __shared__ float4 pts[kMaxPoints];
+    const int p = blockIdx.y, lane = threadIdx.x, c = blockIdx.x * kHypLanes + lane;
+    const int count = pair_count(a, p);
+    stage_pair(a, p, count, pts, lane, kHypLanes);
+    __syncthreads();
+    if (c >= ncand) return;
+    float f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = cands[((size_t)p * ncand + c) * 9 + k];
+    int n = 0;
+    for (int k = 0; k < count; ++k) {
+        const float4 q = pts[k];
+        n += is_inlier(f, q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+    }
+    out[(size_t)p * ncand + c] = n;
+}
+
+__global__ __launch_bounds__(kHypLanes) void ransac_samples_kernel(int count, int hypotheses, uint32_t seed,
+                                                                    int32_t* __restrict__ out) {
+    const int h = blockIdx.x * kHypLanes + threadIdx.x;
+    if (h >= hypotheses) return;
+    int idx[7];
+    sample7(seed, h, count, idx);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) out[(size_t)h * 7 + j] = idx[j];
+}
+
+__global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a, int hypotheses, int refits, float thr2,
+                                                                       const float* __restrict__ hyp, float* __restrict__ f_out,
+                                                                       uint8_t* __restrict__ inl_out,
+                                                                       int32_t* __restrict__ num_out,
+                                                                       int32_t* __restrict__ valid_out,
+                                                                       int32_t* __restrict__ best_out) {
+    __shared__ float4 pts[kMaxPoints];
+    __shared__ uint8_t mask[kMaxPoints];
+    __shared__ double buf[kFinThreads];
+    __shared__ int best_c[kFinThreads], best_h[kFinThreads];
+    __shared__ double part[kFinThreads / 64][45];
+    __shared__ double am[81], vm[81];  // the normal matrix and the eigenvectors (columns), row-major 9 x 9
+    __shared__ double rot[4][2];
+    __shared__ double fnew[9];
+    __shared__ int fnew_ok;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int count = pair_count(a, p);
+
+    // the winner: the highest count, the lowest hypothesis among equals
+    int bc = -1, bh = 0x7fffffff;
+    for (int h = tid; h < hypotheses; h += kFinThreads) {
+        const int c = __float_as_int(hyp[((size_t)p * hypotheses + h) * kHypRecord + 9]);
+        if (c > bc) bc = c, bh = h;
+    }
+    best_c[tid] = bc, best_h[tid] = bh;
+    __syncthreads();
+#pragma unroll
+    for (int s = kFinThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            const int oc = best_c[tid + s], oh = best_h[tid + s];
+            if (oc > best_c[tid] || (oc == best_c[tid] && oh < best_h[tid])) best_c[tid] = oc, best_h[tid] = oh;
+        }
+        __syncthreads();
+    }
+    bc = best_c[0], bh = best_h[0];
+    const bool valid = count >= kMinInliers && bc >= kMinInliers;  // (the same for the whole workgroup)
+
+    float f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = 0.f;
+    int num = 0;
+    if (valid) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = hyp[((size_t)p * hypotheses + bh) * kHypRecord + k];
+        stage_pair(a, p, count, pts, tid, kFinThreads);
+        __syncthreads();
+        for (int round = 0;; ++round) {
+            int mine = 0;
+            for (int k = tid; k < count; k += kFinThreads) {
+                const float4 q = pts[k];
+                const bool in = is_inlier(f, q.x, q.y, q.z, q.w, thr2);
+                mask[k] = in ? 1 : 0;
+                mine += in ? 1 : 0;
+            }
+            num = (int)block_sum<kFinThreads>((double)mine, buf, tid);  // (exact: integers below 2^53)
+            if (round >= refits || num < kMinInliers) break;
+            // normalised 8-point least squares over the inliers
+            double c[4], s[2];
+            hartley<kFinThreads>(pts, mask, count, (double)num, buf, tid, c, s);
+            {   // the upper triangle of the normal matrix: a thread sums its inliers (every 256th from tid on, in
+                // ascending order) into 45 registers, a wave adds its lanes in a tree, the four waves in order
+                double acc[45];
+#pragma unroll
+                for (int e = 0; e < 45; ++e) acc[e] = 0.0;
+                for (int k = tid; k < count; k += kFinThreads) {
+                    if (!mask[k]) continue;
+                    const float4 q = pts[k];
+                    const double x0 = ((double)q.x - c[0]) * s[0], y0 = ((double)q.y - c[1]) * s[0];
+                    const double x1 = ((double)q.z - c[2]) * s[1], y1 = ((double)q.w - c[3]) * s[1];
+                    const double row[9] = {x1 * x0, x1 * y0, x1, y1 * x0, y1 * y0, y1, x0, y0, 1.0};
+                    int e = 0;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i)
+#pragma unroll
+                        for (int j = i; j < 9; ++j) acc[e] = fma(row[i], row[j], acc[e]), ++e;
+                }
+#pragma unroll
+                for (int e = 0; e < 45; ++e) {
+                    double v = acc[e];
+#pragma unroll
+                    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+                    if (tid % 64 == 0) part[tid / 64][e] = v;
+                }
+            }
+            __syncthreads();
+            if (tid < 45) {
+                int i, j;
+                tri_index(tid, i, j);
+                const double v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+                am[9 * i + j] = v, am[9 * j + i] = v;
+            }
+            if (tid < 81) vm[tid] = tid / 9 == tid % 9 ? 1.0 : 0.0;
+            __syncthreads();
+            // Jacobi: 4 disjoint rotations a step; A <- Jᵀ A J, V <- V J
+#pragma unroll 1
+            for (int step = 0; step < 9 * kJacobiSweeps; ++step) {
+                if (tid < 4) {
+                    int pp, qq;
+                    jacobi_pair(step, tid, pp, qq);
+                    double cc, ss;
+                    jacobi_cs(am[9 * pp + pp], am[9 * qq + qq], am[9 * pp + qq], cc, ss);
+                    rot[tid][0] = cc, rot[tid][1] = ss;
+                }
+                __syncthreads();
+                if (tid < 72) {  // columns p, q of row k of A and of V
+                    const int g = tid / 18, w = tid % 18, k = w % 9;
+                    double* m = w < 9 ? am : vm;
+                    int pp, qq;
+                    jacobi_pair(step, g, pp, qq);
+                    const double cc = rot[g][0], ss = rot[g][1];
+                    const double mp = m[9 * k + pp], mq = m[9 * k + qq];
+                    m[9 * k + pp] = cc * mp - ss * mq, m[9 * k + qq] = ss * mp + cc * mq;
+                }
+                __syncthreads();
+                if (tid < 36) {  // rows p, q of column k of A
+                    const int g = tid / 9, k = tid % 9;
+                    int pp, qq;
+                    jacobi_pair(step, g, pp, qq);
+                    const double cc = rot[g][0], ss = rot[g][1];
+                    const double mp = am[9 * pp + k], mq = am[9 * qq + k];
+                    am[9 * pp + k] = cc * mp - ss * mq, am[9 * qq + k] = ss * mp + cc * mq;
+                }
+                __syncthreads();
+            }
+            if (tid == 0) {
+                int lo = 0;
+                for (int k = 1; k < 9; ++k) lo = am[10 * k] < am[10 * lo] ? k : lo;
+                double fn[9], fd[9];
+                for (int k = 0; k < 9; ++k) fn[k] = vm[9 * k + lo];
+                rank2(fn);
+                fnew_ok = denormalise64(fn, c[0], c[1], s[0], c[2], c[3], s[1], fd) ? 1 : 0;
+                for (int k = 0; k < 9; ++k) fnew[k] = fd[k];
+            }
+            __syncthreads();
+            if (!fnew_ok) break;  // a refit that is not finite keeps the previous F and mask
+#pragma unroll
+            for (int k = 0; k < 9; ++k) f[k] = (float)fnew[k];
+            __syncthreads();
+        }
+        fix_sign(f);
+    }
+    if (tid < 9) f_out[(size_t)p * 9 + tid] = f[tid];
+    for (int k = tid; k < a.kmax; k += kFinThreads) inl_out[(size_t)p * a.kmax + k] = valid && k < count ? mask[k] : 0;
+    if (tid == 0) num_out[p] = valid ? num : 0, valid_out[p] = valid ? 1 : 0, best_out[p] = valid ? bh : -1;
+}
+
+bool pair_args_ok(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                  int32_t kmax, int32_t k0, int32_t k1) {
+    const int64_t lim = 1 << 28;
+    return pairs >= 0 && pairs <= 65535 && kmax >= 1 && kmax <= kMaxPoints && k0 >= 1 && k1 >= 1 &&
+           (int64_t)pairs * kmax <= lim && (int64_t)pairs * k0 <= lim && (int64_t)pairs * k1 <= lim && matches && counts &&
+           kpts0 && kpts1 && aligned8(matches) && aligned4(counts) && aligned8(kpts0) && aligned8(kpts1);
+}
+bool threshold_ok(float t) { return t > 0.f && t <= 1e6f; }  // (NaN fails; t² stays finite)
+size_t hyp_bytes(int32_t pairs, int32_t hypotheses) { return (size_t)pairs * hypotheses * kHypRecord * sizeof(float); }
+dim3 hyp_grid(int32_t n, int32_t pairs) { return dim3((n + kHypLanes - 1) / kHypLanes, pairs); }
+
+}  // namespace
+
+extern "C" {
+
+size_t lg_ransac_workspace(int32_t pairs, int32_t kmax, int32_t hypotheses) {
+    if (pairs <= 0 || kmax <= 0 || hypotheses <= 0) return 0;
+    return hyp_bytes(pairs, hypotheses);
+}
+
+int32_t lg_ransac_fundamental(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                              int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold, int32_t hypotheses,
+                              int32_t refits, int32_t seed, void* workspace, size_t workspace_bytes, float* f,
+                              uint8_t* inliers, int32_t* num_inliers, int32_t* valid, int32_t* best, hipStream_t stream) {
+    const char* who = "lg_ransac_fundamental";
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || hypotheses < 1 ||
+        hypotheses > kMaxHypotheses || refits < 0 || refits > kMaxRefits || !workspace || !aligned16(workspace) ||
+        workspace_bytes < hyp_bytes(pairs, hypotheses) || !f || !inliers || !num_inliers || !valid || !best || !aligned4(f) ||
+        !aligned4(num_inliers) || !aligned4(valid) || !aligned4(best))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    const float thr2 = threshold * threshold;
+    hipLaunchKernelGGL(ransac_hypothesis_kernel<false>, hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream, a, hypotheses,
+                       (uint32_t)seed, thr2, (const int32_t*)nullptr, (float*)workspace, (float*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(ransac_finalize_kernel, dim3(pairs), dim3(kFinThreads), 0, stream, a, hypotheses, refits, thr2,
+                       (const float*)workspace, f, inliers, num_inliers, valid, best);
+    return launched(who);
+}
+
+int32_t lg_ransac_samples(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream) {
+    const char* who = "lg_ransac_samples";
+    if (count < 7 || count > kMaxPoints || hypotheses < 1 || hypotheses > kMaxHypotheses || !samples || !aligned4(samples))
+        return bad(who);
+    hipLaunchKernelGGL(ransac_samples_kernel, dim3((hypotheses + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, stream, count,
+                       hypotheses, (uint32_t)seed, samples);
+    return launched(who);
+}
+
+int32_t lg_ransac_solve7(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                         int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses, float* candidates,
+                         int32_t* num_roots, hipStream_t stream) {
+    const char* who = "lg_ransac_solve7";
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || hypotheses < 1 || hypotheses > kMaxHypotheses ||
+        !samples || !candidates || !num_roots || !aligned4(samples) || !aligned4(candidates) || !aligned4(num_roots))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    hipLaunchKernelGGL(ransac_hypothesis_kernel<true>, hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream, a, hypotheses, 0u,
+                       1.f, samples, (float*)nullptr, candidates, num_roots);
+    return launched(who);
+}
+
+int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                        int32_t kmax, int32_t k0, int32_t k1, const float* candidates, int32_t num_candidates, float threshold,
+                        int32_t* inlier_counts, hipStream_t stream) {
+    const char* who = "lg_ransac_score";
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || num_candidates < 1 ||
+        num_candidates > kMaxHypotheses || !candidates || !inlier_counts || !aligned4(candidates) || !aligned4(inlier_counts))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    hipLaunchKernelGGL(ransac_score_kernel, hyp_grid(num_candidates, pairs), dim3(kHypLanes), 0, stream, a, candidates,
+                       num_candidates, threshold * threshold, inlier_counts);
+    return launched(who);
+}
+
+}  // extern "C"

@@ -39,8 +39,28 @@ from .image import (  # noqa: F401,E402
     resample_matrix,
     target_size,
 )
+from .geometry import (  # noqa: F401,E402
+    FundamentalRansac,
+    GeometryResult,
+    epipolar_error,
+    fundamental_refit,
+    ransac_reference,
+    ransac_samples,
+    solve7_reference,
+    two_view_scene,
+    verify_source_images,
+)
 
 __all__ = [
+    "FundamentalRansac",
+    "GeometryResult",
+    "epipolar_error",
+    "fundamental_refit",
+    "ransac_reference",
+    "ransac_samples",
+    "solve7_reference",
+    "two_view_scene",
+    "verify_source_images",
     "ImageBatch",
     "ImageInput",
     "PreparedImages",

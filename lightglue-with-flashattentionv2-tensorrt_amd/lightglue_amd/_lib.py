@@ -187,6 +187,13 @@ SIGNATURES.update({
     "lg_img_prepare_batch": ([_P, _I, _I, _I, _I, _I, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I, _I,
                               _I, _I, _P, _P], _I),
     "lg_kp_to_source": ([_P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
+    # geometric verification (csrc/lightglue_geometry.hip)
+    "lg_ransac_workspace": ([_I, _I, _I], _S),
+    "lg_ransac_fundamental": ([_P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, _I, _I, _I, _P, _S, _P, _P, _P, _P, _P, _P],
+                              _I),
+    "lg_ransac_samples": ([_I, _I, _I, _P, _P], _I),
+    "lg_ransac_solve7": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P], _I),
+    "lg_ransac_score": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, ctypes.c_float, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -1,0 +1,391 @@
+"""Geometric verification: a fundamental matrix per image pair by RANSAC over the matcher's matches, on gfx950
+kernels (include/lightglue_glue.h, "geometric verification"; csrc/lightglue_geometry.hip).
+
+The reference's demo does not stop at matches: after LightGlueTRT::PostProcess it runs
+``cv::findFundamentalMat(points0, points1, cv::FM_RANSAC, 3, 0.99, inliers)`` on the host and draws only the
+inliers (demo/demo_mono.cpp:326-366). ``FundamentalRansac.verify`` is that step for the P pairs of a
+``MatchResult`` in two launches, with nothing read back: ``verify_source_images`` is ``match_source_images``
+followed by it, still one capturable piece.
+
+The contract is pinned here in float64 on the CPU: ``ransac_samples`` (the minimal samples, which the kernel
+equals bitwise), ``epipolar_error``, ``solve7_reference`` (an SVD null space and ``numpy.roots``, deliberately
+not the kernel's elimination and closed form), ``fundamental_refit`` and ``ransac_reference`` (the whole).
+``two_view_scene`` makes the synthetic pairs the tests use.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, synth
+from ._host import call, carve, require_gpu, stream_of
+from .image import ImageInput, match_source_images
+from .matches import MatchResult
+
+_STAGE = "the geometric verification"
+MAX_POINTS = 2048       # kmax: the plugin's N limit
+MAX_HYPOTHESES = 4096
+MAX_REFITS = 8
+MIN_INLIERS = 8         # a model, and a refit, needs 8 correspondences
+PIVOT_EPS = 1e-6        # a pivot of the 7 x 9 elimination below this: no candidate
+_M32 = 0xFFFFFFFF
+
+
+class GeometryResult(NamedTuple):
+    """F [P, 3, 3] (x1ᵀ F x0 = 0, unit Frobenius norm, the entry of the largest magnitude positive; zeros where
+    valid == 0), inliers [P, Kmax] uint8 aligned with the rows of MatchResult.matches (0 past the count),
+    num_inliers, valid, best [P] int32 (best: the winning hypothesis, -1 where valid == 0)."""
+    F: torch.Tensor
+    inliers: torch.Tensor
+    num_inliers: torch.Tensor
+    valid: torch.Tensor
+    best: torch.Tensor
+
+
+# ---- the minimal samples --------------------------------------------------------------------------------------
+def _hash32(seed: int, h: np.ndarray, j: int) -> np.ndarray:
+    """The counter-based hash of (seed, hypothesis, draw), uint32 arithmetic: the key folded by odd multipliers,
+    then the lowbias32 finaliser."""
+    x = ((seed & _M32) * 0x9E3779B1 + h.astype(np.uint64) * 0x85EBCA77 + j * 0xC2B2AE3D + 0x27D4EB2F) & _M32
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & _M32
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & _M32
+    x ^= x >> 16
+    return x
+
+
+def ransac_samples(seed: int, hypotheses: int, count: int) -> torch.Tensor:
+    """[H, 7] int32: hypothesis h's 7 distinct indices in [0, count), in draw order. Draw j is
+    hash32(seed, h, j) % (count - j), moved past the earlier draws in ascending order (one more for each earlier
+    draw <= it, the smallest first). The pair is not in the key: a pair's result does not depend on its place in
+    a batch."""
+    seed, hypotheses, count = int(seed), int(hypotheses), int(count)
+    if count < 7 or hypotheses < 1:
+        raise ValueError(f"ransac_samples: count >= 7 and hypotheses >= 1, got {count} and {hypotheses}")
+    h = np.arange(hypotheses, dtype=np.uint64)
+    out = np.zeros((hypotheses, 7), dtype=np.int64)
+    for j in range(7):
+        r = (_hash32(seed, h, j) % np.uint64(count - j)).astype(np.int64)
+        earlier = np.sort(out[:, :j], axis=1)
+        for e in range(j):
+            r = r + (r >= earlier[:, e])
+        out[:, j] = r
+    return torch.from_numpy(out.astype(np.int32))
+
+
+# ---- the contract's pieces in float64 ---------------------------------------------------------------------------
+def _np(t) -> np.ndarray:
+    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.float64)
+
+
+def _epi(f: np.ndarray, x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
+    with np.errstate(all="ignore"):
+        h0 = np.concatenate([x0, np.ones((len(x0), 1))], 1)
+        h1 = np.concatenate([x1, np.ones((len(x1), 1))], 1)
+        l1, l0 = h0 @ f.T, h1 @ f
+        d2 = (h1 * l1).sum(1) ** 2
+        return np.maximum(d2 / (l1[:, 0] ** 2 + l1[:, 1] ** 2), d2 / (l0[:, 0] ** 2 + l0[:, 1] ** 2))
+
+
+def epipolar_error(F, x0, x1) -> torch.Tensor:
+    """The error of each correspondence (x0 [n, 2], x1 [n, 2]) under F [3, 3], in squared pixels, float64 [n]:
+    l1 = F x0, l0 = Fᵀ x1, d = x1 · l1, max(d² / (l1x² + l1y²), d² / (l0x² + l0y²)) (OpenCV's for FM_RANSAC).
+    An inlier has error <= threshold²; NaN (a degenerate line, a non-finite coordinate) is none."""
+    return torch.from_numpy(_epi(_np(F).reshape(3, 3), _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)))
+
+
+def _hartley(pts: np.ndarray) -> np.ndarray:
+    """T [3, 3]: centroid to 0, mean distance sqrt 2."""
+    with np.errstate(all="ignore"):
+        c = pts.mean(0)
+        s = np.sqrt(2.0) / np.sqrt(((pts - c) ** 2).sum(1)).mean()
+    return np.array([[s, 0.0, -s * c[0]], [0.0, s, -s * c[1]], [0.0, 0.0, 1.0]])
+
+
+def _apply(t: np.ndarray, pts: np.ndarray) -> np.ndarray:
+    return pts * t[0, 0] + t[:2, 2]
+
+
+def _rows(x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
+    """The rows of x1ᵀ F x0 = 0 for F row-major: (x1 x0, x1 y0, x1, y1 x0, y1 y0, y1, x0, y0, 1)."""
+    one = np.ones(len(x0))
+    return np.stack([x1[:, 0] * x0[:, 0], x1[:, 0] * x0[:, 1], x1[:, 0], x1[:, 1] * x0[:, 0], x1[:, 1] * x0[:, 1],
+                     x1[:, 1], x0[:, 0], x0[:, 1], one], 1)
+
+
+def _unit(f: np.ndarray):
+    """f at unit Frobenius norm with the sign rule (the entry of the largest magnitude positive, the lowest index
+    among equals), or None where it is zero or not finite."""
+    with np.errstate(all="ignore"):
+        n = np.sqrt((f * f).sum())
+        if not np.isfinite(n) or n == 0.0 or not np.isfinite(1.0 / n):
+            return None
+        f = f / n
+    return -f if f.flat[int(np.argmax(np.abs(f)))] < 0 else f
+
+
+def elimination_pivots(a: np.ndarray) -> float:
+    """The smallest pivot magnitude of the Gauss-Jordan elimination with partial (row) pivoting on the 7 x 9
+    system, columns 0..6 in order: the quantity the contract's epsilon is about. NaN where not finite."""
+    a = np.array(a, dtype=np.float64)
+    low = np.inf
+    with np.errstate(all="ignore"):
+        for c in range(7):
+            piv = c + int(np.argmax(np.abs(a[c:, c])))
+            best = abs(a[piv, c])
+            if not best > 0.0:
+                return float(best)
+            low = min(low, best)
+            a[[c, piv]] = a[[piv, c]]
+            a[c] /= a[c, c]
+            for r in range(7):
+                if r != c:
+                    a[r] -= a[r, c] * a[c]
+    return float(low)
+
+
+class Solve7(NamedTuple):
+    """candidates [n, 3, 3] float64 in pixels (unit norm, sign rule), in ascending root; roots: the cubic's three
+    complex roots (fewer where its leading coefficients vanish); pivot: elimination_pivots of the system."""
+    candidates: np.ndarray
+    roots: np.ndarray
+    pivot: float
+
+
+def _det_poly(g: np.ndarray, d: np.ndarray) -> np.ndarray:
+    """Coefficients (highest first) of det(g + l d) for 3 x 3 g, d: each a sum of determinants of mixed rows."""
+    det = np.linalg.det
+
+    def mixed(mask):
+        return det(np.stack([d[i] if mask >> i & 1 else g[i] for i in range(3)]))
+
+    return np.array([mixed(7), mixed(3) + mixed(5) + mixed(6), mixed(1) + mixed(2) + mixed(4), mixed(0)])
+
+
+def solve7_reference(x0, x1, sample) -> Solve7:
+    """The 7-point solve of the contract in float64: x0, x1 [n, 2] all correspondences of the pair (the Hartley
+    normalisation is over all of them), sample 7 indices. The null space by SVD, brought to the canonical basis
+    f1 = (.., 1, 0), f2 = (.., 0, 1) (which fixes the parameter l whatever found the null space), the roots of
+    det(l f1 + (1 - l) f2) by numpy.roots, the real ones in ascending order de-normalised to unit norm. A pivot
+    below PIVOT_EPS, or anything non-finite, gives no candidate."""
+    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
+    idx = np.asarray(sample, dtype=np.int64).reshape(7)
+    t0, t1 = _hartley(x0), _hartley(x1)
+    a = _rows(_apply(t0, x0[idx]), _apply(t1, x1[idx]))
+    none = Solve7(np.zeros((0, 3, 3)), np.zeros((0,), dtype=complex), float("nan"))
+    if not np.isfinite(a).all():
+        return none
+    pivot = elimination_pivots(a)
+    null = np.linalg.svd(a)[2][7:9]
+    with np.errstate(all="ignore"):
+        try:
+            basis = np.linalg.solve(null[:, 7:9], null)  # rows end (1, 0) and (0, 1)
+        except np.linalg.LinAlgError:
+            return Solve7(none.candidates, none.roots, pivot)
+    if not np.isfinite(basis).all():
+        return Solve7(none.candidates, none.roots, pivot)
+    g, d = basis[1].reshape(3, 3), (basis[0] - basis[1]).reshape(3, 3)
+    roots = np.roots(_det_poly(g, d)).astype(complex)
+    real = sorted(float(r.real) for r in roots if abs(r.imag) <= 1e-12 * max(1.0, abs(r)))
+    cands = []
+    if pivot >= PIVOT_EPS:
+        for lam in real:
+            f = _unit(t1.T @ (g + lam * d) @ t0)
+            if f is not None:
+                cands.append(f)
+    return Solve7(np.array(cands).reshape(-1, 3, 3), roots, pivot)
+
+
+def _refit(x0: np.ndarray, x1: np.ndarray):
+    t0, t1 = _hartley(x0), _hartley(x1)
+    a = _rows(_apply(t0, x0), _apply(t1, x1))
+    if not (np.isfinite(a).all() and np.isfinite(t0).all() and np.isfinite(t1).all()):
+        return None
+    f = np.linalg.eigh(a.T @ a)[1][:, 0].reshape(3, 3)
+    v = np.linalg.svd(f)[2][2]
+    return _unit(t1.T @ (f - np.outer(f @ v, v)) @ t0)
+
+
+def fundamental_refit(x0, x1) -> torch.Tensor:
+    """One refit round of the contract on the given correspondences (x0, x1 [n, 2], n >= 8), float64 [3, 3]:
+    Hartley normalisation over them, the eigenvector of the smallest eigenvalue of the 9 x 9 normal matrix, rank
+    2 by F <- F (I - v vᵀ) with v the smallest right-singular direction, de-normalised to unit norm with the
+    sign rule."""
+    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
+    if len(x0) < MIN_INLIERS or len(x0) != len(x1):
+        raise ValueError(f"fundamental_refit: two sets of n >= {MIN_INLIERS} points, got {len(x0)} and {len(x1)}")
+    f = _refit(x0, x1)
+    if f is None:
+        raise ValueError("fundamental_refit: the correspondences give no finite matrix")
+    return torch.from_numpy(f)
+
+
+def _check_params(threshold, hypotheses, refits) -> None:
+    if not 0.0 < float(threshold) <= 1e6:
+        raise ValueError(f"threshold must be in (0, 1e6] pixels, got {threshold}")
+    if not 1 <= int(hypotheses) <= MAX_HYPOTHESES:
+        raise ValueError(f"hypotheses must be in [1, {MAX_HYPOTHESES}], got {hypotheses}")
+    if not 0 <= int(refits) <= MAX_REFITS:
+        raise ValueError(f"refits must be in [0, {MAX_REFITS}], got {refits}")
+
+
+def gather_correspondences(matches, count: int, kpts0, kpts1) -> Tuple[np.ndarray, np.ndarray]:
+    """One pair's correspondences as the kernels read them: matches [Kmax, 2], kpts0 [K0, 2], kpts1 [K1, 2] ->
+    (x0, x1) float64 [count, 2], the count clamped into [0, Kmax] and the indices into range."""
+    m = np.asarray(matches.cpu() if isinstance(matches, torch.Tensor) else matches).astype(np.int64)
+    k0, k1 = _np(kpts0), _np(kpts1)
+    n = min(max(int(count), 0), len(m))
+    return k0[np.clip(m[:n, 0], 0, len(k0) - 1)], k1[np.clip(m[:n, 1], 0, len(k1) - 1)]
+
+
+def ransac_reference(matches, counts, kpts0, kpts1, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2,
+                     seed: int = 888) -> GeometryResult:
+    """FundamentalRansac(threshold, hypotheses, refits, seed).verify in float64 on the CPU: matches [P, Kmax, 2],
+    counts [P], kpts0 [P, K0, 2], kpts1 [P, K1, 2] -> GeometryResult (F float64). The steps are the header's:
+    gather and normalise, ransac_samples, solve7_reference, every candidate scored in pixels (the winner: the
+    highest count, then the lowest hypothesis, then the lowest root), `refits` rounds of fundamental_refit's
+    arithmetic over the current inliers (a round with fewer than 8 keeps F and mask)."""
+    _check_params(threshold, hypotheses, refits)
+    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
+    out = GeometryResult(torch.zeros((pr, 3, 3), dtype=torch.float64), torch.zeros((pr, kmax), dtype=torch.uint8),
+                         torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr,), dtype=torch.int32),
+                         torch.full((pr,), -1, dtype=torch.int32))
+    thr2 = float(threshold) ** 2
+    for p in range(pr):
+        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
+        n = len(x0)
+        if n < MIN_INLIERS:
+            continue
+        best_n, best_h, best_f = -1, -1, None
+        for h, sample in enumerate(ransac_samples(seed, hypotheses, n).numpy()):
+            for f in solve7_reference(x0, x1, sample).candidates:
+                got = int((_epi(f, x0, x1) <= thr2).sum())
+                if got > best_n:
+                    best_n, best_h, best_f = got, h, f
+        if best_n < MIN_INLIERS:
+            continue
+        f, mask = best_f, _epi(best_f, x0, x1) <= thr2
+        for _ in range(int(refits)):
+            if int(mask.sum()) < MIN_INLIERS:
+                break
+            again = _refit(x0[mask], x1[mask])
+            if again is None:
+                break
+            f, mask = again, _epi(again, x0, x1) <= thr2
+        out.F[p] = torch.from_numpy(f)
+        out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
+        out.num_inliers[p], out.valid[p], out.best[p] = int(mask.sum()), 1, best_h
+    return out
+
+
+# ---- synthetic pairs ------------------------------------------------------------------------------------------------
+def two_view_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
+    """Two pinhole views (size = (h, w), focal length w, the second camera turned and moved sideways) of random
+    3D points, from synth.uniform24: (kpts0 [k, 2] fp32, kpts1 [k, 2] fp32, gt_mask [k] bool, F_true [3, 3]
+    float64 at unit norm). round(k outlier_fraction) rows are outliers: both ends uniform in the images, redrawn
+    until their error under F_true exceeds 12 px; the inliers are projections moved by at most noise_px in each
+    image; the rows are shuffled."""
+    h, w = int(size[0]), int(size[1])
+    n_out = int(round(k * outlier_fraction))
+    n_in = k - n_out
+    if k < 1 or n_in < 0 or n_out < 0 or noise_px < 0:
+        raise ValueError(f"two_view_scene: bad k / outlier_fraction / noise_px {k}, {outlier_fraction}, {noise_px}")
+    pool = 16 * k + 64
+    u = synth.uniform24(int(seed), 16 + 9 * pool).astype(np.float64)
+    cam, u = u[:16], u[16:].reshape(9, pool)
+    kk = np.array([[w, 0.0, w / 2.0], [0.0, w, h / 2.0], [0.0, 0.0, 1.0]])
+    ang = (cam[:3] - 0.5) * np.array([0.12, 0.5, 0.12]) + np.array([0.0, 0.15, 0.0])  # radians about x, y, z
+    cx, cy, cz = np.cos(ang)
+    sx, sy, sz = np.sin(ang)
+    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    rot = rz @ ry @ rx
+    t = np.array([-1.0 - cam[3], 0.3 * (cam[4] - 0.5), 0.3 * (cam[5] - 0.5)])
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    kinv = np.linalg.inv(kk)
+    f_true = kinv.T @ tx @ rot @ kinv
+    f_true = _unit(f_true)
+    # inliers: a pixel of image 0 at a depth, seen in image 1
+    p0 = np.stack([u[0] * (w - 1), u[1] * (h - 1)], 1)
+    depth = 4.0 + 8.0 * u[2]
+    xyz = (np.concatenate([p0, np.ones((pool, 1))], 1) @ kinv.T) * depth[:, None]
+    q = (xyz @ rot.T + t) @ kk.T
+    p1 = q[:, :2] / q[:, 2:3]
+    ok = (q[:, 2] > 0.5) & (p1[:, 0] >= 0) & (p1[:, 0] <= w - 1) & (p1[:, 1] >= 0) & (p1[:, 1] <= h - 1)
+    keep = np.nonzero(ok)[0][:n_in]
+    # outliers
+    o0 = np.stack([u[3] * (w - 1), u[4] * (h - 1)], 1)
+    o1 = np.stack([u[5] * (w - 1), u[6] * (h - 1)], 1)
+    far = np.nonzero(np.sqrt(_epi(f_true, o0, o1)) > 12.0)[0][:n_out]
+    if len(keep) < n_in or len(far) < n_out:
+        raise ValueError("two_view_scene: the pool ran out (a seed whose second view sees too little)")
+    a = noise_px / np.sqrt(2.0)
+    noise = (u[7:9, :2 * n_in].reshape(2, 2, n_in) * 2.0 - 1.0) * a
+    k0 = np.concatenate([p0[keep] + noise[0].T, o0[far]])
+    k1 = np.concatenate([p1[keep] + noise[1].T, o1[far]])
+    gt = np.concatenate([np.ones(n_in, dtype=bool), np.zeros(n_out, dtype=bool)])
+    order = np.argsort(synth.uniform24(int(seed) + 0x5EED, k), kind="stable")
+    return (torch.from_numpy(k0[order].astype(np.float32)), torch.from_numpy(k1[order].astype(np.float32)),
+            torch.from_numpy(gt[order]), torch.from_numpy(f_true))
+
+
+# ---- the kernels --------------------------------------------------------------------------------------------------
+class FundamentalRansac:
+    """RANSAC for the fundamental matrix of every pair of a MatchResult. threshold: the inlier bound in pixels
+    (the demo's 3); hypotheses: their fixed number per pair (no early termination: the launches do not depend
+    on the data); refits: least-squares rounds over the inliers; seed: of the samples."""
+
+    def __init__(self, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2, seed: int = 888) -> None:
+        _check_params(threshold, hypotheses, refits)
+        self.threshold, self.hypotheses, self.refits = float(threshold), int(hypotheses), int(refits)
+        self.seed = int(seed) & _M32
+
+    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor) -> GeometryResult:
+        """result.matches [P, Kmax, 2] / result.counts [P] (int32) index kpts0 [P, K0, 2] and kpts1 [P, K1, 2]
+        (fp32, (x, y) in pixels; ImageInput.keypoints' output is the intended one) -> GeometryResult. Two
+        launches on the current stream, nothing read back; counts and indices are clamped, never trusted."""
+        matches, counts = result.matches, result.counts
+        require_gpu("matches", matches, _STAGE, (torch.int32,), 3)
+        require_gpu("counts", counts, _STAGE, (torch.int32,), 1)
+        require_gpu("kpts0", kpts0, _STAGE, (torch.float32,), 3)
+        require_gpu("kpts1", kpts1, _STAGE, (torch.float32,), 3)
+        pr, kmax = int(matches.shape[0]), int(matches.shape[1])
+        if matches.shape[2] != 2 or not 1 <= kmax <= MAX_POINTS:
+            raise ValueError(f"matches: expected [P, Kmax, 2] with 1 <= Kmax <= {MAX_POINTS}, got {tuple(matches.shape)}")
+        if tuple(counts.shape) != (pr,):
+            raise ValueError(f"counts: expected [{pr}], got {tuple(counts.shape)}")
+        for name, t in (("kpts0", kpts0), ("kpts1", kpts1)):
+            if t.shape[0] != pr or t.shape[1] < 1 or t.shape[2] != 2:
+                raise ValueError(f"{name}: expected [{pr}, K, 2] with K >= 1, got {tuple(t.shape)}")
+            if t.device != matches.device:
+                raise ValueError(f"{name}: on {t.device}, the matches on {matches.device}")
+        dev = matches.device
+        out = GeometryResult(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
+                             torch.empty((pr, kmax), dtype=torch.uint8, device=dev),
+                             torch.empty((pr,), dtype=torch.int32, device=dev),
+                             torch.empty((pr,), dtype=torch.int32, device=dev),
+                             torch.empty((pr,), dtype=torch.int32, device=dev))
+        if pr == 0:
+            return out
+        matches, counts, kpts0, kpts1 = (t.contiguous() for t in (matches, counts, kpts0, kpts1))
+        stream = stream_of(matches)
+        nbytes = int(_lib.load().lg_ransac_workspace(pr, kmax, self.hypotheses))
+        ws, = carve(dev, stream, [nbytes])
+        seed = self.seed - (1 << 32) if self.seed >= 1 << 31 else self.seed  # the same 32 bits as int32
+        call("lg_ransac_fundamental", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), pr, kmax,
+             int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses, self.refits, seed, ws.data_ptr(),
+             nbytes, *(t.data_ptr() for t in out), stream)
+        return out
+
+
+def verify_source_images(image_input: ImageInput, encoder, frontend, matcher, ransac: FundamentalRansac, images0, images1):
+    """match_source_images followed by ransac.verify on its outputs: (MatchResult, kpts0_src, kpts1_src,
+    GeometryResult), the fundamental matrices in the source images' own pixels. What replaces the demo's
+    PostProcess + cv::findFundamentalMat (demo/demo_mono.cpp:326-366); nothing is read back, so it enqueues, or
+    is captured, as one piece."""
+    result, kp0, kp1 = match_source_images(image_input, encoder, frontend, matcher, images0, images1)
+    return result, kp0, kp1, ransac.verify(result, kp0, kp1)

@@ -1,0 +1,222 @@
+"""A/B on one GPU: FundamentalRansac.verify (two gfx950 launches) against the same contract restated as batched
+framework ops on the same device (ransac_reference's stages: the samples gathered, an SVD null space per
+hypothesis, the cubic's roots as companion eigenvalues, every candidate scored by products over all
+correspondences, refits by eigh / svd), and the share verify adds to verify_source_images over match_source_images.
+
+Cases: K in {256, 1024, 2048} correspondences a pair (all pairs full), P in {1, 16} pairs, H = 512, R = 2, 25 %
+outliers. verify is timed as graph replays (N calls captured back to back, replay time / N, events on the
+stream); the framework arm is timed eagerly, by a host clock around two calls that end in a device synchronise:
+its SVD and eigenvalue routines synchronise with the host, which a capture refuses (framework_mode in the
+record; verify_eager_us is our arm under the same clock). Arms alternate; --repeats repeats, median [min, max].
+
+The pipeline part: 480 x 640 grey sources at the target size, 512 keypoints a side, the seeded 9-layer matcher,
+P = 1 and 2: match_source_images and verify_source_images each captured as one graph, replayed alternately.
+
+    python tools/geometry_ab.py [--repeats 5] [--part all|verify|pipeline] [--out profiles/geometry/ab.jsonl]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "lightglue-with-flashattentionv2-tensorrt_amd")]
+import torch  # noqa: E402
+
+from lightglue_amd import (FundamentalRansac, ImageInput, KeypointFrontend, SuperPointEncoder, match_source_images,  # noqa: E402
+                           matcher, ransac_samples, seeded_superpoint_state_dict, two_view_scene, verify_source_images)
+from lightglue_amd.matches import MatchResult  # noqa: E402
+
+H, R, THR, SEED = 512, 2, 3.0, 888
+CALLS = 20  # calls a graph
+
+
+def _rows(x0, x1):
+    one = torch.ones_like(x0[..., 0])
+    return torch.stack([x1[..., 0] * x0[..., 0], x1[..., 0] * x0[..., 1], x1[..., 0], x1[..., 1] * x0[..., 0],
+                        x1[..., 1] * x0[..., 1], x1[..., 1], x0[..., 0], x0[..., 1], one], -1)
+
+
+def _hartley(x, w):
+    """x [P, K, 2], weights w [P, K] -> T [P, 3, 3] float64."""
+    n = w.sum(1, keepdim=True)
+    c = (x * w[..., None]).sum(1) / n
+    d = (((x - c[:, None]) ** 2).sum(-1).sqrt() * w).sum(1) / n[:, 0]
+    s = 2.0 ** 0.5 / d
+    t = torch.zeros((x.shape[0], 3, 3), dtype=x.dtype, device=x.device)
+    t[:, 0, 0], t[:, 1, 1], t[:, 2, 2] = s, s, 1.0
+    t[:, 0, 2], t[:, 1, 2] = -s * c[:, 0], -s * c[:, 1]
+    return t
+
+
+def _apply(t, x):
+    return x * t[:, None, 0, 0, None] + t[:, None, :2, 2]
+
+
+def _inliers(f, x0, x1, thr2):
+    """f [P, C, 3, 3], x [P, K, 2] (fp32) -> [P, C, K] bool."""
+    h0 = torch.cat([x0, torch.ones_like(x0[..., :1])], -1)
+    h1 = torch.cat([x1, torch.ones_like(x1[..., :1])], -1)
+    l1 = torch.einsum("pcij,pkj->pcki", f, h0)
+    l0 = torch.einsum("pcji,pkj->pcki", f, h1)
+    d2 = (l1 * h1[:, None]).sum(-1) ** 2
+    err = torch.maximum(d2 / (l1[..., 0] ** 2 + l1[..., 1] ** 2), d2 / (l0[..., 0] ** 2 + l0[..., 1] ** 2))
+    return err <= thr2
+
+
+def framework_ransac(x0, x1, samples):
+    """x0, x1 [P, K, 2] fp32 on the GPU, samples [H, 7] -> (F [P, 3, 3] fp32, mask [P, K])."""
+    pr, k, _ = x0.shape
+    a0, a1 = x0.double(), x1.double()
+    ones = torch.ones((pr, k), dtype=torch.float64, device=x0.device)
+    t0, t1 = _hartley(a0, ones), _hartley(a1, ones)
+    n0, n1 = _apply(t0, a0), _apply(t1, a1)
+    a = _rows(n0[:, samples], n1[:, samples])                         # [P, H, 7, 9]
+    null = torch.linalg.svd(a, full_matrices=True)[2][..., 7:9, :]    # [P, H, 2, 9]
+    basis = torch.linalg.solve(null[..., 7:9], null)
+    g, d = basis[..., 1, :].reshape(pr, -1, 3, 3), (basis[..., 0, :] - basis[..., 1, :]).reshape(pr, -1, 3, 3)
+    det = torch.linalg.det
+
+    def mixed(mask):
+        return det(torch.stack([d[..., i, :] if mask >> i & 1 else g[..., i, :] for i in range(3)], -2))
+
+    c3, c2, c1, c0 = mixed(7), mixed(3) + mixed(5) + mixed(6), mixed(1) + mixed(2) + mixed(4), mixed(0)
+    comp = torch.zeros(c3.shape + (3, 3), dtype=torch.float64, device=x0.device)
+    comp[..., 0, 0], comp[..., 0, 1], comp[..., 0, 2] = -c2 / c3, -c1 / c3, -c0 / c3
+    comp[..., 1, 0], comp[..., 2, 1] = 1.0, 1.0
+    lam = torch.linalg.eigvals(comp)                                  # [P, H, 3] complex
+    real = lam.imag.abs() <= 1e-9 * lam.abs().clamp(min=1.0)
+    fn = g[:, :, None] + lam.real[..., None, None] * d[:, :, None]    # [P, H, 3, 3, 3]
+    f = torch.einsum("pji,phrjk,pkl->phril", t1, fn, t0)
+    f = (f / f.flatten(-2).norm(dim=-1)[..., None, None]).reshape(pr, -1, 3, 3).float()
+    inl = _inliers(f, x0, x1, THR * THR)
+    counts = torch.where(real.reshape(pr, -1), inl.sum(-1), -1)
+    best = counts.argmax(1)
+    fb = f[torch.arange(pr, device=x0.device), best]
+    mask = inl[torch.arange(pr, device=x0.device), best]
+    for _ in range(R):
+        w = mask.double()
+        t0, t1 = _hartley(a0, w), _hartley(a1, w)
+        rows = _rows(_apply(t0, a0), _apply(t1, a1)) * w[..., None]
+        fe = torch.linalg.eigh(rows.transpose(1, 2) @ rows)[1][..., 0].reshape(pr, 3, 3)
+        v = torch.linalg.svd(fe)[2][:, 2]
+        fe = fe - (fe @ v[..., None]) * v[:, None]
+        fb = t1.transpose(1, 2) @ fe @ t0
+        fb = (fb / fb.flatten(1).norm(dim=1)[:, None, None]).float()
+        mask = _inliers(fb[:, None], x0, x1, THR * THR)[:, 0]
+    return fb, mask
+
+
+def graph_of(fn, stream, calls):
+    with torch.cuda.stream(stream):
+        fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=stream):
+            for _ in range(calls):
+                fn()
+    return g
+
+
+def time_graph(g, stream, calls):
+    g.replay()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(stream):
+        s.record(stream)
+        g.replay()
+        e.record(stream)
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) * 1e3 / calls  # us a call
+
+
+def time_eager(fn, calls):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e6 / calls
+
+
+def spread(v):
+    return {"min": round(min(v), 2), "median": round(statistics.median(v), 2), "max": round(max(v), 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "geometry", "ab.jsonl"))
+    ap.add_argument("--part", choices=("all", "verify", "pipeline"), default="all")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("geometry_ab.py: needs a GPU (timings from anywhere else mean nothing)")
+    dev = torch.device("cuda:0")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    stream = torch.cuda.Stream(dev)
+    base = {"H": H, "refits": R, "threshold": THR, "repeats": args.repeats, "device": torch.cuda.get_device_name(0)}
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        with open(args.out, "a") as out:
+            out.write(line + "\n")
+
+    fr = FundamentalRansac(THR, H, R, SEED)
+    for k in (256, 1024, 2048) if args.part != "pipeline" else ():
+        k0, k1, gt, _ = two_view_scene(k, k, 0.25, 0.25)
+        samples = ransac_samples(SEED, H, k).long().to(dev)
+        for pr in (1, 16):
+            x0, x1 = k0.to(dev)[None].repeat(pr, 1, 1), k1.to(dev)[None].repeat(pr, 1, 1)
+            m = torch.arange(k, dtype=torch.int32, device=dev)[None, :, None].repeat(pr, 1, 2).contiguous()
+            counts = torch.full((pr,), k, dtype=torch.int32, device=dev)
+            res = MatchResult(None, None, None, None, m, None, counts)
+            with torch.no_grad():
+                ours = lambda: fr.verify(res, x0, x1)              # noqa: E731
+                theirs = lambda: framework_ransac(x0, x1, samples)  # noqa: E731
+                mine, (_, their_mask) = ours(), theirs()
+                torch.cuda.synchronize()
+                rec = dict(base, part="verify", K=k, P=pr,
+                           ours_mask_is_gt=bool((mine.inliers.bool().cpu() == gt[None]).all()),
+                           framework_mask_is_gt=bool((their_mask.cpu() == gt[None]).all()))
+                g = graph_of(ours, stream, CALLS)
+                t_ours, t_theirs = [], []
+                for _ in range(args.repeats):
+                    t_ours.append(time_graph(g, stream, CALLS))
+                    t_theirs.append(time_eager(theirs, 2))
+                rec.update(verify_us=spread(t_ours), framework_us=spread(t_theirs), framework_mode="eager",
+                           verify_eager_us=round(time_eager(ours, 50), 2),
+                           framework_over_verify_median=round(statistics.median(t_theirs) / statistics.median(t_ours), 1))
+            emit(rec)
+            del g
+    if args.part == "verify":
+        return
+    encoder = SuperPointEncoder(seeded_superpoint_state_dict(3))
+    model = matcher.LightGlueMatcher(n_layers=9).eval()
+    model.load_state_dict(matcher.seeded_state_dict(7, 9), strict=True)
+    model = model.to(dev, torch.float16)
+    fe, ii = KeypointFrontend(max_keypoints=512), ImageInput((480, 640))
+    for pr in (1, 2):
+        gen = torch.Generator().manual_seed(40 + pr)
+        s0 = torch.randint(0, 256, (pr, 480, 640), generator=gen, dtype=torch.uint8).to(dev)
+        s1 = torch.randint(0, 256, (pr, 480, 640), generator=gen, dtype=torch.uint8).to(dev)
+        with torch.no_grad():
+            a = lambda: match_source_images(ii, encoder, fe, model, s0, s1)          # noqa: E731
+            b = lambda: verify_source_images(ii, encoder, fe, model, fr, s0, s1)     # noqa: E731
+            counts = b()[0].counts.cpu().tolist()
+            ga, gb = graph_of(a, stream, 1), graph_of(b, stream, 1)
+            ta, tb = [], []
+            for _ in range(args.repeats):
+                ta.append(time_graph(ga, stream, 1))
+                tb.append(time_graph(gb, stream, 1))
+        ma, mb = statistics.median(ta), statistics.median(tb)
+        emit(dict(base, part="pipeline", P=pr, source=[480, 640], max_keypoints=512, match_counts=counts,
+                  match_source_images_us=spread(ta), verify_source_images_us=spread(tb),
+                  verify_adds_us=round(mb - ma, 2), verify_share_of_total=round((mb - ma) / mb, 3)))
+
+
+if __name__ == "__main__":
+    main()
