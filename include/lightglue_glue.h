@@ -502,6 +502,59 @@ int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const flo
                         int32_t kmax, int32_t k0, int32_t k1, const float* candidates, int32_t num_candidates, float threshold,
                         int32_t* inlier_counts, hipStream_t stream);
 
+/* The homography, next to the fundamental matrix: what stitching, planar tracking, registration and the
+ * HPatches protocol run on the host as cv::findHomography(pts0, pts1, cv::RANSAC, 3), and the right model where
+ * the epipolar constraint is degenerate (a planar scene, a purely rotating camera). The same kernels, templates on
+ * the model. Inputs, clamping, limits and alignment are lg_ransac_fundamental's, and so is every general
+ * statement above (arguments checked first, a no-op for pairs == 0, no atomics, no allocation, every output
+ * entry written). lightglue_amd/geometry.py restates the contract in float64 (homography_reference).
+ *
+ * Model: x1 ~ H x0 with x = (x, y, 1), H row-major. Error of a correspondence (OpenCV's for findHomography with
+ * RANSAC): (X, Y, W) = H x0, err = (x1 - X/W)² + (y1 - Y/W)²; an inlier iff err <= threshold². A non-finite err is
+ * none (W = 0, a NaN or Inf coordinate, a zero or NaN H). The kernels test dx² + dy² <= threshold² W² with
+ * dx = x1 W - X, dy = y1 W - Y, W² > 0 and the left side finite. Per pair, independently:
+ *   1. Hartley normalisation, as step 1 above.
+ *   2. Hypothesis h samples 4 distinct indices: the first four draws of step 2 above (for count >= 7 the first
+ *      four columns of the 7-sample; defined from count = 4 on; ransac_samples(size=4) in geometry.py).
+ *   3. The 4-point solve in normalised coordinates, fp64 (for the reason of the 7-point solve; the fp32 figures
+ *      are in profiles/geometry/INDEX.md): the 8 x 9 system of two rows a point,
+ *      (-x0, -y0, -1, 0, 0, 0, x1 x0, x1 y0, x1) and (0, 0, 0, -x0, -y0, -1, y1 x0, y1 y0, y1), by Gauss-Jordan with
+ *      row pivoting on columns 0..7 in order; the canonical null vector ends in 1 (h8 = 1 in the normalised frame).
+ *      A pivot below 1e-6: no candidate (three collinear sample points, a repeated index, a true h8 of 0).
+ *      Orientation rule (OpenCV's checkSubset): for the four triples of the sample, the sign of the 2 x 2
+ *      orientation determinant in image 0 times that in image 1, in the normalised fp64 coordinates; products
+ *      neither all positive nor all negative: no candidate. De-normalised by H = T1⁻¹ Hn T0, scaled to unit
+ *      Frobenius norm with the sign rule of f, rounded to fp32 (a non-finite one is dropped): 0 or 1 candidate.
+ *   4. The candidate is scored against all correspondences in pixels, fp32. The winner: the highest inlier count,
+ *      then the lowest hypothesis.
+ *   5. `refits` rounds of a normalised DLT over the current inliers in fp64 (Hartley over the inliers, the same two
+ *      rows an inlier, the eigenvector of the smallest eigenvalue of the 9 x 9 normal matrix by the same Jacobi,
+ *      no rank step, de-normalised), then the inliers again. A round with fewer than 4 inliers, or a refit that
+ *      is not finite, keeps the previous H and mask. OpenCV's final Levenberg-Marquardt polish is not built.
+ * A pair with count < 4, with no candidate or with a winner of fewer than 4 inliers: valid = 0, H = 0, no inlier,
+ * best = -1. A 4-inlier winner is only its own sample: callers should threshold num_inliers.
+ *
+ * lg_ransac_homography: lg_ransac_fundamental's arguments with h [pairs, 3, 3] fp32 in place of f; the workspace
+ * is lg_ransac_workspace's (the record of a hypothesis is the same). Two launches. */
+int32_t lg_ransac_homography(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                             int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold, int32_t hypotheses,
+                             int32_t refits, int32_t seed, void* workspace, size_t workspace_bytes, float* h,
+                             uint8_t* inliers, int32_t* num_inliers, int32_t* valid, int32_t* best, hipStream_t stream);
+/* Stage hooks over the same device code (tests). lg_ransac_samples4: step 2 for one count in [4, 2048] ->
+ * samples [hypotheses, 4] int32 in draw order. */
+int32_t lg_ransac_samples4(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream);
+/* lg_ransac_solve4: steps 1 and 3 on given samples [hypotheses, 4] int32 (device; clamped into [0, count), shared
+ * by the pairs) -> candidates [pairs, hypotheses, 9] fp32 (zeros where there is none) and num [pairs, hypotheses]
+ * int32, 0 or 1. A pair with count < 4: zeros. */
+int32_t lg_ransac_solve4(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                         int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses, float* candidates,
+                         int32_t* num, hipStream_t stream);
+/* lg_ransac_score_homography: step 4's count for given candidates [pairs, num_candidates, 9] fp32
+ * (1 <= num_candidates <= 4096) -> inlier_counts [pairs, num_candidates] int32. */
+int32_t lg_ransac_score_homography(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                                   int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* candidates,
+                                   int32_t num_candidates, float threshold, int32_t* inlier_counts, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

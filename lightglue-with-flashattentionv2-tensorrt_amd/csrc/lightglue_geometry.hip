@@ -1,7 +1,12 @@
 // lightglue_geometry.hip — geometric verification (include/lightglue_glue.h, "geometric verification"): a
 // fundamental matrix per image pair by RANSAC over the matcher's matches, what the reference's demo does on the
 // host with cv::findFundamentalMat(points0, points1, cv::FM_RANSAC, 3, 0.99, inliers) after PostProcess
-// (demo/demo_mono.cpp:326-366). The contract is restated in float64 in lightglue_amd/geometry.py.
+// (demo/demo_mono.cpp:326-366), and a homography by the same scheme (cv::findHomography(points0, points1,
+// cv::RANSAC, 3) without its final Levenberg-Marquardt polish). The contract is restated in float64 in
+// lightglue_amd/geometry.py. The kernels are templates on the model (FundamentalModel, HomographyModel below):
+// the sample size, the minimal solve, the error, the refit's rows and its last step are the model's, the rest
+// is shared. The description that follows is in the fundamental matrix's numbers (the homography's: 4 indices,
+// the 4-point system, one candidate, no rank step).
 //
 // Two launches. ransac_hypothesis_kernel: grid (hypothesis blocks, pairs), 64 hypotheses a workgroup; the
 // workgroup gathers the pair's correspondences into LDS once (2048 x 16 B) and computes the Hartley
@@ -88,9 +93,48 @@ __device__ __forceinline__ void hartley(const float4* pts, const uint8_t* use, i
     for (int i = 0; i < 2; ++i) s[i] = 1.4142135623730951 / (block_sum<NT>(dist[i], buf, tid) / n);
 }
 
-// GIVEN: the samples are an input and every candidate an output (lg_ransac_solve7); else the samples are
+// ---- the models ---------------------------------------------------------------------------------------------------
+// kSample: indices a hypothesis; kCands: candidates a hypothesis at most; kMin: correspondences a model, a winner
+// and a refit need. solve: normalised sample -> candidates in pixels; inlier: the error test; accumulate: one
+// inlier's share of the refit's normal matrix; finish: the eigenvector to the matrix in pixels at unit norm.
+struct FundamentalModel {
+    static constexpr int kSample = 7, kCands = 3, kMin = kMinInliers;
+    static __device__ __forceinline__ int solve(const double x0[7], const double y0[7], const double x1[7], const double y1[7],
+                                                const NormT<double>& t, float cand[3][9]) {
+        return solve7(x0, y0, x1, y1, t, cand);
+    }
+    static __device__ __forceinline__ bool inlier(const float f[9], float x0, float y0, float x1, float y1, float thr2) {
+        return is_inlier(f, x0, y0, x1, y1, thr2);
+    }
+    static __device__ __forceinline__ void accumulate(double acc[45], double x0, double y0, double x1, double y1) {
+        normal_accumulate_f(acc, x0, y0, x1, y1);
+    }
+    static __device__ __forceinline__ bool finish(double fn[9], const double c[4], const double s[2], double out[9]) {
+        rank2(fn);
+        return denormalise64(fn, c[0], c[1], s[0], c[2], c[3], s[1], out);
+    }
+};
+
+struct HomographyModel {
+    static constexpr int kSample = 4, kCands = 1, kMin = kMinInliersH;
+    static __device__ __forceinline__ int solve(const double x0[4], const double y0[4], const double x1[4], const double y1[4],
+                                                const NormT<double>& t, float cand[1][9]) {
+        return solve4(x0, y0, x1, y1, t, cand[0]);
+    }
+    static __device__ __forceinline__ bool inlier(const float h[9], float x0, float y0, float x1, float y1, float thr2) {
+        return is_inlier_h(h, x0, y0, x1, y1, thr2);
+    }
+    static __device__ __forceinline__ void accumulate(double acc[45], double x0, double y0, double x1, double y1) {
+        normal_accumulate_h(acc, x0, y0, x1, y1);
+    }
+    static __device__ __forceinline__ bool finish(double hn[9], const double c[4], const double s[2], double out[9]) {
+        return denormalise_h(hn, c[0], c[1], s[0], c[2], c[3], s[1], out);
+    }
+};
+
+// GIVEN: the samples are an input and every candidate an output (lg_ransac_solve7, lg_ransac_solve4); else the samples are
 // hashed and the best candidate's record goes to the workspace.
-template <bool GIVEN>
+template <class M, bool GIVEN>
 __global__ __launch_bounds__(kHypThreads) void ransac_hypothesis_kernel(PairArgs a, int hypotheses, uint32_t seed, float thr2,
                                                                          const int32_t* __restrict__ samples,
                                                                          float* __restrict__ hyp, float* __restrict__ cand_out,
@@ -101,57 +145,63 @@ __global__ __launch_bounds__(kHypThreads) void ransac_hypothesis_kernel(PairArgs
     const int h = blockIdx.x * kHypLanes + tid / kHypSplit;
     const bool live = h < hypotheses;
     const int count = pair_count(a, p);
-    float cand[3][9];
+    constexpr int NS = M::kSample, NC = M::kCands;
+    float cand[NC][9];
     int nc = 0;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NC; ++i)
 #pragma unroll
         for (int k = 0; k < 9; ++k) cand[i][k] = 0.f;
-    if (count >= kMinInliers) {  // (the same for the whole workgroup)
+    if (count >= M::kMin) {  // (the same for the whole workgroup)
         stage_pair(a, p, count, pts, tid, kHypThreads);
         double c[4], s[2];
         hartley<kHypThreads>(pts, nullptr, count, (double)count, buf, tid, c, s);
         const NormT<double> t{c[0], c[1], s[0], c[2], c[3], s[1]};
         if (live) {  // (the lanes of a hypothesis solve it alike: the same statements on the same values)
-            int idx[7];
+            int idx[NS];
             if constexpr (GIVEN) {
 #pragma unroll
-                for (int j = 0; j < 7; ++j) idx[j] = min(max(samples[(size_t)h * 7 + j], 0), count - 1);
+                for (int j = 0; j < NS; ++j) idx[j] = min(max(samples[(size_t)h * NS + j], 0), count - 1);
             } else {
-                sample7(seed, h, count, idx);
+                sample<NS>(seed, h, count, idx);
             }
-            double x0[7], y0[7], x1[7], y1[7];
+            double x0[NS], y0[NS], x1[NS], y1[NS];
 #pragma unroll
-            for (int j = 0; j < 7; ++j) {
+            for (int j = 0; j < NS; ++j) {
                 const float4 q = pts[idx[j]];
                 x0[j] = ((double)q.x - t.cx0) * t.s0, y0[j] = ((double)q.y - t.cy0) * t.s0;
                 x1[j] = ((double)q.z - t.cx1) * t.s1, y1[j] = ((double)q.w - t.cy1) * t.s1;
             }
-            nc = solve7(x0, y0, x1, y1, t, cand);
+            nc = M::solve(x0, y0, x1, y1, t, cand);
         }
     }
     if constexpr (GIVEN) {
         if (!live || sub != 0) return;
-        float* out = cand_out + ((size_t)p * hypotheses + h) * 27;
+        float* out = cand_out + ((size_t)p * hypotheses + h) * (9 * NC);
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < NC; ++i)
 #pragma unroll
             for (int k = 0; k < 9; ++k) out[9 * i + k] = cand[i][k];
         nroots_out[(size_t)p * hypotheses + h] = nc;
     } else {
+        // (n1, n2 and candidates 1, 2 exist for the model of three candidates only; the other's are constants)
         int n0 = 0, n1 = 0, n2 = 0;
+        const float* c1 = cand[NC > 1 ? 1 : 0];
+        const float* c2 = cand[NC > 2 ? 2 : 0];
         if (nc > 0) {
 #pragma unroll 2
             for (int k = sub; k < count; k += kHypSplit) {
                 const float4 q = pts[k];
-                n0 += is_inlier(cand[0], q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
-                n1 += is_inlier(cand[1], q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
-                n2 += is_inlier(cand[2], q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+                n0 += M::inlier(cand[0], q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+                if constexpr (NC > 1) n1 += M::inlier(c1, q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+                if constexpr (NC > 2) n2 += M::inlier(c2, q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
             }
         }
 #pragma unroll
         for (int d = 1; d < kHypSplit; d <<= 1) {  // (integers: the order of the sum does not matter)
-            n0 += __shfl_xor(n0, d), n1 += __shfl_xor(n1, d), n2 += __shfl_xor(n2, d);
+            n0 += __shfl_xor(n0, d);
+            if constexpr (NC > 1) n1 += __shfl_xor(n1, d);
+            if constexpr (NC > 2) n2 += __shfl_xor(n2, d);
         }
         if (!live || sub != 0) return;
         // the highest count, the lowest root among equals (a zero candidate counts nothing)
@@ -159,12 +209,13 @@ __global__ __launch_bounds__(kHypThreads) void ransac_hypothesis_kernel(PairArgs
         const int best = max(n0, max(n1, n2));
         float* rec = hyp + ((size_t)p * hypotheses + h) * kHypRecord;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) rec[k] = root == 2 ? cand[2][k] : (root == 1 ? cand[1][k] : cand[0][k]);
+        for (int k = 0; k < 9; ++k) rec[k] = root == 2 ? c2[k] : (root == 1 ? c1[k] : cand[0][k]);
         rec[9] = __int_as_float(best), rec[10] = __int_as_float(root), rec[11] = 0.f;
     }
 }
 
-// lg_ransac_score: a lane is one given candidate.
+// lg_ransac_score, lg_ransac_score_homography: a lane is one given candidate.
+template <class M>
 __global__ __launch_bounds__(kHypLanes) void ransac_score_kernel(PairArgs a, const float* __restrict__ cands, int ncand,
                                                                   float thr2, int32_t* __restrict__ out) {
     __shared__ float4 pts[kMaxPoints];
@@ -179,21 +230,24 @@ __global__ __launch_bounds__(kHypLanes) void ransac_score_kernel(PairArgs a, con
     int n = 0;
     for (int k = 0; k < count; ++k) {
         const float4 q = pts[k];
-        n += is_inlier(f, q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
+        n += M::inlier(f, q.x, q.y, q.z, q.w, thr2) ? 1 : 0;
     }
     out[(size_t)p * ncand + c] = n;
 }
 
+template <int N>
 __global__ __launch_bounds__(kHypLanes) void ransac_samples_kernel(int count, int hypotheses, uint32_t seed,
                                                                     int32_t* __restrict__ out) {
     const int h = blockIdx.x * kHypLanes + threadIdx.x;
     if (h >= hypotheses) return;
-    int idx[7];
-    sample7(seed, h, count, idx);
+    int idx[N];
+    sample<N>(seed, h, count, idx);
 #pragma unroll
-    for (int j = 0; j < 7; ++j) out[(size_t)h * 7 + j] = idx[j];
+    for (int j = 0; j < N; ++j) out[(size_t)h * N + j] = idx[j];
 }
 
+// (f, f_out, fnew and "F" in the comments below: the model's 3 x 3 matrix, F or H.)
+template <class M>
 __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a, int hypotheses, int refits, float thr2,
                                                                        const float* __restrict__ hyp, float* __restrict__ f_out,
                                                                        uint8_t* __restrict__ inl_out,
@@ -229,7 +283,7 @@ __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a
         __syncthreads();
     }
     bc = best_c[0], bh = best_h[0];
-    const bool valid = count >= kMinInliers && bc >= kMinInliers;  // (the same for the whole workgroup)
+    const bool valid = count >= M::kMin && bc >= M::kMin;  // (the same for the whole workgroup)
 
     float f[9];
 #pragma unroll
@@ -244,13 +298,13 @@ __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a
             int mine = 0;
             for (int k = tid; k < count; k += kFinThreads) {
                 const float4 q = pts[k];
-                const bool in = is_inlier(f, q.x, q.y, q.z, q.w, thr2);
+                const bool in = M::inlier(f, q.x, q.y, q.z, q.w, thr2);
                 mask[k] = in ? 1 : 0;
                 mine += in ? 1 : 0;
             }
             num = (int)block_sum<kFinThreads>((double)mine, buf, tid);  // (exact: integers below 2^53)
-            if (round >= refits || num < kMinInliers) break;
-            // normalised 8-point least squares over the inliers
+            if (round >= refits || num < M::kMin) break;
+            // normalised least squares over the inliers (8-point; the homography's DLT)
             double c[4], s[2];
             hartley<kFinThreads>(pts, mask, count, (double)num, buf, tid, c, s);
             {   // the upper triangle of the normal matrix: a thread sums its inliers (every 256th from tid on, in
@@ -263,12 +317,7 @@ __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a
                     const float4 q = pts[k];
                     const double x0 = ((double)q.x - c[0]) * s[0], y0 = ((double)q.y - c[1]) * s[0];
                     const double x1 = ((double)q.z - c[2]) * s[1], y1 = ((double)q.w - c[3]) * s[1];
-                    const double row[9] = {x1 * x0, x1 * y0, x1, y1 * x0, y1 * y0, y1, x0, y0, 1.0};
-                    int e = 0;
-#pragma unroll
-                    for (int i = 0; i < 9; ++i)
-#pragma unroll
-                        for (int j = i; j < 9; ++j) acc[e] = fma(row[i], row[j], acc[e]), ++e;
+                    M::accumulate(acc, x0, y0, x1, y1);
                 }
 #pragma unroll
                 for (int e = 0; e < 45; ++e) {
@@ -323,8 +372,7 @@ __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a
                 for (int k = 1; k < 9; ++k) lo = am[10 * k] < am[10 * lo] ? k : lo;
                 double fn[9], fd[9];
                 for (int k = 0; k < 9; ++k) fn[k] = vm[9 * k + lo];
-                rank2(fn);
-                fnew_ok = denormalise64(fn, c[0], c[1], s[0], c[2], c[3], s[1], fd) ? 1 : 0;
+                fnew_ok = M::finish(fn, c, s, fd) ? 1 : 0;
                 for (int k = 0; k < 9; ++k) fnew[k] = fd[k];
             }
             __syncthreads();
@@ -373,10 +421,11 @@ int32_t lg_ransac_fundamental(const int32_t* matches, const int32_t* counts, con
     if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
     const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
     const float thr2 = threshold * threshold;
-    hipLaunchKernelGGL(ransac_hypothesis_kernel<false>, hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream, a, hypotheses,
-                       (uint32_t)seed, thr2, (const int32_t*)nullptr, (float*)workspace, (float*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(ransac_finalize_kernel, dim3(pairs), dim3(kFinThreads), 0, stream, a, hypotheses, refits, thr2,
-                       (const float*)workspace, f, inliers, num_inliers, valid, best);
+    hipLaunchKernelGGL((ransac_hypothesis_kernel<FundamentalModel, false>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0,
+                       stream, a, hypotheses, (uint32_t)seed, thr2, (const int32_t*)nullptr, (float*)workspace, (float*)nullptr,
+                       (int32_t*)nullptr);
+    hipLaunchKernelGGL(ransac_finalize_kernel<FundamentalModel>, dim3(pairs), dim3(kFinThreads), 0, stream, a, hypotheses, refits,
+                       thr2, (const float*)workspace, f, inliers, num_inliers, valid, best);
     return launched(who);
 }
 
@@ -384,7 +433,7 @@ int32_t lg_ransac_samples(int32_t count, int32_t hypotheses, int32_t seed, int32
     const char* who = "lg_ransac_samples";
     if (count < 7 || count > kMaxPoints || hypotheses < 1 || hypotheses > kMaxHypotheses || !samples || !aligned4(samples))
         return bad(who);
-    hipLaunchKernelGGL(ransac_samples_kernel, dim3((hypotheses + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, stream, count,
+    hipLaunchKernelGGL(ransac_samples_kernel<7>, dim3((hypotheses + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, stream, count,
                        hypotheses, (uint32_t)seed, samples);
     return launched(who);
 }
@@ -398,8 +447,8 @@ int32_t lg_ransac_solve7(const int32_t* matches, const int32_t* counts, const fl
         return bad(who);
     if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
     const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    hipLaunchKernelGGL(ransac_hypothesis_kernel<true>, hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream, a, hypotheses, 0u,
-                       1.f, samples, (float*)nullptr, candidates, num_roots);
+    hipLaunchKernelGGL((ransac_hypothesis_kernel<FundamentalModel, true>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0,
+                       stream, a, hypotheses, 0u, 1.f, samples, (float*)nullptr, candidates, num_roots);
     return launched(who);
 }
 
@@ -412,8 +461,66 @@ int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const flo
         return bad(who);
     if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
     const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    hipLaunchKernelGGL(ransac_score_kernel, hyp_grid(num_candidates, pairs), dim3(kHypLanes), 0, stream, a, candidates,
-                       num_candidates, threshold * threshold, inlier_counts);
+    hipLaunchKernelGGL(ransac_score_kernel<FundamentalModel>, hyp_grid(num_candidates, pairs), dim3(kHypLanes), 0, stream, a,
+                       candidates, num_candidates, threshold * threshold, inlier_counts);
+    return launched(who);
+}
+
+int32_t lg_ransac_homography(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                             int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold, int32_t hypotheses,
+                             int32_t refits, int32_t seed, void* workspace, size_t workspace_bytes, float* h,
+                             uint8_t* inliers, int32_t* num_inliers, int32_t* valid, int32_t* best, hipStream_t stream) {
+    const char* who = "lg_ransac_homography";
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || hypotheses < 1 ||
+        hypotheses > kMaxHypotheses || refits < 0 || refits > kMaxRefits || !workspace || !aligned16(workspace) ||
+        workspace_bytes < hyp_bytes(pairs, hypotheses) || !h || !inliers || !num_inliers || !valid || !best || !aligned4(h) ||
+        !aligned4(num_inliers) || !aligned4(valid) || !aligned4(best))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    const float thr2 = threshold * threshold;
+    hipLaunchKernelGGL((ransac_hypothesis_kernel<HomographyModel, false>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0,
+                       stream, a, hypotheses, (uint32_t)seed, thr2, (const int32_t*)nullptr, (float*)workspace, (float*)nullptr,
+                       (int32_t*)nullptr);
+    hipLaunchKernelGGL(ransac_finalize_kernel<HomographyModel>, dim3(pairs), dim3(kFinThreads), 0, stream, a, hypotheses, refits,
+                       thr2, (const float*)workspace, h, inliers, num_inliers, valid, best);
+    return launched(who);
+}
+
+int32_t lg_ransac_samples4(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream) {
+    const char* who = "lg_ransac_samples4";
+    if (count < 4 || count > kMaxPoints || hypotheses < 1 || hypotheses > kMaxHypotheses || !samples || !aligned4(samples))
+        return bad(who);
+    hipLaunchKernelGGL(ransac_samples_kernel<4>, dim3((hypotheses + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, stream, count,
+                       hypotheses, (uint32_t)seed, samples);
+    return launched(who);
+}
+
+int32_t lg_ransac_solve4(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                         int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses, float* candidates,
+                         int32_t* num, hipStream_t stream) {
+    const char* who = "lg_ransac_solve4";
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || hypotheses < 1 || hypotheses > kMaxHypotheses ||
+        !samples || !candidates || !num || !aligned4(samples) || !aligned4(candidates) || !aligned4(num))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    hipLaunchKernelGGL((ransac_hypothesis_kernel<HomographyModel, true>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream,
+                       a, hypotheses, 0u, 1.f, samples, (float*)nullptr, candidates, num);
+    return launched(who);
+}
+
+int32_t lg_ransac_score_homography(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                                   int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* candidates,
+                                   int32_t num_candidates, float threshold, int32_t* inlier_counts, hipStream_t stream) {
+    const char* who = "lg_ransac_score_homography";
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || num_candidates < 1 ||
+        num_candidates > kMaxHypotheses || !candidates || !inlier_counts || !aligned4(candidates) || !aligned4(inlier_counts))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    hipLaunchKernelGGL(ransac_score_kernel<HomographyModel>, hyp_grid(num_candidates, pairs), dim3(kHypLanes), 0, stream, a,
+                       candidates, num_candidates, threshold * threshold, inlier_counts);
     return launched(who);
 }
 

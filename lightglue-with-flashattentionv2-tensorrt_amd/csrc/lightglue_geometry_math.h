@@ -1,9 +1,9 @@
-// lightglue_geometry_math.h — the per-lane arithmetic of the fundamental-matrix RANSAC
+// lightglue_geometry_math.h — the per-lane arithmetic of the fundamental-matrix and homography RANSAC
 // (csrc/lightglue_geometry.hip; include/lightglue_glue.h, "geometric verification"): the sample hash, the
-// 7-point solve, the epipolar error and the pieces of the fp64 refit. Plain functions on values and small
-// fixed-size arrays, every index a compile-time constant after unrolling (a run-time index into a register
-// array goes to scratch on this compiler): pivoting and compaction are selects. The functions are
-// __host__ __device__, so a host program can run the same statements on the CPU.
+// 7-point and 4-point solves, the epipolar and transfer errors and the pieces of the fp64 refits. Plain
+// functions on values and small fixed-size arrays, every index a compile-time constant after unrolling (a
+// run-time index into a register array goes to scratch on this compiler): pivoting and compaction are
+// selects. The functions are __host__ __device__, so a host program can run the same statements on the CPU.
 #pragma once
 
 #include <math.h>
@@ -20,8 +20,9 @@ namespace lg_geom {
 constexpr int kMaxPoints = 2048;     // the plugin's N limit
 constexpr int kMaxHypotheses = 4096;
 constexpr int kMaxRefits = 8;
-constexpr int kMinInliers = 8;       // a model, and a refit, needs 8 correspondences
-constexpr float kPivotEps = 1e-6f;   // a pivot of the 7 x 9 elimination below this: no candidate
+constexpr int kMinInliers = 8;       // a fundamental matrix, and its refit, needs 8 correspondences
+constexpr int kMinInliersH = 4;      // a homography, and its refit, needs 4
+constexpr float kPivotEps = 1e-6f;   // a pivot of the 7 x 9 (8 x 9) elimination below this: no candidate
 constexpr int kJacobiSweeps = 7;     // 9 x 9, fp64, 9 steps of 4 disjoint rotations a sweep; off-diagonal / diagonal
                                      // norm on the test scenes: 3e-4 after 4 sweeps, 4e-8 after 5, 6e-16 after 6
 constexpr int kJacobi3Sweeps = 6;
@@ -39,12 +40,14 @@ LG_HD uint32_t hash32(uint32_t seed, uint32_t h, uint32_t j) {
     return x;
 }
 
-// 7 distinct indices in [0, count), count >= 7: draw j is hash % (count - j), moved past the earlier draws in
-// ascending order (r += 1 for each earlier draw <= r, smallest first). idx is in draw order.
-LG_HD void sample7(uint32_t seed, int h, int count, int idx[7]) {
-    int sorted[7];
+// N distinct indices in [0, count), count >= N: draw j is hash % (count - j), moved past the earlier draws in
+// ascending order (r += 1 for each earlier draw <= r, smallest first). idx is in draw order. The first draws do
+// not depend on N: the 4-sample of a hypothesis is the first four of its 7-sample.
+template <int N>
+LG_HD void sample(uint32_t seed, int h, int count, int idx[N]) {
+    int sorted[N];
 #pragma unroll
-    for (int j = 0; j < 7; ++j) {
+    for (int j = 0; j < N; ++j) {
         int r = (int)(hash32(seed, (uint32_t)h, (uint32_t)j) % (uint32_t)(count - j));
 #pragma unroll
         for (int e = 0; e < j; ++e) r += r >= sorted[e] ? 1 : 0;
@@ -79,6 +82,32 @@ LG_HD bool is_inlier(const float f[9], float x0, float y0, float x1, float y1, f
     const float d2 = d * d;
     const float den1 = fmaf(l1x, l1x, l1y * l1y), den0 = fmaf(l0x, l0x, l0y * l0y);
     return d2 <= thr2 * den1 && d2 <= thr2 * den0 && den1 > 0.f && den0 > 0.f && d2 < INFINITY;
+}
+
+// ---- the transfer error (homography) -------------------------------------------------------------------------------
+// (X, Y, W) = H x0; err = (x1 - X/W)² + (y1 - Y/W)² <= thr2, without the division: with dx = x1 W - X and
+// dy = y1 W - Y, dx² + dy² <= thr2 W², where W² is positive and the left side finite (W = 0 or anything
+// non-finite makes err non-finite: no inlier; NaN fails every comparison).
+LG_HD bool is_inlier_h(const float h[9], float x0, float y0, float x1, float y1, float thr2) {
+    const float X = fmaf(h[0], x0, fmaf(h[1], y0, h[2]));
+    const float Y = fmaf(h[3], x0, fmaf(h[4], y0, h[5]));
+    const float W = fmaf(h[6], x0, fmaf(h[7], y0, h[8]));
+    const float dx = fmaf(x1, W, -X), dy = fmaf(y1, W, -Y);
+    const float d2 = fmaf(dx, dx, dy * dy), w2 = W * W;
+    return d2 <= thr2 * w2 && w2 > 0.f && d2 < INFINITY;
+}
+
+// The sign rule of the output: the entry of the largest magnitude (the lowest index among equals) is positive.
+LG_HD void fix_sign(float f[9]) {
+    float best = fabsf(f[0]), val = f[0];
+#pragma unroll
+    for (int i = 1; i < 9; ++i) {
+        const bool up = fabsf(f[i]) > best;
+        best = up ? fabsf(f[i]) : best, val = up ? f[i] : val;
+    }
+    const float sg = val < 0.f ? -1.f : 1.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) f[i] *= sg;
 }
 
 // float and double forms of the few library functions the solve uses. The solve is a template on its real type:
@@ -259,6 +288,111 @@ LG_HD int solve7(const T x0[7], const T y0[7], const T x1[7], const T y1[7], con
     return (good[0] ? 1 : 0) + (good[1] ? 1 : 0) + (good[2] ? 1 : 0);
 }
 
+// T1⁻¹ Hn T0 of a homography in normalised coordinates, scaled to unit Frobenius norm; false where the result is
+// not finite or zero (out is then zeros).
+template <typename T>
+LG_HD bool denormalise_h(const T hn[9], T cx0, T cy0, T s0, T cx1, T cy1, T s1, T out[9]) {
+    T m[9], ss = T(0);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        m[3 * r] = s0 * hn[3 * r];
+        m[3 * r + 1] = s0 * hn[3 * r + 1];
+        m[3 * r + 2] = hn[3 * r + 2] - s0 * (cx0 * hn[3 * r] + cy0 * hn[3 * r + 1]);
+    }
+    const T r1 = T(1) / s1;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        out[k] = m_fma(cx1, m[6 + k], r1 * m[k]);
+        out[3 + k] = m_fma(cy1, m[6 + k], r1 * m[3 + k]);
+        out[6 + k] = m[6 + k];
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ss = m_fma(out[i], out[i], ss);
+    const T inv = T(1) / m_sqrt(ss);
+    const bool ok = ss > T(0) && ss < T(INFINITY) && inv < T(INFINITY);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out[i] = ok ? out[i] * inv : T(0);
+    return ok;
+}
+
+// The sign of the orientation of the triple (i, j, k) in image 0 times that in image 1: +1, -1 or 0 (a
+// collinear triple in either image, or NaN).
+template <typename T>
+LG_HD int orientation_product(const T x0[4], const T y0[4], const T x1[4], const T y1[4], int i, int j, int k) {
+    const T d0 = (x0[j] - x0[i]) * (y0[k] - y0[i]) - (y0[j] - y0[i]) * (x0[k] - x0[i]);
+    const T d1 = (x1[j] - x1[i]) * (y1[k] - y1[i]) - (y1[j] - y1[i]) * (x1[k] - x1[i]);
+    const int a = d0 > T(0) ? 1 : (d0 < T(0) ? -1 : 0), b = d1 > T(0) ? 1 : (d1 < T(0) ? -1 : 0);
+    return a * b;
+}
+
+// The 4-point solve on normalised points, in T: the null vector of the 8 x 9 system (two rows a point:
+// (-x0, -y0, -1, 0, 0, 0, x1 x0, x1 y0, x1) and (0, 0, 0, -x0, -y0, -1, y1 x0, y1 y0, y1)) by Gauss-Jordan
+// elimination with partial (row) pivoting on columns 0..7, hn = (-B, 1) for the reduced system [I | B]; no
+// candidate where a pivot is below kPivotEps or the four triples of the sample are not oriented alike in both
+// images (all products of orientation_product positive, or all negative); de-normalised to pixels at unit norm
+// with the sign rule, fp32. Returns the number of candidates, 0 or 1 (cand zeros for 0). H row-major, x1 ~ H x0.
+template <typename T>
+LG_HD int solve4(const T x0[4], const T y0[4], const T x1[4], const T y1[4], const NormT<T>& t, float cand[9]) {
+    T a[8][9];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        a[2 * i][0] = -x0[i], a[2 * i][1] = -y0[i], a[2 * i][2] = T(-1);
+        a[2 * i][3] = T(0), a[2 * i][4] = T(0), a[2 * i][5] = T(0);
+        a[2 * i][6] = x1[i] * x0[i], a[2 * i][7] = x1[i] * y0[i], a[2 * i][8] = x1[i];
+        a[2 * i + 1][0] = T(0), a[2 * i + 1][1] = T(0), a[2 * i + 1][2] = T(0);
+        a[2 * i + 1][3] = -x0[i], a[2 * i + 1][4] = -y0[i], a[2 * i + 1][5] = T(-1);
+        a[2 * i + 1][6] = y1[i] * x0[i], a[2 * i + 1][7] = y1[i] * y0[i], a[2 * i + 1][8] = y1[i];
+    }
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        T best = m_abs(a[c][c]);
+        int piv = c;
+#pragma unroll
+        for (int r = c + 1; r < 8; ++r) {
+            const T v = m_abs(a[r][c]);
+            const bool up = v > best;
+            best = up ? v : best, piv = up ? r : piv;
+        }
+        ok = ok && best >= T(kPivotEps);  // (NaN: false)
+#pragma unroll
+        for (int r = c + 1; r < 8; ++r) {
+            const bool sw = piv == r;
+#pragma unroll
+            for (int k = c; k < 9; ++k) {
+                const T u = a[c][k], v = a[r][k];
+                a[c][k] = sw ? v : u, a[r][k] = sw ? u : v;
+            }
+        }
+        const T inv = T(1) / a[c][c];
+#pragma unroll
+        for (int k = c + 1; k < 9; ++k) a[c][k] *= inv;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r == c) continue;
+            const T f = a[r][c];
+#pragma unroll
+            for (int k = c + 1; k < 9; ++k) a[r][k] = m_fma(-f, a[c][k], a[r][k]);
+        }
+    }
+    int pos = 0, neg = 0;
+#pragma unroll
+    for (int tr = 0; tr < 4; ++tr) {  // the triples (0 1 2), (0 1 3), (0 2 3), (1 2 3)
+        const int o = orientation_product(x0, y0, x1, y1, tr == 3 ? 1 : 0, tr >= 2 ? 2 : 1, tr == 0 ? 2 : 3);
+        pos += o > 0 ? 1 : 0, neg += o < 0 ? 1 : 0;
+    }
+    ok = ok && (pos == 4 || neg == 4);
+    T hn[9], hd[9];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) hn[r] = -a[r][8];
+    hn[8] = T(1);
+    ok = denormalise_h(hn, t.cx0, t.cy0, t.s0, t.cx1, t.cy1, t.s1, hd) && ok;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cand[k] = ok ? (float)hd[k] : 0.f;
+    fix_sign(cand);
+    return ok ? 1 : 0;
+}
+
 // ---- the refit, fp64 ---------------------------------------------------------------------------------------------
 // Entry e of the 45 upper-triangle entries (i <= j) of a symmetric 9 x 9 matrix, row by row.
 LG_HD void tri_index(int e, int& i, int& j) {
@@ -363,17 +497,31 @@ LG_HD bool denormalise64(const double fn[9], double cx0, double cy0, double s0, 
     return ok;
 }
 
-// The sign rule of the output: the entry of the largest magnitude (the lowest index among equals) is positive.
-LG_HD void fix_sign(float f[9]) {
-    float best = fabsf(f[0]), val = f[0];
+// One inlier's share of the upper triangle of the normal matrix (45 entries, row by row), normalised points.
+// The fundamental matrix: one row (x1 x0, x1 y0, x1, y1 x0, y1 y0, y1, x0, y0, 1).
+LG_HD void normal_accumulate_f(double acc[45], double x0, double y0, double x1, double y1) {
+    const double row[9] = {x1 * x0, x1 * y0, x1, y1 * x0, y1 * y0, y1, x0, y0, 1.0};
+    int e = 0;
 #pragma unroll
-    for (int i = 1; i < 9; ++i) {
-        const bool up = fabsf(f[i]) > best;
-        best = up ? fabsf(f[i]) : best, val = up ? f[i] : val;
-    }
-    const float sg = val < 0.f ? -1.f : 1.f;
+    for (int i = 0; i < 9; ++i)
 #pragma unroll
-    for (int i = 0; i < 9; ++i) f[i] *= sg;
+        for (int j = i; j < 9; ++j) acc[e] = fma(row[i], row[j], acc[e]), ++e;
+}
+
+// The homography: the row pair of solve4; products with a structural zero are left out (they add nothing), so
+// entries (0..2) x (3..5) of the matrix stay exactly zero.
+LG_HD void normal_accumulate_h(double acc[45], double x0, double y0, double x1, double y1) {
+    const double ra[9] = {-x0, -y0, -1.0, 0.0, 0.0, 0.0, x1 * x0, x1 * y0, x1};
+    const double rb[9] = {0.0, 0.0, 0.0, -x0, -y0, -1.0, y1 * x0, y1 * y0, y1};
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+        for (int j = i; j < 9; ++j) {
+            if (!(i >= 3 && i < 6) && !(j >= 3 && j < 6)) acc[e] = fma(ra[i], ra[j], acc[e]);
+            if (!(i < 3) && !(j < 3)) acc[e] = fma(rb[i], rb[j], acc[e]);
+            ++e;
+        }
 }
 
 }  // namespace lg_geom

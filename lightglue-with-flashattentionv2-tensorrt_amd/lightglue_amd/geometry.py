@@ -11,6 +11,12 @@ The contract is pinned here in float64 on the CPU: ``ransac_samples`` (the minim
 equals bitwise), ``epipolar_error``, ``solve7_reference`` (an SVD null space and ``numpy.roots``, deliberately
 not the kernel's elimination and closed form), ``fundamental_refit`` and ``ransac_reference`` (the whole).
 ``two_view_scene`` makes the synthetic pairs the tests use.
+
+``HomographyRansac.verify`` is the same scheme for the homography x1 ~ H x0 (planar scenes and rotating cameras,
+where the epipolar constraint is degenerate): ``cv::findHomography(pts0, pts1, cv::RANSAC, 3)`` without its final
+Levenberg-Marquardt polish. Its float64 contract: ``ransac_samples(size=4)``, ``transfer_error``,
+``solve4_reference`` (an SVD null vector scaled to the canonical one, not the kernel's elimination),
+``homography_refit`` and ``homography_reference``; ``planar_scene`` makes its pairs.
 """
 from __future__ import annotations
 
@@ -28,8 +34,9 @@ _STAGE = "the geometric verification"
 MAX_POINTS = 2048       # kmax: the plugin's N limit
 MAX_HYPOTHESES = 4096
 MAX_REFITS = 8
-MIN_INLIERS = 8         # a model, and a refit, needs 8 correspondences
-PIVOT_EPS = 1e-6        # a pivot of the 7 x 9 elimination below this: no candidate
+MIN_INLIERS = 8         # a fundamental matrix, and its refit, needs 8 correspondences
+MIN_INLIERS_H = 4       # a homography, and its refit, needs 4
+PIVOT_EPS = 1e-6        # a pivot of the 7 x 9 (8 x 9) elimination below this: no candidate
 _M32 = 0xFFFFFFFF
 
 
@@ -38,6 +45,18 @@ class GeometryResult(NamedTuple):
     valid == 0), inliers [P, Kmax] uint8 aligned with the rows of MatchResult.matches (0 past the count),
     num_inliers, valid, best [P] int32 (best: the winning hypothesis, -1 where valid == 0)."""
     F: torch.Tensor
+    inliers: torch.Tensor
+    num_inliers: torch.Tensor
+    valid: torch.Tensor
+    best: torch.Tensor
+
+
+class HomographyResult(NamedTuple):
+    """H [P, 3, 3] (x1 ~ H x0, unit Frobenius norm, the entry of the largest magnitude positive; zeros where
+    valid == 0), inliers [P, Kmax] uint8 aligned with the rows of MatchResult.matches (0 past the count),
+    num_inliers, valid, best [P] int32 (best: the winning hypothesis, -1 where valid == 0). A pair is valid from 4
+    inliers on, and a 4-inlier winner is only its own sample: threshold num_inliers before trusting H."""
+    H: torch.Tensor
     inliers: torch.Tensor
     num_inliers: torch.Tensor
     valid: torch.Tensor
@@ -57,17 +76,20 @@ def _hash32(seed: int, h: np.ndarray, j: int) -> np.ndarray:
     return x
 
 
-def ransac_samples(seed: int, hypotheses: int, count: int) -> torch.Tensor:
-    """[H, 7] int32: hypothesis h's 7 distinct indices in [0, count), in draw order. Draw j is
-    hash32(seed, h, j) % (count - j), moved past the earlier draws in ascending order (one more for each earlier
-    draw <= it, the smallest first). The pair is not in the key: a pair's result does not depend on its place in
-    a batch."""
-    seed, hypotheses, count = int(seed), int(hypotheses), int(count)
-    if count < 7 or hypotheses < 1:
-        raise ValueError(f"ransac_samples: count >= 7 and hypotheses >= 1, got {count} and {hypotheses}")
+def ransac_samples(seed: int, hypotheses: int, count: int, size: int = 7) -> torch.Tensor:
+    """[H, size] int32: hypothesis h's `size` (7: the fundamental matrix, 4: the homography) distinct indices in
+    [0, count), in draw order. Draw j is hash32(seed, h, j) % (count - j), moved past the earlier draws in
+    ascending order (one more for each earlier draw <= it, the smallest first): for count >= 7 the 4-sample is the
+    first four columns of the 7-sample. The pair is not in the key: a pair's result does not depend on its place
+    in a batch."""
+    seed, hypotheses, count, size = int(seed), int(hypotheses), int(count), int(size)
+    if size not in (4, 7):
+        raise ValueError(f"ransac_samples: size is 4 or 7, got {size}")
+    if count < size or hypotheses < 1:
+        raise ValueError(f"ransac_samples: count >= {size} and hypotheses >= 1, got {count} and {hypotheses}")
     h = np.arange(hypotheses, dtype=np.uint64)
-    out = np.zeros((hypotheses, 7), dtype=np.int64)
-    for j in range(7):
+    out = np.zeros((hypotheses, size), dtype=np.int64)
+    for j in range(size):
         r = (_hash32(seed, h, j) % np.uint64(count - j)).astype(np.int64)
         earlier = np.sort(out[:, :j], axis=1)
         for e in range(j):
@@ -128,12 +150,14 @@ def _unit(f: np.ndarray):
 
 
 def elimination_pivots(a: np.ndarray) -> float:
-    """The smallest pivot magnitude of the Gauss-Jordan elimination with partial (row) pivoting on the 7 x 9
-    system, columns 0..6 in order: the quantity the contract's epsilon is about. NaN where not finite."""
+    """The smallest pivot magnitude of the Gauss-Jordan elimination with partial (row) pivoting on the n x 9
+    system (7 rows: the 7-point solve, 8: the 4-point), columns 0..n-1 in order: the quantity the contract's
+    epsilon is about. NaN where not finite."""
     a = np.array(a, dtype=np.float64)
     low = np.inf
+    rows = len(a)
     with np.errstate(all="ignore"):
-        for c in range(7):
+        for c in range(rows):
             piv = c + int(np.argmax(np.abs(a[c:, c])))
             best = abs(a[piv, c])
             if not best > 0.0:
@@ -141,7 +165,7 @@ def elimination_pivots(a: np.ndarray) -> float:
             low = min(low, best)
             a[[c, piv]] = a[[piv, c]]
             a[c] /= a[c, c]
-            for r in range(7):
+            for r in range(rows):
                 if r != c:
                     a[r] -= a[r, c] * a[c]
     return float(low)
@@ -223,6 +247,99 @@ def fundamental_refit(x0, x1) -> torch.Tensor:
     return torch.from_numpy(f)
 
 
+# ---- the homography's pieces in float64 -------------------------------------------------------------------------
+def _transfer(h: np.ndarray, x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
+    with np.errstate(all="ignore"):
+        q = np.concatenate([x0, np.ones((len(x0), 1))], 1) @ h.T
+        return (x1[:, 0] - q[:, 0] / q[:, 2]) ** 2 + (x1[:, 1] - q[:, 1] / q[:, 2]) ** 2
+
+
+def transfer_error(H, x0, x1) -> torch.Tensor:
+    """The error of each correspondence (x0 [n, 2], x1 [n, 2]) under H [3, 3] (x1 ~ H x0), in squared pixels,
+    float64 [n]: (X, Y, W) = H x0, (x1 - X/W)² + (y1 - Y/W)² (OpenCV's for findHomography with RANSAC). An inlier
+    has error <= threshold²; a non-finite error (W = 0, a non-finite coordinate, a zero or NaN H) is none."""
+    return torch.from_numpy(_transfer(_np(H).reshape(3, 3), _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)))
+
+
+def _rows_h(x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
+    """The two rows a point of x1 ~ H x0 for H row-major: (-x0, -y0, -1, 0, 0, 0, x1 x0, x1 y0, x1) and
+    (0, 0, 0, -x0, -y0, -1, y1 x0, y1 y0, y1); [2 n, 9], a point's pair adjacent."""
+    one, zero = np.ones(len(x0)), np.zeros(len(x0))
+    ra = np.stack([-x0[:, 0], -x0[:, 1], -one, zero, zero, zero, x1[:, 0] * x0[:, 0], x1[:, 0] * x0[:, 1], x1[:, 0]], 1)
+    rb = np.stack([zero, zero, zero, -x0[:, 0], -x0[:, 1], -one, x1[:, 1] * x0[:, 0], x1[:, 1] * x0[:, 1], x1[:, 1]], 1)
+    return np.stack([ra, rb], 1).reshape(-1, 9)
+
+
+_TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
+
+
+def _orientations(p: np.ndarray) -> np.ndarray:
+    """The 2 x 2 orientation determinant of each of the four triples of four points [4, 2]."""
+    return np.array([(p[j, 0] - p[i, 0]) * (p[k, 1] - p[i, 1]) - (p[j, 1] - p[i, 1]) * (p[k, 0] - p[i, 0])
+                     for i, j, k in _TRIPLES])
+
+
+class Solve4(NamedTuple):
+    """candidates [n, 3, 3] float64 in pixels (unit norm, sign rule), n 0 or 1; pivot: elimination_pivots of the
+    8 x 9 system; orientation: the smallest magnitude of the eight orientation determinants (four triples, two
+    images) in normalised coordinates."""
+    candidates: np.ndarray
+    pivot: float
+    orientation: float
+
+
+def solve4_reference(x0, x1, sample) -> Solve4:
+    """The 4-point solve of the contract in float64: x0, x1 [n, 2] all correspondences of the pair (the Hartley
+    normalisation is over all of them), sample 4 indices. The null vector of the 8 x 9 system by SVD, scaled to
+    the canonical one (h8 = 1 in the normalised frame, which fixes it whatever found the null space),
+    de-normalised by T1⁻¹ Hn T0 to unit norm with the sign rule. A pivot of the elimination below PIVOT_EPS (three
+    collinear points, a repeated index, a true h8 of 0), a sample whose four triples are not oriented alike in
+    both images (the products of the two orientation determinants all positive or all negative: OpenCV's
+    checkSubset), or anything non-finite gives no candidate."""
+    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
+    idx = np.asarray(sample, dtype=np.int64).reshape(4)
+    t0, t1 = _hartley(x0), _hartley(x1)
+    n0, n1 = _apply(t0, x0[idx]), _apply(t1, x1[idx])
+    a = _rows_h(n0, n1)
+    none = np.zeros((0, 3, 3))
+    if not np.isfinite(a).all():
+        return Solve4(none, float("nan"), float("nan"))
+    pivot = elimination_pivots(a)
+    d0, d1 = _orientations(n0), _orientations(n1)
+    orientation = float(min(np.abs(d0).min(), np.abs(d1).min()))
+    prod = np.sign(d0) * np.sign(d1)
+    if not (pivot >= PIVOT_EPS and ((prod > 0).all() or (prod < 0).all())):
+        return Solve4(none, pivot, orientation)
+    v = np.linalg.svd(a)[2][8]
+    with np.errstate(all="ignore"):
+        hn = (v / v[8]).reshape(3, 3)
+        h = _unit(np.linalg.inv(t1) @ hn @ t0) if np.isfinite(hn).all() else None
+    return Solve4(none if h is None else h[None], pivot, orientation)
+
+
+def _refit_h(x0: np.ndarray, x1: np.ndarray):
+    t0, t1 = _hartley(x0), _hartley(x1)
+    a = _rows_h(_apply(t0, x0), _apply(t1, x1))
+    if not (np.isfinite(a).all() and np.isfinite(t0).all() and np.isfinite(t1).all()):
+        return None
+    hn = np.linalg.eigh(a.T @ a)[1][:, 0].reshape(3, 3)
+    with np.errstate(all="ignore"):
+        return _unit(np.linalg.inv(t1) @ hn @ t0)
+
+
+def homography_refit(x0, x1) -> torch.Tensor:
+    """One refit round of the homography's contract on the given correspondences (x0, x1 [n, 2], n >= 4), float64
+    [3, 3]: Hartley normalisation over them, two rows a point, the eigenvector of the smallest eigenvalue of the
+    9 x 9 normal matrix (no rank step), de-normalised by T1⁻¹ Hn T0 to unit norm with the sign rule."""
+    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
+    if len(x0) < MIN_INLIERS_H or len(x0) != len(x1):
+        raise ValueError(f"homography_refit: two sets of n >= {MIN_INLIERS_H} points, got {len(x0)} and {len(x1)}")
+    h = _refit_h(x0, x1)
+    if h is None:
+        raise ValueError("homography_refit: the correspondences give no finite matrix")
+    return torch.from_numpy(h)
+
+
 def _check_params(threshold, hypotheses, refits) -> None:
     if not 0.0 < float(threshold) <= 1e6:
         raise ValueError(f"threshold must be in (0, 1e6] pixels, got {threshold}")
@@ -281,6 +398,46 @@ def ransac_reference(matches, counts, kpts0, kpts1, threshold: float = 3.0, hypo
     return out
 
 
+def homography_reference(matches, counts, kpts0, kpts1, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2,
+                         seed: int = 888) -> HomographyResult:
+    """HomographyRansac(threshold, hypotheses, refits, seed).verify in float64 on the CPU: matches [P, Kmax, 2],
+    counts [P], kpts0 [P, K0, 2], kpts1 [P, K1, 2] -> HomographyResult (H float64). The steps are the header's:
+    gather and normalise, ransac_samples(size=4), solve4_reference, the candidate scored in pixels (the winner: the
+    highest count, then the lowest hypothesis), `refits` rounds of homography_refit's arithmetic over the current
+    inliers (a round with fewer than 4 keeps H and mask). No Levenberg-Marquardt polish."""
+    _check_params(threshold, hypotheses, refits)
+    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
+    out = HomographyResult(torch.zeros((pr, 3, 3), dtype=torch.float64), torch.zeros((pr, kmax), dtype=torch.uint8),
+                           torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr,), dtype=torch.int32),
+                           torch.full((pr,), -1, dtype=torch.int32))
+    thr2 = float(threshold) ** 2
+    for p in range(pr):
+        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
+        n = len(x0)
+        if n < MIN_INLIERS_H:
+            continue
+        best_n, best_h, best_m = -1, -1, None
+        for h, sample in enumerate(ransac_samples(seed, hypotheses, n, size=4).numpy()):
+            for m in solve4_reference(x0, x1, sample).candidates:
+                got = int((_transfer(m, x0, x1) <= thr2).sum())
+                if got > best_n:
+                    best_n, best_h, best_m = got, h, m
+        if best_n < MIN_INLIERS_H:
+            continue
+        m, mask = best_m, _transfer(best_m, x0, x1) <= thr2
+        for _ in range(int(refits)):
+            if int(mask.sum()) < MIN_INLIERS_H:
+                break
+            again = _refit_h(x0[mask], x1[mask])
+            if again is None:
+                break
+            m, mask = again, _transfer(again, x0, x1) <= thr2
+        out.H[p] = torch.from_numpy(m)
+        out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
+        out.num_inliers[p], out.valid[p], out.best[p] = int(mask.sum()), 1, best_h
+    return out
+
+
 # ---- synthetic pairs ------------------------------------------------------------------------------------------------
 def two_view_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
     """Two pinhole views (size = (h, w), focal length w, the second camera turned and moved sideways) of random
@@ -333,20 +490,78 @@ def two_view_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, 
             torch.from_numpy(gt[order]), torch.from_numpy(f_true))
 
 
+def planar_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640),
+                 rotation_only: bool = False):
+    """two_view_scene's twin for the homography: two pinhole views (size = (h, w), focal length w) of points on one
+    random plane (a depth of 5 to 9 at the image centre, tilted by up to 0.3 in x and in y), the second camera
+    turned and moved sideways as two_view_scene's is; rotation_only: the second camera only turned, the points at
+    any depth. From synth.uniform24: (kpts0 [k, 2] fp32, kpts1 [k, 2] fp32, gt_mask [k] bool, H_true [3, 3] float64
+    at unit norm, x1 ~ H_true x0). round(k outlier_fraction) rows are outliers: both ends uniform in the images,
+    redrawn until their transfer error under H_true exceeds 12 px; the inliers are projections moved by at most
+    noise_px in each image; the rows are shuffled."""
+    h, w = int(size[0]), int(size[1])
+    n_out = int(round(k * outlier_fraction))
+    n_in = k - n_out
+    if k < 1 or n_in < 0 or n_out < 0 or noise_px < 0:
+        raise ValueError(f"planar_scene: bad k / outlier_fraction / noise_px {k}, {outlier_fraction}, {noise_px}")
+    pool = 16 * k + 64
+    u = synth.uniform24(int(seed) + (0x9A7A if rotation_only else 0x91A9), 16 + 8 * pool).astype(np.float64)
+    cam, u = u[:16], u[16:].reshape(8, pool)
+    kk = np.array([[w, 0.0, w / 2.0], [0.0, w, h / 2.0], [0.0, 0.0, 1.0]])
+    ang = (cam[:3] - 0.5) * np.array([0.12, 0.5, 0.12]) + np.array([0.0, 0.15, 0.0])  # radians about x, y, z
+    cx, cy, cz = np.cos(ang)
+    sx, sy, sz = np.sin(ang)
+    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    rot = rz @ ry @ rx
+    kinv = np.linalg.inv(kk)
+    if rotation_only:
+        h_true = kk @ rot @ kinv
+    else:  # the plane n · X = d in the first camera's frame, X' = R X + t: H = K (R + t nᵀ / d) K⁻¹
+        t = np.array([-1.0 - cam[3], 0.3 * (cam[4] - 0.5), 0.3 * (cam[5] - 0.5)])
+        n = np.array([-0.6 * (cam[6] - 0.5), -0.6 * (cam[7] - 0.5), 1.0])
+        d = 5.0 + 4.0 * cam[8]
+        h_true = kk @ (rot + np.outer(t, n) / d) @ kinv
+    h_true = _unit(h_true)
+    # inliers: a pixel of image 0 through H_true
+    p0 = np.stack([u[0] * (w - 1), u[1] * (h - 1)], 1)
+    q = np.concatenate([p0, np.ones((pool, 1))], 1) @ h_true.T
+    p1 = q[:, :2] / q[:, 2:3]
+    ok = (q[:, 2] * h_true[2, 2] > 0) & (p1[:, 0] >= 0) & (p1[:, 0] <= w - 1) & (p1[:, 1] >= 0) & (p1[:, 1] <= h - 1)
+    keep = np.nonzero(ok)[0][:n_in]
+    # outliers
+    o0 = np.stack([u[2] * (w - 1), u[3] * (h - 1)], 1)
+    o1 = np.stack([u[4] * (w - 1), u[5] * (h - 1)], 1)
+    with np.errstate(all="ignore"):
+        far = np.nonzero(np.sqrt(_transfer(h_true, o0, o1)) > 12.0)[0][:n_out]
+    if len(keep) < n_in or len(far) < n_out:
+        raise ValueError("planar_scene: the pool ran out (a seed whose second view sees too little)")
+    a = noise_px / np.sqrt(2.0)
+    noise = (u[6:8, :2 * n_in].reshape(2, 2, n_in) * 2.0 - 1.0) * a
+    k0 = np.concatenate([p0[keep] + noise[0].T, o0[far]])
+    k1 = np.concatenate([p1[keep] + noise[1].T, o1[far]])
+    gt = np.concatenate([np.ones(n_in, dtype=bool), np.zeros(n_out, dtype=bool)])
+    order = np.argsort(synth.uniform24(int(seed) + 0x5EED, k), kind="stable")
+    return (torch.from_numpy(k0[order].astype(np.float32)), torch.from_numpy(k1[order].astype(np.float32)),
+            torch.from_numpy(gt[order]), torch.from_numpy(h_true))
+
+
 # ---- the kernels --------------------------------------------------------------------------------------------------
-class FundamentalRansac:
-    """RANSAC for the fundamental matrix of every pair of a MatchResult. threshold: the inlier bound in pixels
-    (the demo's 3); hypotheses: their fixed number per pair (no early termination: the launches do not depend
-    on the data); refits: least-squares rounds over the inliers; seed: of the samples."""
+class _Ransac:
+    """What the two estimators share: the parameters, the checks of verify's inputs and the call. _ENTRY: the C
+    entry point; _RESULT: the NamedTuple of its five outputs."""
+    _ENTRY = ""
+    _RESULT = None
 
     def __init__(self, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2, seed: int = 888) -> None:
         _check_params(threshold, hypotheses, refits)
         self.threshold, self.hypotheses, self.refits = float(threshold), int(hypotheses), int(refits)
         self.seed = int(seed) & _M32
 
-    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor) -> GeometryResult:
+    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor):
         """result.matches [P, Kmax, 2] / result.counts [P] (int32) index kpts0 [P, K0, 2] and kpts1 [P, K1, 2]
-        (fp32, (x, y) in pixels; ImageInput.keypoints' output is the intended one) -> GeometryResult. Two
+        (fp32, (x, y) in pixels; ImageInput.keypoints' output is the intended one) -> the estimator's result. Two
         launches on the current stream, nothing read back; counts and indices are clamped, never trusted."""
         matches, counts = result.matches, result.counts
         require_gpu("matches", matches, _STAGE, (torch.int32,), 3)
@@ -364,11 +579,11 @@ class FundamentalRansac:
             if t.device != matches.device:
                 raise ValueError(f"{name}: on {t.device}, the matches on {matches.device}")
         dev = matches.device
-        out = GeometryResult(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
-                             torch.empty((pr, kmax), dtype=torch.uint8, device=dev),
-                             torch.empty((pr,), dtype=torch.int32, device=dev),
-                             torch.empty((pr,), dtype=torch.int32, device=dev),
-                             torch.empty((pr,), dtype=torch.int32, device=dev))
+        out = self._RESULT(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
+                           torch.empty((pr, kmax), dtype=torch.uint8, device=dev),
+                           torch.empty((pr,), dtype=torch.int32, device=dev),
+                           torch.empty((pr,), dtype=torch.int32, device=dev),
+                           torch.empty((pr,), dtype=torch.int32, device=dev))
         if pr == 0:
             return out
         matches, counts, kpts0, kpts1 = (t.contiguous() for t in (matches, counts, kpts0, kpts1))
@@ -376,16 +591,40 @@ class FundamentalRansac:
         nbytes = int(_lib.load().lg_ransac_workspace(pr, kmax, self.hypotheses))
         ws, = carve(dev, stream, [nbytes])
         seed = self.seed - (1 << 32) if self.seed >= 1 << 31 else self.seed  # the same 32 bits as int32
-        call("lg_ransac_fundamental", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), pr, kmax,
+        call(self._ENTRY, matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), pr, kmax,
              int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses, self.refits, seed, ws.data_ptr(),
              nbytes, *(t.data_ptr() for t in out), stream)
         return out
 
 
-def verify_source_images(image_input: ImageInput, encoder, frontend, matcher, ransac: FundamentalRansac, images0, images1):
+class FundamentalRansac(_Ransac):
+    """RANSAC for the fundamental matrix of every pair of a MatchResult. threshold: the inlier bound in pixels
+    (the demo's 3); hypotheses: their fixed number per pair (no early termination: the launches do not depend
+    on the data); refits: least-squares rounds over the inliers; seed: of the samples. verify -> GeometryResult."""
+    _ENTRY, _RESULT = "lg_ransac_fundamental", GeometryResult
+
+    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor) -> GeometryResult:
+        return super().verify(result, kpts0, kpts1)
+
+    verify.__doc__ = _Ransac.verify.__doc__
+
+class HomographyRansac(_Ransac):
+    """RANSAC for the homography x1 ~ H x0 of every pair of a MatchResult (planar scenes, a rotating camera; what
+    cv::findHomography(pts0, pts1, cv::RANSAC, 3) does on the host, without its final Levenberg-Marquardt polish).
+    The parameters are FundamentalRansac's; verify -> HomographyResult. A pair is valid from 4 inliers on, and a
+    4-inlier winner is only its own sample: threshold num_inliers before trusting H."""
+    _ENTRY, _RESULT = "lg_ransac_homography", HomographyResult
+
+    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor) -> HomographyResult:
+        return super().verify(result, kpts0, kpts1)
+
+    verify.__doc__ = _Ransac.verify.__doc__
+
+def verify_source_images(image_input: ImageInput, encoder, frontend, matcher,
+                         ransac: "FundamentalRansac | HomographyRansac", images0, images1):
     """match_source_images followed by ransac.verify on its outputs: (MatchResult, kpts0_src, kpts1_src,
-    GeometryResult), the fundamental matrices in the source images' own pixels. What replaces the demo's
-    PostProcess + cv::findFundamentalMat (demo/demo_mono.cpp:326-366); nothing is read back, so it enqueues, or
-    is captured, as one piece."""
+    GeometryResult or HomographyResult), the matrices in the source images' own pixels; ransac is a
+    FundamentalRansac or a HomographyRansac. What replaces the demo's PostProcess + cv::findFundamentalMat
+    (demo/demo_mono.cpp:326-366); nothing is read back, so it enqueues, or is captured, as one piece."""
     result, kp0, kp1 = match_source_images(image_input, encoder, frontend, matcher, images0, images1)
     return result, kp0, kp1, ransac.verify(result, kp0, kp1)

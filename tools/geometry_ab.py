@@ -12,7 +12,14 @@ record; verify_eager_us is our arm under the same clock). Arms alternate; --repe
 The pipeline part: 480 x 640 grey sources at the target size, 512 keypoints a side, the seeded 9-layer matcher,
 P = 1 and 2: match_source_images and verify_source_images each captured as one graph, replayed alternately.
 
-    python tools/geometry_ab.py [--repeats 5] [--part all|verify|pipeline] [--out profiles/geometry/ab.jsonl]
+--model homography: the same method for HomographyRansac.verify on planar scenes (the framework arm: an SVD null
+vector per hypothesis, the orientation rule, the transfer error, refits by eigh), with FundamentalRansac.verify
+re-measured at the same K, P and H on the same points in the same repeats, the three arms alternating
+(fundamental_us in the record; the two estimators run the same launches, so the comparison is of the models'
+arithmetic). The pipeline part is the fundamental matrix's alone.
+
+    python tools/geometry_ab.py [--model fundamental|homography] [--repeats 5] [--part all|verify|pipeline]
+                                [--out profiles/geometry/ab.jsonl]
 """
 import argparse
 import json
@@ -25,8 +32,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "lightglue-with-flashattentionv2-tensorrt_amd")]
 import torch  # noqa: E402
 
-from lightglue_amd import (FundamentalRansac, ImageInput, KeypointFrontend, SuperPointEncoder, match_source_images,  # noqa: E402
-                           matcher, ransac_samples, seeded_superpoint_state_dict, two_view_scene, verify_source_images)
+from lightglue_amd import (FundamentalRansac, HomographyRansac, ImageInput, KeypointFrontend, SuperPointEncoder,  # noqa: E402
+                           match_source_images, matcher, planar_scene, ransac_samples, seeded_superpoint_state_dict,
+                           two_view_scene, verify_source_images)
 from lightglue_amd.matches import MatchResult  # noqa: E402
 
 H, R, THR, SEED = 512, 2, 3.0, 888
@@ -109,6 +117,61 @@ def framework_ransac(x0, x1, samples):
     return fb, mask
 
 
+def _rows_h(x0, x1):
+    """[..., n, 2] x 2 -> [..., 2 n, 9]: the two rows a point of x1 ~ H x0."""
+    one, zero = torch.ones_like(x0[..., 0]), torch.zeros_like(x0[..., 0])
+    ra = torch.stack([-x0[..., 0], -x0[..., 1], -one, zero, zero, zero, x1[..., 0] * x0[..., 0], x1[..., 0] * x0[..., 1],
+                      x1[..., 0]], -1)
+    rb = torch.stack([zero, zero, zero, -x0[..., 0], -x0[..., 1], -one, x1[..., 1] * x0[..., 0], x1[..., 1] * x0[..., 1],
+                      x1[..., 1]], -1)
+    return torch.stack([ra, rb], -2).flatten(-3, -2)
+
+
+def _inliers_h(h, x0, x1, thr2):
+    """h [P, C, 3, 3], x [P, K, 2] (fp32) -> [P, C, K] bool."""
+    q = torch.einsum("pcij,pkj->pcki", h, torch.cat([x0, torch.ones_like(x0[..., :1])], -1))
+    err = (x1[:, None, :, 0] - q[..., 0] / q[..., 2]) ** 2 + (x1[:, None, :, 1] - q[..., 1] / q[..., 2]) ** 2
+    return err <= thr2
+
+
+def _orient(p):
+    """p [P, H, 4, 2] -> the orientation determinants of the four triples [P, H, 4]."""
+    out = []
+    for i, j, k in ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3)):
+        a, b = p[..., j, :] - p[..., i, :], p[..., k, :] - p[..., i, :]
+        out.append(a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0])
+    return torch.stack(out, -1)
+
+
+def framework_homography(x0, x1, samples):
+    """x0, x1 [P, K, 2] fp32 on the GPU, samples [H, 4] -> (H [P, 3, 3] fp32, mask [P, K])."""
+    pr, k, _ = x0.shape
+    a0, a1 = x0.double(), x1.double()
+    ones = torch.ones((pr, k), dtype=torch.float64, device=x0.device)
+    t0, t1 = _hartley(a0, ones), _hartley(a1, ones)
+    n0, n1 = _apply(t0, a0)[:, samples], _apply(t1, a1)[:, samples]              # [P, H, 4, 2]
+    v = torch.linalg.svd(_rows_h(n0, n1), full_matrices=True)[2][..., 8, :]      # [P, H, 9]
+    hn = (v / v[..., 8:9]).reshape(pr, -1, 3, 3)
+    prod = torch.sign(_orient(n0)) * torch.sign(_orient(n1))
+    good = (prod > 0).all(-1) | (prod < 0).all(-1)
+    h = torch.linalg.inv(t1)[:, None] @ hn @ t0[:, None]
+    h = (h / h.flatten(-2).norm(dim=-1)[..., None, None]).float()
+    inl = _inliers_h(h, x0, x1, THR * THR)
+    counts = torch.where(good, inl.sum(-1), -1)
+    best = counts.argmax(1)
+    hb = h[torch.arange(pr, device=x0.device), best]
+    mask = inl[torch.arange(pr, device=x0.device), best]
+    for _ in range(R):
+        w = mask.double()
+        t0, t1 = _hartley(a0, w), _hartley(a1, w)
+        rows = _rows_h(_apply(t0, a0), _apply(t1, a1)) * w.repeat_interleave(2, 1)[..., None]
+        he = torch.linalg.eigh(rows.transpose(1, 2) @ rows)[1][..., 0].reshape(pr, 3, 3)
+        hb = torch.linalg.inv(t1) @ he @ t0
+        hb = (hb / hb.flatten(1).norm(dim=1)[:, None, None]).float()
+        mask = _inliers_h(hb[:, None], x0, x1, THR * THR)[:, 0]
+    return hb, mask
+
+
 def graph_of(fn, stream, calls):
     with torch.cuda.stream(stream):
         fn()
@@ -151,6 +214,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "geometry", "ab.jsonl"))
     ap.add_argument("--part", choices=("all", "verify", "pipeline"), default="all")
+    ap.add_argument("--model", choices=("fundamental", "homography"), default="fundamental")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("geometry_ab.py: needs a GPU (timings from anywhere else mean nothing)")
@@ -166,6 +230,9 @@ def main():
             out.write(line + "\n")
 
     fr = FundamentalRansac(THR, H, R, SEED)
+    if args.model == "homography":
+        homography_part(args, dev, stream, base, emit, fr)
+        return
     for k in (256, 1024, 2048) if args.part != "pipeline" else ():
         k0, k1, gt, _ = two_view_scene(k, k, 0.25, 0.25)
         samples = ransac_samples(SEED, H, k).long().to(dev)
@@ -216,6 +283,39 @@ def main():
         emit(dict(base, part="pipeline", P=pr, source=[480, 640], max_keypoints=512, match_counts=counts,
                   match_source_images_us=spread(ta), verify_source_images_us=spread(tb),
                   verify_adds_us=round(mb - ma, 2), verify_share_of_total=round((mb - ma) / mb, 3)))
+
+
+def homography_part(args, dev, stream, base, emit, fr):
+    hr = HomographyRansac(THR, H, R, SEED)
+    for k in (256, 1024, 2048):
+        k0, k1, gt, _ = planar_scene(k, k, 0.25, 0.25)
+        samples = ransac_samples(SEED, H, k, size=4).long().to(dev)
+        for pr in (1, 16):
+            x0, x1 = k0.to(dev)[None].repeat(pr, 1, 1), k1.to(dev)[None].repeat(pr, 1, 1)
+            m = torch.arange(k, dtype=torch.int32, device=dev)[None, :, None].repeat(pr, 1, 2).contiguous()
+            counts = torch.full((pr,), k, dtype=torch.int32, device=dev)
+            res = MatchResult(None, None, None, None, m, None, counts)
+            with torch.no_grad():
+                ours = lambda: hr.verify(res, x0, x1)                   # noqa: E731
+                fund = lambda: fr.verify(res, x0, x1)                   # noqa: E731
+                theirs = lambda: framework_homography(x0, x1, samples)  # noqa: E731
+                mine, (_, their_mask) = ours(), theirs()
+                torch.cuda.synchronize()
+                rec = dict(base, part="verify", model="homography", K=k, P=pr,
+                           ours_mask_is_gt=bool((mine.inliers.bool().cpu() == gt[None]).all()),
+                           framework_mask_is_gt=bool((their_mask.cpu() == gt[None]).all()))
+                g, gf = graph_of(ours, stream, CALLS), graph_of(fund, stream, CALLS)
+                t_ours, t_fund, t_theirs = [], [], []
+                for _ in range(args.repeats):
+                    t_ours.append(time_graph(g, stream, CALLS))
+                    t_fund.append(time_graph(gf, stream, CALLS))
+                    t_theirs.append(time_eager(theirs, 2))
+                rec.update(verify_us=spread(t_ours), fundamental_us=spread(t_fund), framework_us=spread(t_theirs),
+                           framework_mode="eager", verify_eager_us=round(time_eager(ours, 50), 2),
+                           homography_over_fundamental_median=round(statistics.median(t_ours) / statistics.median(t_fund), 3),
+                           framework_over_verify_median=round(statistics.median(t_theirs) / statistics.median(t_ours), 1))
+            emit(rec)
+            del g, gf
 
 
 if __name__ == "__main__":
