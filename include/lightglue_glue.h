@@ -76,7 +76,7 @@ int32_t lg_layernorm_gelu(int32_t dtype, const void* x, const void* gamma, const
                           int32_t dim, float eps, void* y, hipStream_t stream);
 
 /* ---- projections with their neighbours fused (fp16 only; csrc/lightglue_linear.hip; the FFN entry
- * points lg_linear_cat_ln_gelu, lg_linear_cat_ffn*, lg_ffn_pack: csrc/lightglue_ffn.hip) ----
+ * points lg_linear_cat_ln_gelu: csrc/lightglue_ffn_ln.hip; lg_linear_cat_ffn*, lg_ffn_pack: csrc/lightglue_ffn.hip) ----
  * W [n, k] row-major (nn.Linear layout), bias [n]; k in {256, 512}; n a multiple of 64; rows m
  * any. A/W/x/ctx 16-byte aligned, bias/out/res/cos/sin 8-byte aligned.
  * lg_linear:            out [m, n] = A [m, k] · Wᵀ + bias (+ res [m, n] when res != NULL). */

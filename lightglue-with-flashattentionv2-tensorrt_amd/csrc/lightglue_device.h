@@ -1,9 +1,9 @@
 // lightglue_device.h — what more than one of the matcher's kernel files uses (lightglue_linear.hip: the
-// projections, lightglue_ffn.hip: the FFN, lightglue_assign.hip: the assignment and match heads,
-// lightglue_glue.hip: the layout / normalisation kernels): the vector types, the projections' argument
-// block and A-gather, their output arithmetic, the 256-row forms' DMA sources, and the entry points'
-// argument-check and launch-status helpers. Everything sits in an unnamed namespace: each file
-// compiles its own copy, and the kernels' mangled names do not depend on the file they live in.
+// projections, lightglue_ffn_ln.hip and lightglue_ffn.hip: the FFN (what only they share: lightglue_ffn_device.h),
+// lightglue_assign.hip: the assignment and match heads, lightglue_glue.hip: the layout / normalisation
+// kernels): the vector types, the projections' argument block and A-gather, their output arithmetic, the
+// 256-row forms' DMA sources, the entry points' argument-check and launch-status helpers. All in an unnamed
+// namespace: each file compiles its own copy, and the kernels' mangled names do not depend on their file.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@
 
 namespace lightglue {
 // The projections' tile form, forced (0..5) or -1 = chosen by size: lg_linear_set_wide / LG_LINEAR_WIDE
-// (lightglue_linear.hip; lg_linear_cat_ln_gelu in lightglue_ffn.hip reads it too)
+// (lightglue_linear.hip; lg_linear_cat_ln_gelu in lightglue_ffn_ln.hip reads it too)
 __attribute__((visibility("hidden"))) int wide_mode();
 }  // namespace lightglue
 
@@ -87,7 +87,7 @@ __device__ __forceinline__ f16 res_add(f16 v, f16 r) { return (f16)((float)v + (
 // below the fp16 rounding of the output), folded: with z = |x| / sqrt(2), r = 1 / (1 + p z) and
 // erf(z) = 1 - y(r) e^{-z^2}, x Phi(x) = max(x, 0) - |x| (y / 2) e^{-x^2 / 2} for either sign of x (no
 // 1 + erf cancellation for negative x); one v_rcp_f32 and one v_exp_f32, the 1/2 and 1/sqrt(2) in
-// the constants. (lightglue_glue.hip and lightglue_ffn.hip compute it alike: this definition.)
+// the constants. (lightglue_glue.hip and the FFN's files compute it alike: this definition.)
 __device__ __forceinline__ float gelu_as(float x) {
     const float ax = fabsf(x);
     const float r = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, ax, 1.f));

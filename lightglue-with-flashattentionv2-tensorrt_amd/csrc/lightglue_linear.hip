@@ -22,7 +22,7 @@
 // conflict-free ds_read_b128 of 16 rows at one k); the MFMAs of chunk c start once c has
 // landed (counted vmcnt + barrier) while the later chunks stream in.
 //
-// The FFN's own kernels (lg_linear_cat_ln_gelu, lg_linear_cat_ffn*) are in lightglue_ffn.hip, the
+// The FFN's own kernels are in lightglue_ffn_ln.hip (lg_linear_cat_ln_gelu) and lightglue_ffn.hip (lg_linear_cat_ffn*), the
 // assignment and match heads in lightglue_assign.hip; what they share with this file (LinArgs, the
 // A-gather, the output arithmetic, the tile forms' DMA sources) is in lightglue_device.h.
 #include <stdlib.h>

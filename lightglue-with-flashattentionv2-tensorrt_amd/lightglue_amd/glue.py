@@ -65,7 +65,7 @@ class _Hip:
              out.data_ptr(), stream_of(x))
         return out
 
-    # ---- projections with their neighbours fused (fp16; csrc/lightglue_linear.hip, lightglue_ffn.hip) ----
+    # ---- projections with their neighbours fused (fp16; csrc/lightglue_linear.hip, lightglue_ffn_ln.hip, lightglue_ffn.hip) ----
     @staticmethod
     def linear(a, w, b, res=None):
         """a [1, M, K] -> a·wᵀ + b (+ res) [1, M, N]."""

@@ -12,7 +12,7 @@ The store points, each read from the kernel (csrc/):
   folded weights  weights._ffn_in_fused: [W_x | W_m W_p] and b + W_m b_p in fp32, then fp16 (_cached's .to(dtype));
                   the head's [W_final / 4 ; w_match] likewise (MatchAssignment.aug_weights)
   projections     fp16(acc + b), one rounding: lin_val, lightglue_device.h:84 (Wqkv, to_qk | to_v, the FFN's second
-                  layer, the head's rows v; phase 3 of the FFN kernels: lightglue_ffn.hip:689 and :1005-1017)
+                  layer, the head's rows v; phase 3 of the FFN kernels: lightglue_ffn.hip:370 and :644-655)
   rotary          on that fp16 value, in fp16 arithmetic: both products and the sum rounded (rot_pair,
                   lightglue_device.h:126-133); v is the projection's fp16 value as it is
   attention       q~ = fp16(q * kScaleLog2), P = fp16(exp2(s - m)), the row sum and P V from that fp16 P, the context
@@ -20,8 +20,8 @@ The store points, each read from the kernel (csrc/):
                   takes m as the row's true maximum; the kernels' m may trail it by up to 8 log2 units and the
                   single-pass kernels round P * alpha once more: roundings of the same size at other places
   FFN             h = fp16(acc + b1) BEFORE the LayerNorm, whose statistics come from that fp16 h
-                  (lightglue_ffn.hip:278-281); fp16(GELU(LayerNorm(h))) (:578-579); y = fp16(acc + b2) (:615), then the
-                  residual x' = fp16(y + x) as a second rounding (res_add, :629)
+                  (lightglue_ffn.hip:33-36); fp16(GELU(LayerNorm(h))) (:263-264); y = fp16(acc + b2) (:300), then the
+                  residual x' = fp16(y + x) as a second rounding (res_add, :313)
   the head        v = fp16(acc + b) for the 256 scaled channels and the matchability logit; the similarity is rounded
                   to fp16 as it leaves the MFMA accumulators ((f16)acc, lightglue_assign.hip:133: the reference's fp16
                   bmm), and both logsumexps and the combine 2 sim + row term + column term read that fp16 value; the
@@ -225,8 +225,9 @@ def max_err(a, b):
 
 def ffn_rows_form(rows):
     """Which one-launch FFN kernel launch_ffn_rows (lightglue_ffn.hip) takes for `rows` rows, with kTileGrid = 256
-    (lightglue_device.h): 16-row tiles up to 16 * 256 = 4096 rows, their projection split over two workgroups up to
-    64 tiles; 32-row tiles up to 32 * 256 = 8192 rows; 64-row tiles beyond."""
+    (lightglue_device.h): 16-row tiles up to kRows16Round = 16 * 256 = 4096 rows, their projection split over two
+    workgroups up to 64 tiles (ffn_split_parts); 32-row tiles up to kRows32Round = 32 * 256 = 8192 rows; 64-row
+    tiles beyond."""
     if rows <= 16 * 256:
         return "rows16 split" if (rows + 15) // 16 <= 64 else "rows16"
     return "rows32" if rows <= 32 * 256 else "rows64"

@@ -1,5 +1,5 @@
-"""The fp16 projection, LayerNorm + GELU and FFN kernels on the MI355X (csrc/lightglue_linear.hip, lightglue_ffn.hip, the
-row kernels of lightglue_glue.hip, with lightglue_device.h) against exact arithmetic: every reference is float64 on the
+"""The fp16 projection, LayerNorm + GELU and FFN kernels on the MI355X (csrc/lightglue_linear.hip, lightglue_ffn_ln.hip,
+lightglue_ffn.hip, the row kernels of lightglue_glue.hip, with lightglue_device.h) against exact arithmetic: every reference is float64 on the
 CPU, computed here (tests/projection_refs.py) from the fp16 operands the kernel reads. Nothing reads the reference
 tree and no reference comes from a GPU GEMM. tests/test_projections_reference.py shows on the CPU that each bound
 below accepts the stated arithmetic in fp32 and rejects fp16 partial sums, a dropped k-slice, a neighbour's residual

@@ -300,7 +300,7 @@ def test_glue_kernels_match_torch(dtype):
         ref = torch.nn.functional.gelu(ln(hx).float()).to(dt)
         tol_ln = 2e-2 if dtype == "float16" else 1e-4
         assert float((mt._Hip.layernorm_gelu(hx, ln).float() - ref.float()).abs().max()) <= tol_ln
-        if dtype == "float16":  # the fused projections (csrc/lightglue_linear.hip, lightglue_ffn.hip, fp16 only)
+        if dtype == "float16":  # the fused projections (csrc/lightglue_linear.hip, lightglue_ffn_ln.hip, lightglue_ffn.hip, fp16 only)
             _check_fused_linear(mt, blk, dev, rnd, n0, n1, h)
             _check_fused_linear(mt, blk, dev, rnd, 700, 1301, h)
         for m_, n_ in ((130, 211), (1024, 777), (1, 2000), (2000, 5)):  # column pass: 128-row chunks

@@ -1,5 +1,5 @@
 """Diagnostic: where ffn_rows_kernel's time goes (stamps build, -DLG_FR_STAMPS: per wave, s_memtime
-cycles of chained segments; see csrc/lightglue_ffn.hip).
+cycles of chained segments; see csrc/lightglue_ffn.hip, the stamps themselves in csrc/lightglue_ffn_device.h).
 
     make -C lightglue-with-flashattentionv2-tensorrt_amd variant SRC=lightglue_ffn NAME=frstamps DEFS=-DLG_FR_STAMPS
 

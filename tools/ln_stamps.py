@@ -1,7 +1,8 @@
 """Diagnostic: where the one-launch FFN kernel's time goes (linear_ln_kernel stamps build,
--DLG_LN_STAMPS: per wave, s_memtime cycles of chained segments; see csrc/lightglue_ffn.hip).
+-DLG_LN_STAMPS: per wave, s_memtime cycles of chained segments; see csrc/lightglue_ffn_ln.hip, the stamps
+themselves in csrc/lightglue_ffn_device.h).
 
-    make -C lightglue-with-flashattentionv2-tensorrt_amd variant SRC=lightglue_ffn NAME=lnstamps DEFS=-DLG_LN_STAMPS
+    make -C lightglue-with-flashattentionv2-tensorrt_amd variant SRC=lightglue_ffn_ln NAME=lnstamps DEFS=-DLG_LN_STAMPS
 
     MHA_HD64_LIB=lib/ab/libmha_hd64_lnstamps.so python tools/ln_stamps.py [P=16] [n=1024]
 """
