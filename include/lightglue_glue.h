@@ -555,6 +555,68 @@ int32_t lg_ransac_score_homography(const int32_t* matches, const int32_t* counts
                                    int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* candidates,
                                    int32_t num_candidates, float threshold, int32_t* inlier_counts, hipStream_t stream);
 
+/* The calibrated relative pose (csrc/lightglue_essential.hip): an essential matrix per pair by five-point RANSAC
+ * and (R, t) from it, for callers who know their cameras (visual odometry, localisation, pose-AUC evaluation).
+ * Five points need far fewer hypotheses than seven at the same outlier rate, and the five-point solve is not
+ * degenerate on planar scenes, which the 7- and 8-point solves are. Inputs, clamping, limits and alignment are
+ * lg_ransac_fundamental's, and so is every general statement above (arguments checked first, a no-op for
+ * pairs == 0, counts and indices clamped, no atomics, no allocation, every output entry written).
+ * lightglue_amd/geometry.py restates the contract in float64 (essential_reference).
+ *
+ * Extra input: intrinsics [pairs, 2, 4] fp32, (fx, fy, cx, cy) of image 0 then image 1 in the pixel frame of the
+ * keypoints. Model: x1ᵀ E x0 = 0 in camera coordinates q = ((x - cx) / fx, (y - cy) / fy) (fp64), E row-major;
+ * X1 = R X0 + t, |t| = 1, det R = +1, E ∝ [t]x R. Canonical: unit Frobenius norm with the sign rule of f. Per pair:
+ *   1. Gather as above. Fewer than 5 correspondences, an intrinsic that is not finite or a focal length <= 0:
+ *      the pair is invalid, every output zeros and best = -1.
+ *   2. Hypothesis h samples 5 distinct indices: the first five draws of step 2 above (ransac_samples5).
+ *   3. The five-point solve, fp64: the null space of the 5 x 9 system by Gauss-Jordan with row pivoting on columns
+ *      0..4, made orthonormal; E = x X + y Y + z Z + W; the ten cubic constraints det E = 0 and
+ *      2 E Eᵀ E - tr(E Eᵀ) E = 0 as a 10 x 20 matrix, eliminated by Gauss-Jordan with row pivoting; the real roots z
+ *      of the resulting degree-10 polynomial within its Cauchy bound (brackets from the roots of the successive
+ *      derivatives, 36 bisections and 5 bracketed Newton steps each: every loop has a compile-time bound); (x, y)
+ *      from the null vector at the root. A pivot of either elimination below 1e-6 or a non-finite value: no
+ *      candidate. 0 to 10 candidates.
+ *   4. Each candidate is scored in pixels as F = K1⁻ᵀ E K0⁻¹ at unit norm, fp32, with the error and threshold² of
+ *      the fundamental matrix. The winner: the highest count, then the lowest hypothesis, then the candidate whose
+ *      canonical E has the smallest entry [0, 0].
+ *   5. `refits` rounds: with at least 8 inliers, the normalised 8-point least squares of step 5 above on the
+ *      Hartley-normalised camera coordinates of the inliers, de-normalised, then the nearest essential matrix
+ *      (singular values (1, 1, 0), a one-sided Jacobi SVD). A round whose E counts fewer inliers than the current
+ *      one, or is not finite, is dropped and the rounds stop: on a planar scene the 8-point fit is degenerate and
+ *      the five-point winner stays.
+ *   6. The pose: E = U diag(1, 1, 0) Vᵀ with det U = det V = +1, W the quarter turn about z; of (U W Vᵀ, +u3),
+ *      (U W Vᵀ, -u3), (U Wᵀ Vᵀ, +u3), (U Wᵀ Vᵀ, -u3) the one under which the most inliers triangulate (the midpoint
+ *      method: the least-squares depths of d0 R a - d1 b = -t for the rays a = (q0, 1), b = (q1, 1)) to a positive
+ *      depth in both cameras, the lowest index among equals; num_front is that count.
+ *   7. valid = 1 from 5 inliers on. A 5-inlier winner is only its own sample: callers should threshold num_inliers.
+ * Not built: a non-linear polish of the pose, and the choice between the two solutions a plane admits. */
+/* Bytes of lg_ransac_essential's workspace (0 for an empty call): a hypothesis' record holds F and E. */
+size_t lg_ransac_essential_workspace(int32_t pairs, int32_t kmax, int32_t hypotheses);
+/* lg_ransac_essential: two launches, the shapes of lg_ransac_fundamental's (the four lanes of a hypothesis hold five
+ * columns of the 10 x 20 matrix each). Parameters as there. Outputs: e, r [pairs, 3, 3], t [pairs, 3] fp32 (e
+ * canonical), inliers [pairs, kmax] uint8, num_inliers, num_front, valid, best [pairs] int32. */
+int32_t lg_ransac_essential(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                            const float* intrinsics, int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold,
+                            int32_t hypotheses, int32_t refits, int32_t seed, void* workspace, size_t workspace_bytes, float* e,
+                            float* r, float* t, uint8_t* inliers, int32_t* num_inliers, int32_t* num_front, int32_t* valid,
+                            int32_t* best, hipStream_t stream);
+/* Stage hooks over the same device code (tests). lg_ransac_samples5: step 2 for one count in [5, 2048] ->
+ * samples [hypotheses, 5] int32 in draw order. */
+int32_t lg_ransac_samples5(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream);
+/* lg_ransac_solve5: step 3 on given samples [hypotheses, 5] int32 (device; clamped into [0, count), shared by the
+ * pairs) -> candidates [pairs, hypotheses, 10, 9] fp32, canonical E in camera coordinates (those that exist first,
+ * in ascending root, the rest zeros) and num [pairs, hypotheses] int32. An invalid pair: zeros. Step 4 needs no
+ * hook: lg_ransac_score takes the F of a candidate. */
+int32_t lg_ransac_solve5(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                         const float* intrinsics, int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples,
+                         int32_t hypotheses, float* candidates, int32_t* num, hipStream_t stream);
+/* lg_pose_from_essential: step 6 for given e [pairs, 3, 3] fp32 (any scale and sign) over the correspondences with
+ * inliers [pairs, kmax] uint8 != 0 -> r [pairs, 3, 3], t [pairs, 3] fp32 and num_front [pairs] int32 (zeros where e
+ * has no decomposition or an intrinsic is bad). One launch. */
+int32_t lg_pose_from_essential(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                               const float* intrinsics, int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* e,
+                               const uint8_t* inliers, float* r, float* t, int32_t* num_front, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

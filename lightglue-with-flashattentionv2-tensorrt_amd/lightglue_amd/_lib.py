@@ -199,6 +199,13 @@ SIGNATURES.update({
     "lg_ransac_samples4": ([_I, _I, _I, _P, _P], _I),
     "lg_ransac_solve4": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P], _I),
     "lg_ransac_score_homography": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, ctypes.c_float, _P, _P], _I),
+    # the calibrated relative pose (csrc/lightglue_essential.hip)
+    "lg_ransac_essential_workspace": ([_I, _I, _I], _S),
+    "lg_ransac_essential": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, _I, _I, _I, _P, _S, _P, _P, _P, _P, _P, _P, _P,
+                             _P, _P], _I),
+    "lg_ransac_samples5": ([_I, _I, _I, _P, _P], _I),
+    "lg_ransac_solve5": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P], _I),
+    "lg_pose_from_essential": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

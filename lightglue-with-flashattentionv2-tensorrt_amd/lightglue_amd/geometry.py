@@ -17,6 +17,13 @@ where the epipolar constraint is degenerate): ``cv::findHomography(pts0, pts1, c
 Levenberg-Marquardt polish. Its float64 contract: ``ransac_samples(size=4)``, ``transfer_error``,
 ``solve4_reference`` (an SVD null vector scaled to the canonical one, not the kernel's elimination),
 ``homography_refit`` and ``homography_reference``; ``planar_scene`` makes its pairs.
+
+``EssentialRansac.verify`` is the calibrated case (csrc/lightglue_essential.hip): five-point RANSAC for the essential
+matrix and the relative pose (R, t) from it, given each image's (fx, fy, cx, cy). Its float64 contract:
+``ransac_samples5``, ``solve5_reference`` (an SVD null space, the ten constraints by generic polynomial products, the
+eigenvalues of the cubic matrix pencil in the hidden variable: not the kernel's elimination and degree-10
+polynomial), ``essential_refit``, ``pose_from_essential_reference`` and ``essential_reference``;
+``calibrated_scene`` and ``calibrated_planar_scene`` are the scenes above with their cameras.
 """
 from __future__ import annotations
 
@@ -36,6 +43,7 @@ MAX_HYPOTHESES = 4096
 MAX_REFITS = 8
 MIN_INLIERS = 8         # a fundamental matrix, and its refit, needs 8 correspondences
 MIN_INLIERS_H = 4       # a homography, and its refit, needs 4
+MIN_INLIERS_E = 5       # an essential matrix needs 5 (its refit 8, as the fundamental matrix's)
 PIVOT_EPS = 1e-6        # a pivot of the 7 x 9 (8 x 9) elimination below this: no candidate
 _M32 = 0xFFFFFFFF
 
@@ -59,6 +67,23 @@ class HomographyResult(NamedTuple):
     H: torch.Tensor
     inliers: torch.Tensor
     num_inliers: torch.Tensor
+    valid: torch.Tensor
+    best: torch.Tensor
+
+
+class PoseResult(NamedTuple):
+    """E [P, 3, 3] (x1ᵀ E x0 = 0 in camera coordinates, canonical: unit Frobenius norm, the entry of the largest
+    magnitude positive), R [P, 3, 3] and t [P, 3] (X1 = R X0 + t, det R = +1, |t| = 1, E ∝ [t]× R), inliers [P, Kmax]
+    uint8 aligned with the rows of MatchResult.matches (0 past the count), num_inliers, num_front (the inliers that
+    triangulate in front of both cameras under (R, t)), valid, best [P] int32 (best: the winning hypothesis, -1 where
+    valid == 0; every other output is zeros there). A pair is valid from 5 inliers on, and a 5-inlier winner is
+    only its own sample: threshold num_inliers (and num_front) before trusting the pose."""
+    E: torch.Tensor
+    R: torch.Tensor
+    t: torch.Tensor
+    inliers: torch.Tensor
+    num_inliers: torch.Tensor
+    num_front: torch.Tensor
     valid: torch.Tensor
     best: torch.Tensor
 
@@ -87,6 +112,10 @@ def ransac_samples(seed: int, hypotheses: int, count: int, size: int = 7) -> tor
         raise ValueError(f"ransac_samples: size is 4 or 7, got {size}")
     if count < size or hypotheses < 1:
         raise ValueError(f"ransac_samples: count >= {size} and hypotheses >= 1, got {count} and {hypotheses}")
+    return _samples(seed, hypotheses, count, size)
+
+
+def _samples(seed: int, hypotheses: int, count: int, size: int) -> torch.Tensor:
     h = np.arange(hypotheses, dtype=np.uint64)
     out = np.zeros((hypotheses, size), dtype=np.int64)
     for j in range(size):
@@ -96,6 +125,15 @@ def ransac_samples(seed: int, hypotheses: int, count: int, size: int = 7) -> tor
             r = r + (r >= earlier[:, e])
         out[:, j] = r
     return torch.from_numpy(out.astype(np.int32))
+
+
+def ransac_samples5(seed: int, hypotheses: int, count: int) -> torch.Tensor:
+    """[H, 5] int32: hypothesis h's five distinct indices in [0, count) for the essential matrix, by
+    ransac_samples' rule (count >= 5): for count >= 7 the first five columns of its 7-sample."""
+    seed, hypotheses, count = int(seed), int(hypotheses), int(count)
+    if count < 5 or hypotheses < 1:
+        raise ValueError(f"ransac_samples5: count >= 5 and hypotheses >= 1, got {count} and {hypotheses}")
+    return _samples(seed, hypotheses, count, 5)
 
 
 # ---- the contract's pieces in float64 ---------------------------------------------------------------------------
@@ -340,6 +378,216 @@ def homography_refit(x0, x1) -> torch.Tensor:
     return torch.from_numpy(h)
 
 
+# ---- the essential matrix's pieces in float64 -------------------------------------------------------------------
+def _intrinsics_ok(k: np.ndarray) -> bool:
+    return bool(np.isfinite(k).all() and (k[:, :2] > 0).all())
+
+
+def camera_coordinates(pts, intrinsics) -> np.ndarray:
+    """pts [n, 2] in pixels under (fx, fy, cx, cy) -> ((x - cx) / fx, (y - cy) / fy), float64 [n, 2]."""
+    p, k = _np(pts).reshape(-1, 2), _np(intrinsics).reshape(4)
+    with np.errstate(all="ignore"):
+        return (p - k[2:4]) / k[0:2]
+
+
+def _kinv(k: np.ndarray) -> np.ndarray:
+    return np.array([[1.0 / k[0], 0.0, -k[2] / k[0]], [0.0, 1.0 / k[1], -k[3] / k[1]], [0.0, 0.0, 1.0]])
+
+
+def essential_to_fundamental(E, intrinsics) -> torch.Tensor:
+    """F = K1⁻ᵀ E K0⁻¹ at unit Frobenius norm with the sign rule, float64 [3, 3]: the matrix a candidate E (camera
+    coordinates, intrinsics [2, 4] = (fx, fy, cx, cy) of image 0 then image 1) is scored with in pixels."""
+    k = _np(intrinsics).reshape(2, 4)
+    f = _unit(_kinv(k[1]).T @ _np(E).reshape(3, 3) @ _kinv(k[0]))
+    if f is None:
+        raise ValueError("essential_to_fundamental: the matrix is zero or not finite")
+    return torch.from_numpy(f)
+
+
+def _f_of_e(e: np.ndarray, k: np.ndarray):
+    with np.errstate(all="ignore"):
+        return _unit(_kinv(k[1]).T @ e @ _kinv(k[0]))
+
+
+def _pmul(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """The product of two polynomials in (x, y, z), each an array indexed by the three exponents."""
+    out = np.zeros(tuple(i + j - 1 for i, j in zip(a.shape, b.shape)))
+    for idx in np.ndindex(*a.shape):
+        if a[idx] != 0.0:
+            out[idx[0]:idx[0] + b.shape[0], idx[1]:idx[1] + b.shape[1], idx[2]:idx[2] + b.shape[2]] += a[idx] * b
+    return out
+
+
+def essential_constraints(basis: np.ndarray):
+    """The ten cubic constraints on E = x basis[0] + y basis[1] + z basis[2] + basis[3] (basis [4, 3, 3]): det E = 0
+    and the nine entries of 2 E Eᵀ E - tr(E Eᵀ) E = 0, each a polynomial [4, 4, 4] indexed by the exponents of
+    (x, y, z), by generic polynomial products."""
+    e = [[None] * 3 for _ in range(3)]
+    for i in range(3):
+        for j in range(3):
+            p = np.zeros((2, 2, 2))
+            p[1, 0, 0], p[0, 1, 0], p[0, 0, 1], p[0, 0, 0] = basis[0, i, j], basis[1, i, j], basis[2, i, j], basis[3, i, j]
+            e[i][j] = p
+    eet = [[sum(_pmul(e[i][k], e[j][k]) for k in range(3)) for j in range(3)] for i in range(3)]
+    tr = eet[0][0] + eet[1][1] + eet[2][2]
+    out = [_pmul(e[0][0], _pmul(e[1][1], e[2][2]) - _pmul(e[1][2], e[2][1]))
+           - _pmul(e[0][1], _pmul(e[1][0], e[2][2]) - _pmul(e[1][2], e[2][0]))
+           + _pmul(e[0][2], _pmul(e[1][0], e[2][1]) - _pmul(e[1][1], e[2][0]))]
+    for i in range(3):
+        for j in range(3):
+            out.append(sum(_pmul(2.0 * eet[i][k] - (tr if i == k else 0.0), e[k][j]) for k in range(3)))
+    return out
+
+
+def essential_residuals(E) -> Tuple[float, float]:
+    """(|det E|, the largest magnitude among the entries of 2 E Eᵀ E - tr(E Eᵀ) E) of a 3 x 3 matrix."""
+    e = _np(E).reshape(3, 3)
+    return float(abs(np.linalg.det(e))), float(np.abs(2.0 * e @ e.T @ e - np.trace(e @ e.T) * e).max())
+
+
+_XY_MONOMIALS = ((3, 0), (2, 1), (1, 2), (0, 3), (2, 0), (1, 1), (0, 2), (1, 0), (0, 1), (0, 0))
+
+
+class Solve5(NamedTuple):
+    """candidates [n, 3, 3] float64 in camera coordinates (canonical: unit norm, sign rule), ascending in their
+    entry [0, 0]; eigenvalues: the finite eigenvalues of the pencil, complex (the hidden variable at every
+    solution, real or not); pivot: elimination_pivots of the 5 x 9 system; ratio: its smallest singular value over
+    its largest."""
+    candidates: np.ndarray
+    eigenvalues: np.ndarray
+    pivot: float
+    ratio: float
+
+
+def solve5_reference(q0, q1, sample) -> Solve5:
+    """The five-point solve of the contract in float64: q0, q1 [n, 2] the pair's correspondences in camera
+    coordinates, sample 5 indices. The 4-dimensional null space by SVD; the ten cubic constraints by generic
+    polynomial products (essential_constraints); z hidden: C(z) m = 0 for the ten monomials m of (x, y) up to degree
+    3, a cubic matrix pencil whose real finite eigenvalues (scipy.linalg.eig on its linearisation) are the
+    solutions' z, with (x, y) read off the eigenvector. Deliberately not the kernel's elimination and degree-10
+    polynomial. A pivot of the 5 x 9 elimination below PIVOT_EPS, or anything non-finite, gives no candidate."""
+    from scipy.linalg import eig
+
+    q0, q1 = _np(q0).reshape(-1, 2), _np(q1).reshape(-1, 2)
+    idx = np.asarray(sample, dtype=np.int64).reshape(5)
+    a = _rows(q0[idx], q1[idx])
+    none = np.zeros((0, 3, 3))
+    if not np.isfinite(a).all():
+        return Solve5(none, np.zeros((0,), dtype=complex), float("nan"), float("nan"))
+    pivot = elimination_pivots(a)
+    _, sv, vt = np.linalg.svd(a)
+    ratio = float(sv[4] / sv[0]) if sv[0] > 0 else 0.0
+    basis = vt[5:9].reshape(4, 3, 3)
+    cons = essential_constraints(basis)
+    c = np.zeros((4, 10, 10))
+    for r, poly in enumerate(cons):
+        for m, (ex, ey) in enumerate(_XY_MONOMIALS):
+            for d in range(4 - ex - ey):
+                c[d, r, m] = poly[ex, ey, d]
+    eye, zero = np.eye(10), np.zeros((10, 10))
+    lhs = np.block([[zero, eye, zero], [zero, zero, eye], [-c[0], -c[1], -c[2]]])
+    rhs = np.block([[eye, zero, zero], [zero, eye, zero], [zero, zero, c[3]]])
+    with np.errstate(all="ignore"):
+        (alpha, beta), vec = eig(lhs, rhs, homogeneous_eigvals=True)
+        finite = np.abs(beta) > 1e-9 * np.abs(alpha)
+        values = (alpha[finite] / beta[finite]).astype(complex)
+        vec = vec[:, finite]
+    cands = []
+    if pivot >= PIVOT_EPS:
+        for z, v in zip(values, vec.T):
+            if abs(z.imag) > 1e-9 * max(1.0, abs(z)):
+                continue
+            with np.errstate(all="ignore"):
+                m = v[:10] / v[9]
+                x, y = float(m[7].real), float(m[8].real)
+                e = _unit(x * basis[0] + y * basis[1] + float(z.real) * basis[2] + basis[3])
+            if e is not None:
+                cands.append(e)
+    cands.sort(key=lambda e: e[0, 0])
+    return Solve5(np.array(cands).reshape(-1, 3, 3), values, pivot, ratio)
+
+
+def _project_essential(e: np.ndarray) -> np.ndarray:
+    u, _, vt = np.linalg.svd(e)
+    return u @ np.diag([1.0, 1.0, 0.0]) @ vt
+
+
+def _refit_e(q0: np.ndarray, q1: np.ndarray):
+    t0, t1 = _hartley(q0), _hartley(q1)
+    a = _rows(_apply(t0, q0), _apply(t1, q1))
+    if not (np.isfinite(a).all() and np.isfinite(t0).all() and np.isfinite(t1).all()):
+        return None
+    e = t1.T @ np.linalg.eigh(a.T @ a)[1][:, 0].reshape(3, 3) @ t0
+    if not np.isfinite(e).all():
+        return None
+    return _unit(_project_essential(e))
+
+
+def essential_refit(q0, q1) -> torch.Tensor:
+    """One refit round of the essential matrix's contract on the given correspondences in camera coordinates (q0,
+    q1 [n, 2], n >= 8), float64 [3, 3]: Hartley normalisation over them, the eigenvector of the smallest eigenvalue
+    of the 9 x 9 normal matrix, de-normalised, then the nearest essential matrix (singular values (1, 1, 0)),
+    canonical (unit norm, sign rule)."""
+    q0, q1 = _np(q0).reshape(-1, 2), _np(q1).reshape(-1, 2)
+    if len(q0) < MIN_INLIERS or len(q0) != len(q1):
+        raise ValueError(f"essential_refit: two sets of n >= {MIN_INLIERS} points, got {len(q0)} and {len(q1)}")
+    e = _refit_e(q0, q1)
+    if e is None:
+        raise ValueError("essential_refit: the correspondences give no finite matrix")
+    return torch.from_numpy(e)
+
+
+def _depths(r: np.ndarray, t: np.ndarray, q0: np.ndarray, q1: np.ndarray):
+    """The depths (d0, d1) of each correspondence's midpoint triangulation under X1 = R X0 + t: the least-squares
+    solution of d0 R a - d1 b = -t for the rays a = (q0, 1), b = (q1, 1)."""
+    a = np.concatenate([q0, np.ones((len(q0), 1))], 1) @ r.T
+    b = np.concatenate([q1, np.ones((len(q1), 1))], 1)
+    with np.errstate(all="ignore"):
+        aa, bb, ab, at, bt = (a * a).sum(1), (b * b).sum(1), (a * b).sum(1), a @ t, b @ t
+        det = aa * bb - ab * ab
+        return (ab * bt - bb * at) / det, (aa * bt - ab * at) / det
+
+
+def pose_candidates(E):
+    """The four (R, t) of an essential matrix: E = U diag(1, 1, 0) Vᵀ with det U and det V positive, W the quarter
+    turn about z: (U W Vᵀ, +u3), (U W Vᵀ, -u3), (U Wᵀ Vᵀ, +u3), (U Wᵀ Vᵀ, -u3)."""
+    u, _, vt = np.linalg.svd(_np(E).reshape(3, 3))
+    if np.linalg.det(u) < 0:
+        u[:, 2] = -u[:, 2]
+    if np.linalg.det(vt) < 0:
+        vt[2] = -vt[2]
+    w = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    ra, rb, u3 = u @ w @ vt, u @ w.T @ vt, u[:, 2].copy()
+    return [(ra, u3), (ra, -u3), (rb, u3), (rb, -u3)]
+
+
+def pose_from_essential_reference(E, q0, q1):
+    """(R [3, 3], t [3], num_front, the four counts) in float64: of pose_candidates(E), the one under which the
+    most correspondences (q0, q1 [n, 2], camera coordinates) triangulate (_depths: the midpoint method) to a
+    positive depth in both cameras; the lowest index among equals. X1 = R X0 + t, |t| = 1, det R = +1."""
+    q0, q1 = _np(q0).reshape(-1, 2), _np(q1).reshape(-1, 2)
+    cands = pose_candidates(E)
+    counts = []
+    for r, t in cands:
+        d0, d1 = _depths(r, t, q0, q1)
+        counts.append(int(((d0 > 0) & (d1 > 0)).sum()))
+    i = int(np.argmax(counts))
+    return torch.from_numpy(cands[i][0].copy()), torch.from_numpy(cands[i][1].copy()), counts[i], counts
+
+
+def rotation_angle_deg(ra, rb) -> float:
+    """The angle of the rotation Raᵀ Rb in degrees: |Ra - Rb| = 2 sqrt 2 sin(angle / 2) in the Frobenius norm (exact
+    for small angles, where the arc cosine of the trace is not)."""
+    d = np.linalg.norm(_np(ra).reshape(3, 3) - _np(rb).reshape(3, 3))
+    return float(np.degrees(2.0 * np.arcsin(min(1.0, d / (2.0 * np.sqrt(2.0))))))
+
+
+def direction_angle_deg(ta, tb) -> float:
+    """The angle between two directions in degrees: |a - b| = 2 sin(angle / 2) at unit length."""
+    a, b = _np(ta).reshape(3), _np(tb).reshape(3)
+    return float(np.degrees(2.0 * np.arcsin(min(1.0, np.linalg.norm(a / np.linalg.norm(a) - b / np.linalg.norm(b)) / 2.0))))
+
+
 def _check_params(threshold, hypotheses, refits) -> None:
     if not 0.0 < float(threshold) <= 1e6:
         raise ValueError(f"threshold must be in (0, 1e6] pixels, got {threshold}")
@@ -438,7 +686,81 @@ def homography_reference(matches, counts, kpts0, kpts1, threshold: float = 3.0, 
     return out
 
 
+def essential_reference(matches, counts, kpts0, kpts1, intrinsics, threshold: float = 3.0, hypotheses: int = 512,
+                        refits: int = 2, seed: int = 888) -> PoseResult:
+    """EssentialRansac(threshold, hypotheses, refits, seed).verify in float64 on the CPU: matches [P, Kmax, 2],
+    counts [P], kpts0 [P, K0, 2], kpts1 [P, K1, 2], intrinsics [P, 2, 4] -> PoseResult (E, R, t float64). The steps
+    are the header's: gather, camera coordinates, ransac_samples5, solve5_reference, every candidate scored in
+    pixels as essential_to_fundamental's F (the winner: the highest count, then the lowest hypothesis, then the
+    candidate whose canonical E has the smallest entry [0, 0]), `refits` rounds of essential_refit's arithmetic over
+    the current inliers (a round with fewer than 8 stops; a round whose E counts fewer inliers than the current one
+    is dropped and the rounds stop: on a planar scene the 8-point fit is degenerate and the five-point winner
+    stays), the pose by pose_from_essential_reference over the inliers. A pair with fewer than 5 correspondences, or with an intrinsic
+    that is not finite or a focal length <= 0, is invalid."""
+    _check_params(threshold, hypotheses, refits)
+    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
+    out = PoseResult(torch.zeros((pr, 3, 3), dtype=torch.float64), torch.zeros((pr, 3, 3), dtype=torch.float64),
+                     torch.zeros((pr, 3), dtype=torch.float64), torch.zeros((pr, kmax), dtype=torch.uint8),
+                     torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr,), dtype=torch.int32),
+                     torch.zeros((pr,), dtype=torch.int32), torch.full((pr,), -1, dtype=torch.int32))
+    thr2 = float(threshold) ** 2
+    for p in range(pr):
+        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
+        kk = _np(intrinsics[p]).reshape(2, 4)
+        n = len(x0)
+        if n < MIN_INLIERS_E or not _intrinsics_ok(kk):
+            continue
+        q0, q1 = camera_coordinates(x0, kk[0]), camera_coordinates(x1, kk[1])
+
+        def mask_of(e):
+            f = _f_of_e(e, kk)
+            return np.zeros(n, dtype=bool) if f is None else _epi(f, x0, x1) <= thr2
+
+        best_n, best_h, best_e = -1, -1, None
+        for h, sample in enumerate(ransac_samples5(seed, hypotheses, n).numpy()):
+            for e in solve5_reference(q0, q1, sample).candidates:
+                got = int(mask_of(e).sum())
+                if got > best_n:
+                    best_n, best_h, best_e = got, h, e
+        if best_n < MIN_INLIERS_E:
+            continue
+        e, mask = best_e, mask_of(best_e)
+        for _ in range(int(refits)):
+            if int(mask.sum()) < MIN_INLIERS:
+                break
+            again = _refit_e(q0[mask], q1[mask])
+            if again is None:
+                break
+            mask_again = mask_of(again)
+            if int(mask_again.sum()) < int(mask.sum()):
+                break
+            e, mask = again, mask_again
+        r, t, front, _ = pose_from_essential_reference(e, q0[mask], q1[mask])
+        out.E[p], out.R[p], out.t[p] = torch.from_numpy(e), r, t
+        out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
+        out.num_inliers[p], out.num_front[p], out.valid[p], out.best[p] = int(mask.sum()), front, 1, best_h
+    return out
+
+
 # ---- synthetic pairs ------------------------------------------------------------------------------------------------
+def _scene_camera(cam: np.ndarray, h: int, w: int):
+    """The scenes' intrinsics (focal length w, the centre of the image) and the second camera's rotation from the
+    first draws of the stream."""
+    kk = np.array([[w, 0.0, w / 2.0], [0.0, w, h / 2.0], [0.0, 0.0, 1.0]])
+    ang = (cam[:3] - 0.5) * np.array([0.12, 0.5, 0.12]) + np.array([0.0, 0.15, 0.0])  # radians about x, y, z
+    cx, cy, cz = np.cos(ang)
+    sx, sy, sz = np.sin(ang)
+    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return kk, rz @ ry @ rx
+
+
+def _scene_shift(cam: np.ndarray) -> np.ndarray:
+    """The second camera's translation (X1 = R X0 + t): sideways."""
+    return np.array([-1.0 - cam[3], 0.3 * (cam[4] - 0.5), 0.3 * (cam[5] - 0.5)])
+
+
 def two_view_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
     """Two pinhole views (size = (h, w), focal length w, the second camera turned and moved sideways) of random
     3D points, from synth.uniform24: (kpts0 [k, 2] fp32, kpts1 [k, 2] fp32, gt_mask [k] bool, F_true [3, 3]
@@ -453,15 +775,8 @@ def two_view_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, 
     pool = 16 * k + 64
     u = synth.uniform24(int(seed), 16 + 9 * pool).astype(np.float64)
     cam, u = u[:16], u[16:].reshape(9, pool)
-    kk = np.array([[w, 0.0, w / 2.0], [0.0, w, h / 2.0], [0.0, 0.0, 1.0]])
-    ang = (cam[:3] - 0.5) * np.array([0.12, 0.5, 0.12]) + np.array([0.0, 0.15, 0.0])  # radians about x, y, z
-    cx, cy, cz = np.cos(ang)
-    sx, sy, sz = np.sin(ang)
-    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
-    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
-    rot = rz @ ry @ rx
-    t = np.array([-1.0 - cam[3], 0.3 * (cam[4] - 0.5), 0.3 * (cam[5] - 0.5)])
+    kk, rot = _scene_camera(cam, h, w)
+    t = _scene_shift(cam)
     tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
     kinv = np.linalg.inv(kk)
     f_true = kinv.T @ tx @ rot @ kinv
@@ -507,19 +822,12 @@ def planar_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, si
     pool = 16 * k + 64
     u = synth.uniform24(int(seed) + (0x9A7A if rotation_only else 0x91A9), 16 + 8 * pool).astype(np.float64)
     cam, u = u[:16], u[16:].reshape(8, pool)
-    kk = np.array([[w, 0.0, w / 2.0], [0.0, w, h / 2.0], [0.0, 0.0, 1.0]])
-    ang = (cam[:3] - 0.5) * np.array([0.12, 0.5, 0.12]) + np.array([0.0, 0.15, 0.0])  # radians about x, y, z
-    cx, cy, cz = np.cos(ang)
-    sx, sy, sz = np.sin(ang)
-    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
-    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
-    rot = rz @ ry @ rx
+    kk, rot = _scene_camera(cam, h, w)
     kinv = np.linalg.inv(kk)
     if rotation_only:
         h_true = kk @ rot @ kinv
     else:  # the plane n · X = d in the first camera's frame, X' = R X + t: H = K (R + t nᵀ / d) K⁻¹
-        t = np.array([-1.0 - cam[3], 0.3 * (cam[4] - 0.5), 0.3 * (cam[5] - 0.5)])
+        t = _scene_shift(cam)
         n = np.array([-0.6 * (cam[6] - 0.5), -0.6 * (cam[7] - 0.5), 1.0])
         d = 5.0 + 4.0 * cam[8]
         h_true = kk @ (rot + np.outer(t, n) / d) @ kinv
@@ -547,6 +855,27 @@ def planar_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, si
             torch.from_numpy(gt[order]), torch.from_numpy(h_true))
 
 
+def _scene_pose(seed: int, k: int, size, stream_seed: int, rows: int):
+    h, w = int(size[0]), int(size[1])
+    cam = synth.uniform24(stream_seed, 16 + rows * (16 * k + 64)).astype(np.float64)[:16]
+    kk, rot = _scene_camera(cam, h, w)
+    t = _scene_shift(cam)
+    return torch.from_numpy(kk), torch.from_numpy(rot), torch.from_numpy(t / np.linalg.norm(t))
+
+
+def calibrated_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
+    """two_view_scene(seed, k, outlier_fraction, noise_px, size) with its cameras: (kpts0, kpts1, gt_mask, F_true,
+    K [3, 3] float64 (both images'), R [3, 3], t [3] at unit length: X1 = R X0 + t). The first four are two_view_scene's
+    own, bit for bit: the same random stream."""
+    return two_view_scene(seed, k, outlier_fraction, noise_px, size) + _scene_pose(seed, k, size, int(seed), 9)
+
+
+def calibrated_planar_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
+    """planar_scene(seed, k, outlier_fraction, noise_px, size) (the moved camera, not the rotation-only one) with its
+    cameras: (kpts0, kpts1, gt_mask, H_true, K, R, t) as calibrated_scene's."""
+    return planar_scene(seed, k, outlier_fraction, noise_px, size) + _scene_pose(seed, k, size, int(seed) + 0x91A9, 8)
+
+
 # ---- the kernels --------------------------------------------------------------------------------------------------
 class _Ransac:
     """What the two estimators share: the parameters, the checks of verify's inputs and the call. _ENTRY: the C
@@ -559,10 +888,9 @@ class _Ransac:
         self.threshold, self.hypotheses, self.refits = float(threshold), int(hypotheses), int(refits)
         self.seed = int(seed) & _M32
 
-    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor):
-        """result.matches [P, Kmax, 2] / result.counts [P] (int32) index kpts0 [P, K0, 2] and kpts1 [P, K1, 2]
-        (fp32, (x, y) in pixels; ImageInput.keypoints' output is the intended one) -> the estimator's result. Two
-        launches on the current stream, nothing read back; counts and indices are clamped, never trusted."""
+    @staticmethod
+    def _inputs(result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor):
+        """verify's checks of its inputs -> (matches, counts, kpts0, kpts1) contiguous, P, Kmax."""
         matches, counts = result.matches, result.counts
         require_gpu("matches", matches, _STAGE, (torch.int32,), 3)
         require_gpu("counts", counts, _STAGE, (torch.int32,), 1)
@@ -578,6 +906,13 @@ class _Ransac:
                 raise ValueError(f"{name}: expected [{pr}, K, 2] with K >= 1, got {tuple(t.shape)}")
             if t.device != matches.device:
                 raise ValueError(f"{name}: on {t.device}, the matches on {matches.device}")
+        return tuple(t.contiguous() for t in (matches, counts, kpts0, kpts1)), pr, kmax
+
+    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor):
+        """result.matches [P, Kmax, 2] / result.counts [P] (int32) index kpts0 [P, K0, 2] and kpts1 [P, K1, 2]
+        (fp32, (x, y) in pixels; ImageInput.keypoints' output is the intended one) -> the estimator's result. Two
+        launches on the current stream, nothing read back; counts and indices are clamped, never trusted."""
+        (matches, counts, kpts0, kpts1), pr, kmax = self._inputs(result, kpts0, kpts1)
         dev = matches.device
         out = self._RESULT(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
                            torch.empty((pr, kmax), dtype=torch.uint8, device=dev),
@@ -586,15 +921,16 @@ class _Ransac:
                            torch.empty((pr,), dtype=torch.int32, device=dev))
         if pr == 0:
             return out
-        matches, counts, kpts0, kpts1 = (t.contiguous() for t in (matches, counts, kpts0, kpts1))
         stream = stream_of(matches)
         nbytes = int(_lib.load().lg_ransac_workspace(pr, kmax, self.hypotheses))
         ws, = carve(dev, stream, [nbytes])
-        seed = self.seed - (1 << 32) if self.seed >= 1 << 31 else self.seed  # the same 32 bits as int32
         call(self._ENTRY, matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), pr, kmax,
-             int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses, self.refits, seed, ws.data_ptr(),
+             int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses, self.refits, self._seed32(), ws.data_ptr(),
              nbytes, *(t.data_ptr() for t in out), stream)
         return out
+
+    def _seed32(self) -> int:
+        return self.seed - (1 << 32) if self.seed >= 1 << 31 else self.seed  # the same 32 bits as int32
 
 
 class FundamentalRansac(_Ransac):
@@ -607,6 +943,45 @@ class FundamentalRansac(_Ransac):
         return super().verify(result, kpts0, kpts1)
 
     verify.__doc__ = _Ransac.verify.__doc__
+
+class EssentialRansac(_Ransac):
+    """Five-point RANSAC for the essential matrix, and the relative pose from it, of every pair of a MatchResult
+    whose cameras are known (what cv::findEssentialMat and cv::recoverPose do on the host, without a non-linear
+    polish). The parameters are FundamentalRansac's; the threshold is in pixels. verify -> PoseResult. A pair is
+    valid from 5 inliers on, and a 5-inlier winner is only its own sample: threshold num_inliers before trusting
+    the pose. On a planar scene two poses fit; which of them comes out is not specified."""
+
+    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor, intrinsics: torch.Tensor) -> PoseResult:
+        """_Ransac.verify's inputs and intrinsics [P, 2, 4] fp32 ((fx, fy, cx, cy) of image 0 then image 1, in the
+        keypoints' pixel frame) -> PoseResult. Two launches on the current stream, nothing read back; a pair with a
+        non-finite intrinsic or a focal length <= 0 is invalid."""
+        (matches, counts, kpts0, kpts1), pr, kmax = self._inputs(result, kpts0, kpts1)
+        require_gpu("intrinsics", intrinsics, _STAGE, (torch.float32,), 3)
+        if tuple(intrinsics.shape) != (pr, 2, 4):
+            raise ValueError(f"intrinsics: expected [{pr}, 2, 4], got {tuple(intrinsics.shape)}")
+        if intrinsics.device != matches.device:
+            raise ValueError(f"intrinsics: on {intrinsics.device}, the matches on {matches.device}")
+        dev = matches.device
+
+        def i32():
+            return torch.empty((pr,), dtype=torch.int32, device=dev)
+
+        out = PoseResult(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
+                         torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
+                         torch.empty((pr, 3), dtype=torch.float32, device=dev),
+                         torch.empty((pr, kmax), dtype=torch.uint8, device=dev), i32(), i32(), i32(), i32())
+        if pr == 0:
+            return out
+        intrinsics = intrinsics.contiguous()
+        stream = stream_of(matches)
+        nbytes = int(_lib.load().lg_ransac_essential_workspace(pr, kmax, self.hypotheses))
+        ws, = carve(dev, stream, [nbytes])
+        call("lg_ransac_essential", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(),
+             intrinsics.data_ptr(), pr, kmax, int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses,
+             self.refits, self._seed32(), ws.data_ptr(), nbytes, *(t.data_ptr() for t in out), stream)
+        return out
+
+
 
 class HomographyRansac(_Ransac):
     """RANSAC for the homography x1 ~ H x0 of every pair of a MatchResult (planar scenes, a rotating camera; what
@@ -621,10 +996,17 @@ class HomographyRansac(_Ransac):
     verify.__doc__ = _Ransac.verify.__doc__
 
 def verify_source_images(image_input: ImageInput, encoder, frontend, matcher,
-                         ransac: "FundamentalRansac | HomographyRansac", images0, images1):
+                         ransac: "FundamentalRansac | HomographyRansac | EssentialRansac", images0, images1, *, intrinsics=None):
     """match_source_images followed by ransac.verify on its outputs: (MatchResult, kpts0_src, kpts1_src,
-    GeometryResult or HomographyResult), the matrices in the source images' own pixels; ransac is a
-    FundamentalRansac or a HomographyRansac. What replaces the demo's PostProcess + cv::findFundamentalMat
-    (demo/demo_mono.cpp:326-366); nothing is read back, so it enqueues, or is captured, as one piece."""
+    GeometryResult, HomographyResult or PoseResult), the matrices in the source images' own pixels; ransac is a
+    FundamentalRansac, a HomographyRansac or an EssentialRansac, which takes intrinsics [P, 2, 4] (of the source
+    images; required with it, refused with the others). What replaces the demo's PostProcess +
+    cv::findFundamentalMat (demo/demo_mono.cpp:326-366); nothing is read back, so it enqueues, or is captured, as
+    one piece."""
+    calibrated = isinstance(ransac, EssentialRansac)
+    if calibrated != (intrinsics is not None):
+        raise ValueError("verify_source_images: intrinsics go with an EssentialRansac, and only with it")
     result, kp0, kp1 = match_source_images(image_input, encoder, frontend, matcher, images0, images1)
+    if calibrated:
+        return result, kp0, kp1, ransac.verify(result, kp0, kp1, intrinsics)
     return result, kp0, kp1, ransac.verify(result, kp0, kp1)

@@ -18,7 +18,13 @@ re-measured at the same K, P and H on the same points in the same repeats, the t
 (fundamental_us in the record; the two estimators run the same launches, so the comparison is of the models'
 arithmetic). The pipeline part is the fundamental matrix's alone.
 
-    python tools/geometry_ab.py [--model fundamental|homography] [--repeats 5] [--part all|verify|pipeline]
+--model essential: EssentialRansac.verify on calibrated_scene's pairs (the scenes of the fundamental matrix with
+their cameras) and FundamentalRansac.verify on the same points in the same repeats, alternating, and the
+lg_ransac_solve5 hook alone on the call's own samples under the same method (solve5_us: the sample, the solve and the
+candidates of every hypothesis without the scoring pass, the finalize launch and the pose). No framework arm: batched
+framework ops have no five-point solve to put next to it.
+
+    python tools/geometry_ab.py [--model fundamental|homography|essential] [--repeats 5] [--part all|verify|pipeline]
                                 [--out profiles/geometry/ab.jsonl]
 """
 import argparse
@@ -32,9 +38,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "lightglue-with-flashattentionv2-tensorrt_amd")]
 import torch  # noqa: E402
 
-from lightglue_amd import (FundamentalRansac, HomographyRansac, ImageInput, KeypointFrontend, SuperPointEncoder,  # noqa: E402
-                           match_source_images, matcher, planar_scene, ransac_samples, seeded_superpoint_state_dict,
-                           two_view_scene, verify_source_images)
+from lightglue_amd import (EssentialRansac, FundamentalRansac, HomographyRansac, ImageInput, KeypointFrontend, SuperPointEncoder,  # noqa: E402
+                           calibrated_scene, match_source_images, matcher, planar_scene, ransac_samples, ransac_samples5,
+                           seeded_superpoint_state_dict, two_view_scene, verify_source_images)
+from lightglue_amd._host import call  # noqa: E402
 from lightglue_amd.matches import MatchResult  # noqa: E402
 
 H, R, THR, SEED = 512, 2, 3.0, 888
@@ -214,7 +221,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "geometry", "ab.jsonl"))
     ap.add_argument("--part", choices=("all", "verify", "pipeline"), default="all")
-    ap.add_argument("--model", choices=("fundamental", "homography"), default="fundamental")
+    ap.add_argument("--model", choices=("fundamental", "homography", "essential"), default="fundamental")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("geometry_ab.py: needs a GPU (timings from anywhere else mean nothing)")
@@ -232,6 +239,9 @@ def main():
     fr = FundamentalRansac(THR, H, R, SEED)
     if args.model == "homography":
         homography_part(args, dev, stream, base, emit, fr)
+        return
+    if args.model == "essential":
+        essential_part(args, dev, stream, base, emit, fr)
         return
     for k in (256, 1024, 2048) if args.part != "pipeline" else ():
         k0, k1, gt, _ = two_view_scene(k, k, 0.25, 0.25)
@@ -316,6 +326,46 @@ def homography_part(args, dev, stream, base, emit, fr):
                            framework_over_verify_median=round(statistics.median(t_theirs) / statistics.median(t_ours), 1))
             emit(rec)
             del g, gf
+
+
+def essential_part(args, dev, stream, base, emit, fr):
+    er = EssentialRansac(THR, H, R, SEED)
+    for k in (256, 1024, 2048):
+        k0, k1, gt, _, kk, _, _ = calibrated_scene(k, k, 0.25, 0.25)
+        samples = ransac_samples5(SEED, H, k).to(dev)
+        for pr in (1, 16):
+            x0, x1 = k0.to(dev)[None].repeat(pr, 1, 1), k1.to(dev)[None].repeat(pr, 1, 1)
+            m = torch.arange(k, dtype=torch.int32, device=dev)[None, :, None].repeat(pr, 1, 2).contiguous()
+            counts = torch.full((pr,), k, dtype=torch.int32, device=dev)
+            intr = torch.tensor([[kk[0, 0], kk[1, 1], kk[0, 2], kk[1, 2]]] * 2, dtype=torch.float32, device=dev)[None].repeat(pr, 1, 1)
+            res = MatchResult(None, None, None, None, m, None, counts)
+            cand = torch.empty((pr, H, 10, 9), dtype=torch.float32, device=dev)
+            num = torch.empty((pr, H), dtype=torch.int32, device=dev)
+
+            def solve():
+                call("lg_ransac_solve5", m.data_ptr(), counts.data_ptr(), x0.data_ptr(), x1.data_ptr(), intr.data_ptr(), pr, k, k, k,
+                     samples.data_ptr(), H, cand.data_ptr(), num.data_ptr(), torch.cuda.current_stream().cuda_stream)
+
+            with torch.no_grad():
+                ours = lambda: er.verify(res, x0, x1, intr)  # noqa: E731
+                fund = lambda: fr.verify(res, x0, x1)        # noqa: E731
+                mine = ours()
+                torch.cuda.synchronize()
+                rec = dict(base, part="verify", model="essential", K=k, P=pr,
+                           ours_mask_is_gt=bool((mine.inliers.bool().cpu() == gt[None]).all()),
+                           num_front_is_num_inliers=bool((mine.num_front == mine.num_inliers).all()))
+                g, gf, gs = graph_of(ours, stream, CALLS), graph_of(fund, stream, CALLS), graph_of(solve, stream, CALLS)
+                t_ours, t_fund, t_solve = [], [], []
+                for _ in range(args.repeats):
+                    t_ours.append(time_graph(g, stream, CALLS))
+                    t_fund.append(time_graph(gf, stream, CALLS))
+                    t_solve.append(time_graph(gs, stream, CALLS))
+                rec.update(verify_us=spread(t_ours), fundamental_us=spread(t_fund), solve5_us=spread(t_solve),
+                           verify_eager_us=round(time_eager(ours, 50), 2), candidates_per_hypothesis=round(float(num.float().mean()), 2),
+                           essential_over_fundamental_median=round(statistics.median(t_ours) / statistics.median(t_fund), 3),
+                           solve5_share_of_verify=round(statistics.median(t_solve) / statistics.median(t_ours), 3))
+            emit(rec)
+            del g, gf, gs
 
 
 if __name__ == "__main__":
