@@ -589,7 +589,8 @@ int32_t lg_ransac_score_homography(const int32_t* matches, const int32_t* counts
  *      method: the least-squares depths of d0 R a - d1 b = -t for the rays a = (q0, 1), b = (q1, 1)) to a positive
  *      depth in both cameras, the lowest index among equals; num_front is that count.
  *   7. valid = 1 from 5 inliers on. A 5-inlier winner is only its own sample: callers should threshold num_inliers.
- * Not built: a non-linear polish of the pose, and the choice between the two solutions a plane admits. */
+ * The non-linear polish of the pose is lg_pose_polish, below. Not built: the choice between the two solutions a
+ * plane admits. */
 /* Bytes of lg_ransac_essential's workspace (0 for an empty call): a hypothesis' record holds F and E. */
 size_t lg_ransac_essential_workspace(int32_t pairs, int32_t kmax, int32_t hypotheses);
 /* lg_ransac_essential: two launches, the shapes of lg_ransac_fundamental's (the four lanes of a hypothesis hold five
@@ -616,6 +617,64 @@ int32_t lg_ransac_solve5(const int32_t* matches, const int32_t* counts, const fl
 int32_t lg_pose_from_essential(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
                                const float* intrinsics, int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* e,
                                const uint8_t* inliers, float* r, float* t, int32_t* num_front, hipStream_t stream);
+
+/* The pose polish (csrc/lightglue_polish.hip): the (R, t) that lg_ransac_essential returns is the last kept 8-point
+ * refit projected to the essential manifold, or the raw five-point winner; neither minimises a geometric error over
+ * the inliers. lg_pose_polish does, and lg_triangulate writes the points of the result. New symbols only:
+ * LG_GLUE_ABI_VERSION stays 4. The general statements of lg_ransac_fundamental hold (arguments checked before any
+ * device call, a no-op for pairs == 0, counts and indices clamped, no atomics, no allocation, no workspace, every output
+ * entry written). lightglue_amd/geometry.py restates the contract in float64 by another route (polish_reference:
+ * scipy's least squares to convergence in another parameterisation; the converged minimiser is what is compared).
+ *
+ * Inputs: lg_ransac_essential's pair arguments and intrinsics; r [pairs, 3, 3], t [pairs, 3] fp32; inliers
+ * [pairs, kmax] uint8 (non-zero: an inlier) and valid [pairs] int32, as lg_ransac_essential wrote them; threshold;
+ * iterations in [1, 16]. The homography has no such call on purpose (its Hartley-normalised DLT refit is at the minimum
+ * of the transfer cost to 3e-6 .. 8e-5 relative on the test scenes), and neither has the fundamental matrix
+ * (OpenCV polishes neither). Per pair:
+ *   1. The fixed set: the rows with inliers != 0 whose residual (step 2) under the entering pose is finite; n_in is the
+ *      number of rows with inliers != 0. The pair is passed through (step 5) where valid == 0, an intrinsic is not
+ *      finite or a focal length <= 0, the fixed set has fewer than 5 rows, R or t is not finite, or t has zero length.
+ *      The entering pose is t at unit length and R one Newton step of the polar iteration nearer the rotations
+ *      (R (3 I - Rᵀ R) / 2: a rotation rounded to fp32 is 1e-7 off, the step leaves 1e-14).
+ *   2. The residual of a row, fp64, is the signed Sampson distance in pixels: with E = [t]x R, q the camera
+ *      coordinates, (a, b, .) = E q0 and (a', b', .) = Eᵀ q1: d = q1ᵀ E q0 and
+ *      s = d / sqrt((a / fx1)² + (b / fy1)² + (a' / fx0)² + (b' / fy0)²). The cost is Σ s² over the fixed set, which
+ *      does not change during the iterations.
+ *   3. `iterations` rounds of Levenberg-Marquardt on the 5 parameters δ = (ω, τ): R <- exp([ω]x) R by the exact
+ *      Rodrigues formula, t <- normalise(t + τ1 b1 + τ2 b2) with (b1, b2) an orthonormal basis of t's tangent plane
+ *      (b1 = normalise(t x axis), b2 = t x b1, axis the unit axis of t's smallest component in magnitude, the lowest
+ *      index among equals). The Jacobian rows are analytic (∂E/∂ω_i = [t]x [e_i]x R, ∂E/∂τ_j = [b_j]x R). A round
+ *      solves (JᵀJ + λ diag(JᵀJ)) δ = -Jᵀs by a 5 x 5 Cholesky factorisation in fp64, λ = 1e-3 at first; a pivot that is
+ *      not positive or not finite rejects the round. The trial is accepted iff its cost is finite and below the
+ *      current cost; then λ <- max(λ / 10, 1e-12), else λ <- min(10 λ, 1e12). Every loop has a compile-time bound but
+ *      the rounds', which is the same for every pair; the whole workgroup takes each decision alike, from sums it
+ *      reads from one ordered reduction.
+ *   4. E <- canonical([t]x R); the mask over all the pair's correspondences as step 4 of the five-point contract
+ *      scores (fp32 F = K1⁻ᵀ E K0⁻¹, the fundamental matrix' error, threshold²), n_new its count. If n_new >= n_in:
+ *      the polished E, R, t, the new mask, num_inliers = n_new, num_front = the new inliers in front of both cameras
+ *      under (R, t) (step 6 there), kept = 1.
+ *   5. Else, and for the pairs step 1 names, the pass-through, kept = 0: R and t as given (the same bits), the mask
+ *      as given (a non-zero entry written as 1; 0 past the count), E = canonical([t]x R) of the given pose (zeros
+ *      where valid == 0 or the pose is not finite), num_inliers = n_in and num_front over the given mask under the
+ *      given pose (both zeros where valid == 0; num_front 0 where the intrinsics are bad), both costs equal.
+ * Outputs: e, r_out, t_out, inliers_out, num_inliers, num_front as lg_ransac_essential's; cost [pairs, 2] fp32: the
+ * entering and the final Σ s² over the fixed set in px² (zeros where the cost was never taken: valid == 0, bad
+ * intrinsics, a pose that is not finite); kept [pairs] int32. One launch, one workgroup per pair. The outputs may not
+ * alias the inputs. */
+int32_t lg_pose_polish(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                       const float* intrinsics, int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* r, const float* t,
+                       const uint8_t* inliers, const int32_t* valid, float threshold, int32_t iterations, float* e_out, float* r_out,
+                       float* t_out, uint8_t* inliers_out, int32_t* num_inliers, int32_t* num_front, float* cost, int32_t* kept,
+                       hipStream_t stream);
+/* lg_triangulate: the 3D point of every inlier under (r, t): points [pairs, kmax, 3] fp32 and ok [pairs, kmax] uint8.
+ * For a row below the count with inliers != 0 (and good intrinsics), fp64: the depths (d0, d1) of the midpoint method
+ * (step 6 of the five-point contract: the least-squares solution of d0 R a - d1 b = -t for the rays a = (q0, 1),
+ * b = (q1, 1)) and X = (d0 a + Rᵀ (d1 b - t)) / 2 in camera 0's frame, at the scale of the given t (|t| = 1 from the
+ * calls above). ok = 1 iff both depths are positive and X is finite (in the output's fp32 too); every other entry is
+ * zeros. One launch, a flat grid over (rows, pairs). */
+int32_t lg_triangulate(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                       const float* intrinsics, int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* r, const float* t,
+                       const uint8_t* inliers, float* points, uint8_t* ok, hipStream_t stream);
 
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]

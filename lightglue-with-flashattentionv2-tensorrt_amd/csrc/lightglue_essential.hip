@@ -1,7 +1,8 @@
 // lightglue_essential.hip — calibrated relative pose (include/lightglue_glue.h, "geometric verification"): an
 // essential matrix per image pair by five-point RANSAC over the matcher's matches, and (R, t) from it, by the scheme
 // of lightglue_geometry.hip, whose launch shapes and helpers (lightglue_geometry_device.h) this file shares. The
-// contract is restated in float64 in lightglue_amd/geometry.py; the arithmetic is in lightglue_essential_math.h.
+// contract is restated in float64 in lightglue_amd/geometry.py; the arithmetic is in lightglue_essential_math.h, and what
+// the pose polish (lightglue_polish.hip) shares with this file in lightglue_essential_device.h.
 //
 // Two launches. essential_hypothesis_kernel: grid (hypothesis blocks, pairs), 64 hypotheses a workgroup, four
 // adjacent lanes a hypothesis. The workgroup gathers the pair's correspondences into LDS once. The four lanes hash
@@ -15,22 +16,11 @@
 // refits in fp64 (camera coordinates, Hartley, normal matrix, Jacobi on the 9 x 9, de-normalise, the nearest
 // essential matrix; a round that counts fewer inliers is dropped and ends the rounds), takes the pose with the most
 // inliers in front of both cameras and writes every output. No atomics, no allocation, no host synchronisation.
-#include "lightglue_geometry_device.h"
-#include "lightglue_essential_math.h"
+#include "lightglue_essential_device.h"
 
 namespace {
 
 constexpr int kPoseRecord = 20;  // floats per hypothesis in the workspace: F[9] (pixels), E[9] (camera), count, pad
-
-__device__ __forceinline__ Intrinsics load_intrinsics(const float* intr, int p) {
-    const float* k = intr + (size_t)p * 8;
-    return Intrinsics{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7]};
-}
-
-__device__ __forceinline__ void camera(const float4 q, const Intrinsics& k, double c[4]) {
-    c[0] = ((double)q.x - k.cx0) / k.fx0, c[1] = ((double)q.y - k.cy0) / k.fy0;
-    c[2] = ((double)q.z - k.cx1) / k.fx1, c[3] = ((double)q.w - k.cy1) / k.fy1;
-}
 
 __device__ __forceinline__ double from_lane(double v, int lane) { return __shfl(v, lane); }
 
@@ -205,19 +195,6 @@ __device__ __forceinline__ int pose_of(const double e[9], const float4* pts, con
         for (int k = 0; k < 3; ++k) t[k] = take ? tt[k] : t[k];
     }
     return max(best, 0);
-}
-
-// Marks the inliers of f into m and returns their number (every thread).
-__device__ __forceinline__ int mark_inliers(const float f[9], const float4* pts, int count, float thr2, uint8_t* m, double* buf,
-                                            int tid) {
-    int mine = 0;
-    for (int k = tid; k < count; k += kFinThreads) {
-        const float4 q = pts[k];
-        const bool in = is_inlier(f, q.x, q.y, q.z, q.w, thr2);
-        m[k] = in ? 1 : 0;
-        mine += in ? 1 : 0;
-    }
-    return (int)block_sum<kFinThreads>((double)mine, buf, tid);  // (exact: integers below 2^53)
 }
 
 __global__ __launch_bounds__(kFinThreads) void essential_finalize_kernel(PairArgs a, const float* __restrict__ intr, int hypotheses,

@@ -206,6 +206,10 @@ SIGNATURES.update({
     "lg_ransac_samples5": ([_I, _I, _I, _P, _P], _I),
     "lg_ransac_solve5": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P], _I),
     "lg_pose_from_essential": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    # the pose polish and the triangulation (csrc/lightglue_polish.hip)
+    "lg_pose_polish": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                        _P], _I),
+    "lg_triangulate": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -24,6 +24,13 @@ matrix and the relative pose (R, t) from it, given each image's (fx, fy, cx, cy)
 eigenvalues of the cubic matrix pencil in the hidden variable: not the kernel's elimination and degree-10
 polynomial), ``essential_refit``, ``pose_from_essential_reference`` and ``essential_reference``;
 ``calibrated_scene`` and ``calibrated_planar_scene`` are the scenes above with their cameras.
+
+``PosePolish.refine`` (csrc/lightglue_polish.hip; ``EssentialRansac(polish=N)`` appends it) minimises the squared
+Sampson distance in pixels over the pose's inliers by N rounds of Levenberg-Marquardt on the 5 parameters of (R, t),
+recomputes the mask and keeps the result where it loses no inlier; ``triangulate`` writes every inlier's 3D point.
+Their float64 contract: ``sampson_error``, ``polish_pose_reference`` (``scipy.optimize.least_squares(method="lm")``
+on a global rotation vector and two angles of t with a numeric Jacobian, deliberately not the kernel's route: the
+converged minimiser is what is compared), ``polish_reference`` (a batch of it) and ``triangulate_reference``.
 """
 from __future__ import annotations
 
@@ -41,6 +48,8 @@ _STAGE = "the geometric verification"
 MAX_POINTS = 2048       # kmax: the plugin's N limit
 MAX_HYPOTHESES = 4096
 MAX_REFITS = 8
+MAX_POLISH = 16         # rounds of the pose polish
+MIN_POLISH_ROWS = 5     # the polish's fixed set needs as many rows as there are parameters
 MIN_INLIERS = 8         # a fundamental matrix, and its refit, needs 8 correspondences
 MIN_INLIERS_H = 4       # a homography, and its refit, needs 4
 MIN_INLIERS_E = 5       # an essential matrix needs 5 (its refit 8, as the fundamental matrix's)
@@ -86,6 +95,23 @@ class PoseResult(NamedTuple):
     num_front: torch.Tensor
     valid: torch.Tensor
     best: torch.Tensor
+
+
+class PolishResult(NamedTuple):
+    """The pose polish's outputs. E, R, t, inliers, num_inliers, num_front as PoseResult's; cost [P, 2] fp32: the sum of
+    squared Sampson residuals (px²) over the fixed set (the given inliers with a finite residual) under the given
+    and under the returned pose; kept [P] int32: 1 where the polished pose is returned (its mask, recomputed over all
+    the pair's correspondences, has at least as many inliers as the given one), 0 where the given pose and mask are
+    passed through (both costs are then the entering one; every output but R, t and the mask is zeros where the
+    given pose was invalid)."""
+    E: torch.Tensor
+    R: torch.Tensor
+    t: torch.Tensor
+    inliers: torch.Tensor
+    num_inliers: torch.Tensor
+    num_front: torch.Tensor
+    cost: torch.Tensor
+    kept: torch.Tensor
 
 
 # ---- the minimal samples --------------------------------------------------------------------------------------
@@ -575,6 +601,152 @@ def pose_from_essential_reference(E, q0, q1):
     return torch.from_numpy(cands[i][0].copy()), torch.from_numpy(cands[i][1].copy()), counts[i], counts
 
 
+# ---- the pose polish and the triangulation in float64 --------------------------------------------------------------
+def _skew(t: np.ndarray) -> np.ndarray:
+    return np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+
+
+def _sampson(e: np.ndarray, x0: np.ndarray, x1: np.ndarray, k: np.ndarray) -> np.ndarray:
+    with np.errstate(all="ignore"):
+        q0 = np.concatenate([(x0 - k[0, 2:4]) / k[0, 0:2], np.ones((len(x0), 1))], 1)
+        q1 = np.concatenate([(x1 - k[1, 2:4]) / k[1, 0:2], np.ones((len(x1), 1))], 1)
+        l1, l0 = q0 @ e.T, q1 @ e
+        d = (q1 * l1).sum(1)
+        n2 = (l1[:, 0] / k[1, 0]) ** 2 + (l1[:, 1] / k[1, 1]) ** 2 + (l0[:, 0] / k[0, 0]) ** 2 + (l0[:, 1] / k[0, 1]) ** 2
+        return d / np.sqrt(n2)
+
+
+def sampson_error(E, x0, x1, intrinsics) -> torch.Tensor:
+    """The signed Sampson distance in pixels of each correspondence (x0, x1 [n, 2] in pixels) under E [3, 3] (camera
+    coordinates, any scale; intrinsics [2, 4]), float64 [n]: with q the camera coordinates, (a, b, .) = E q0,
+    (a', b', .) = Eᵀ q1 and d = q1ᵀ E q0, d / sqrt((a / fx1)² + (b / fy1)² + (a' / fx0)² + (b' / fy0)²): the first-order
+    distance to the epipolar constraint in the pixels of both images. The polish's cost is the sum of its squares."""
+    return torch.from_numpy(_sampson(_np(E).reshape(3, 3), _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2),
+                                     _np(intrinsics).reshape(2, 4)))
+
+
+def _axis_order(t: np.ndarray):
+    i = int(np.argmin(np.abs(t)))  # (the lowest index among equals)
+    return i, (i + 1) % 3, (i + 2) % 3
+
+
+def polish_pose_reference(R, t, x0, x1, intrinsics, mask, threshold: float = 3.0) -> PolishResult:
+    """PosePolish.refine's contract for one valid pair in float64, run to convergence: R [3, 3], t [3], the pair's
+    correspondences x0, x1 [n, 2] in pixels, intrinsics [2, 4], mask [n] (its non-zeros: the given inliers) ->
+    PolishResult without the batch dimension (E, R, t, cost float64). The fixed set is the given inliers with a finite
+    sampson_error under the given pose; with fewer than 5 of them, bad intrinsics, a non-finite R or t or a zero t
+    the pair is passed through. Else the sum of squared sampson_error over the fixed set is minimised by
+    scipy.optimize.least_squares(method="lm") at its tolerance floor over a global rotation vector and the two
+    angles of t about the axis of its smallest component, with a numeric Jacobian (not the kernel's route: a local
+    rotation, a tangent step of t, an analytic Jacobian and a fixed number of rounds). The mask is then recomputed
+    over all n correspondences as essential_reference scores a candidate; with at least as many inliers as given the
+    polished pose, its mask and its counts are returned (kept = 1), else the given ones (kept = 0, both costs the
+    entering one, E = canonical([t]x R) of the given pose)."""
+    from scipy.optimize import least_squares
+    from scipy.spatial.transform import Rotation
+
+    r, t = _np(R).reshape(3, 3), _np(t).reshape(3)
+    x0, x1, kk = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2), _np(intrinsics).reshape(2, 4)
+    given = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask).reshape(-1) != 0
+    n_in, thr2 = int(given.sum()), float(threshold) ** 2
+    with np.errstate(all="ignore"):
+        e_given = _unit(_skew(t) @ r) if np.isfinite(r).all() and np.isfinite(t).all() else None
+        length = float(np.linalg.norm(t))
+    good = _intrinsics_ok(kk)
+
+    def front_of(rr, tt, rows):
+        if not good:
+            return 0
+        d0, d1 = _depths(rr, tt, camera_coordinates(x0[rows], kk[0]), camera_coordinates(x1[rows], kk[1]))
+        return int(((d0 > 0) & (d1 > 0)).sum())
+
+    def result(e, rr, tt, rows, costs, kept):
+        return PolishResult(torch.from_numpy(np.zeros((3, 3)) if e is None else e.copy()), torch.from_numpy(rr.copy()),
+                            torch.from_numpy(tt.copy()), torch.from_numpy(rows.astype(np.uint8)),
+                            torch.tensor(int(rows.sum()), dtype=torch.int32), torch.tensor(front_of(rr, tt, rows), dtype=torch.int32),
+                            torch.tensor(costs, dtype=torch.float64), torch.tensor(kept, dtype=torch.int32))
+
+    if not (good and e_given is not None and np.isfinite(length) and length > 0.0):
+        return result(e_given, r, t, given, [0.0, 0.0], 0)
+    t0 = t / length
+    rows = np.nonzero(given)[0]
+    rows = rows[np.isfinite(_sampson(_skew(t0) @ r, x0[rows], x1[rows], kk))]
+    rot0 = Rotation.from_matrix(r)  # (the nearest rotation: a pose rounded to fp32 is 1e-7 off)
+    cost0 = float((_sampson(_skew(t0) @ rot0.as_matrix(), x0[rows], x1[rows], kk) ** 2).sum())
+    if len(rows) < MIN_POLISH_ROWS or not np.isfinite(cost0):
+        return result(e_given, r, t, given, [cost0, cost0], 0)
+    i, j, k = _axis_order(t0)
+
+    def pose(p):
+        tt = np.zeros(3)
+        tt[i], tt[j], tt[k] = np.cos(p[3]), np.sin(p[3]) * np.cos(p[4]), np.sin(p[3]) * np.sin(p[4])
+        return Rotation.from_rotvec(p[:3]).as_matrix(), tt
+
+    def residuals(p):
+        rr, tt = pose(p)
+        return _sampson(_skew(tt) @ rr, x0[rows], x1[rows], kk)
+
+    p0 = np.concatenate([rot0.as_rotvec(), [np.arccos(np.clip(t0[i], -1.0, 1.0)), np.arctan2(t0[k], t0[j])]])
+    sol = least_squares(residuals, p0, method="lm", xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=4000)
+    cost1 = float((sol.fun ** 2).sum())
+    r1, t1 = pose(sol.x) if np.isfinite(cost1) and cost1 < cost0 else pose(p0)
+    cost1 = cost1 if np.isfinite(cost1) and cost1 < cost0 else cost0
+    e1 = _unit(_skew(t1) @ r1)
+    f1 = None if e1 is None else _f_of_e(e1, kk)
+    again = np.zeros(len(x0), dtype=bool) if f1 is None else _epi(f1, x0, x1) <= thr2
+    if f1 is None or int(again.sum()) < n_in:
+        return result(e_given, r, t, given, [cost0, cost0], 0)
+    return result(e1, r1, t1, again, [cost0, cost1], 1)
+
+
+def polish_reference(pose, matches, counts, kpts0, kpts1, intrinsics, threshold: float = 3.0) -> PolishResult:
+    """PosePolish(threshold).refine for a batch in float64, run to convergence: polish_pose_reference on every pair
+    with pose.valid != 0 (over its gathered correspondences and pose.inliers); a pair with valid == 0 returns R, t
+    and the mask as given and zeros elsewhere. E, R, t, cost float64."""
+    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
+    out = PolishResult(torch.zeros((pr, 3, 3), dtype=torch.float64), _as64(pose.R).clone(), _as64(pose.t).clone(),
+                       torch.zeros((pr, kmax), dtype=torch.uint8), torch.zeros((pr,), dtype=torch.int32),
+                       torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr, 2), dtype=torch.float64),
+                       torch.zeros((pr,), dtype=torch.int32))
+    for p in range(pr):
+        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
+        n = len(x0)
+        given = pose.inliers[p, :n].cpu()
+        if not int(pose.valid[p]):
+            out.inliers[p, :n] = (given != 0).to(torch.uint8)
+            continue
+        one = polish_pose_reference(pose.R[p], pose.t[p], x0, x1, intrinsics[p], given, threshold)
+        out.E[p], out.R[p], out.t[p], out.cost[p] = one.E, one.R, one.t, one.cost
+        out.inliers[p, :n] = one.inliers
+        out.num_inliers[p], out.num_front[p], out.kept[p] = one.num_inliers, one.num_front, one.kept
+    return out
+
+
+def _as64(t) -> torch.Tensor:
+    return torch.from_numpy(_np(t))
+
+
+def triangulate_reference(R, t, x0, x1, intrinsics, mask):
+    """triangulate's contract for one pair in float64: (points [n, 3], ok [n] uint8). For a row with mask != 0 the
+    midpoint method of pose_from_essential_reference: the depths (d0, d1) of _depths, and X = (d0 a + Rᵀ (d1 b - t)) / 2
+    in camera 0's frame for the rays a = (q0, 1), b = (q1, 1), at the scale |t| = 1; ok where both depths are
+    positive and X is finite. Every other entry is zeros."""
+    r, t = _np(R).reshape(3, 3), _np(t).reshape(3)
+    x0, x1, kk = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2), _np(intrinsics).reshape(2, 4)
+    rows = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask).reshape(-1) != 0
+    pts, ok = np.zeros((len(x0), 3)), np.zeros(len(x0), dtype=bool)
+    if _intrinsics_ok(kk):
+        q0, q1 = camera_coordinates(x0, kk[0]), camera_coordinates(x1, kk[1])
+        d0, d1 = _depths(r, t, q0, q1)
+        with np.errstate(all="ignore"):
+            a = np.concatenate([q0, np.ones((len(q0), 1))], 1)
+            b = np.concatenate([q1, np.ones((len(q1), 1))], 1)
+            x = 0.5 * (d0[:, None] * a + (d1[:, None] * b - t) @ r)
+            ok = rows & (d0 > 0) & (d1 > 0) & np.isfinite(x).all(1)
+        pts[ok] = x[ok]
+    return torch.from_numpy(pts), torch.from_numpy(ok.astype(np.uint8))
+
+
 def rotation_angle_deg(ra, rb) -> float:
     """The angle of the rotation Raᵀ Rb in degrees: |Ra - Rb| = 2 sqrt 2 sin(angle / 2) in the Frobenius norm (exact
     for small angles, where the arc cosine of the trace is not)."""
@@ -946,15 +1118,24 @@ class FundamentalRansac(_Ransac):
 
 class EssentialRansac(_Ransac):
     """Five-point RANSAC for the essential matrix, and the relative pose from it, of every pair of a MatchResult
-    whose cameras are known (what cv::findEssentialMat and cv::recoverPose do on the host, without a non-linear
-    polish). The parameters are FundamentalRansac's; the threshold is in pixels. verify -> PoseResult. A pair is
-    valid from 5 inliers on, and a 5-inlier winner is only its own sample: threshold num_inliers before trusting
-    the pose. On a planar scene two poses fit; which of them comes out is not specified."""
+    whose cameras are known (what cv::findEssentialMat and cv::recoverPose do on the host). The parameters are
+    FundamentalRansac's; the threshold is in pixels; polish: 0 (the RANSAC pose as it is: the last kept 8-point
+    refit, or the five-point winner), or the rounds in [1, 16] of PosePolish's Levenberg-Marquardt over the inliers,
+    appended as a third launch. verify -> PoseResult. A pair is valid from 5 inliers on, and a 5-inlier winner is
+    only its own sample: threshold num_inliers before trusting the pose. On a planar scene two poses fit; which of
+    them comes out is not specified."""
+
+    def __init__(self, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2, seed: int = 888, polish: int = 0) -> None:
+        super().__init__(threshold, hypotheses, refits, seed)
+        if not 0 <= int(polish) <= MAX_POLISH:
+            raise ValueError(f"polish must be in [0, {MAX_POLISH}] rounds, got {polish}")
+        self.polish = int(polish)
 
     def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor, intrinsics: torch.Tensor) -> PoseResult:
         """_Ransac.verify's inputs and intrinsics [P, 2, 4] fp32 ((fx, fy, cx, cy) of image 0 then image 1, in the
-        keypoints' pixel frame) -> PoseResult. Two launches on the current stream, nothing read back; a pair with a
-        non-finite intrinsic or a focal length <= 0 is invalid."""
+        keypoints' pixel frame) -> PoseResult. Two launches on the current stream (three with polish > 0: the result
+        is then the polished one, valid and best the RANSAC's), nothing read back; a pair with a non-finite intrinsic
+        or a focal length <= 0 is invalid."""
         (matches, counts, kpts0, kpts1), pr, kmax = self._inputs(result, kpts0, kpts1)
         require_gpu("intrinsics", intrinsics, _STAGE, (torch.float32,), 3)
         if tuple(intrinsics.shape) != (pr, 2, 4):
@@ -979,13 +1160,93 @@ class EssentialRansac(_Ransac):
         call("lg_ransac_essential", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(),
              intrinsics.data_ptr(), pr, kmax, int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses,
              self.refits, self._seed32(), ws.data_ptr(), nbytes, *(t.data_ptr() for t in out), stream)
-        return out
+        if not self.polish:
+            return out
+        fine = _polish_call(matches, counts, kpts0, kpts1, intrinsics, out, self.threshold, self.polish, stream)
+        return PoseResult(fine.E, fine.R, fine.t, fine.inliers, fine.num_inliers, fine.num_front, out.valid, out.best)
+
+
+def _calibrated_inputs(result: MatchResult, kpts0, kpts1, intrinsics, pose):
+    """The checks PosePolish.refine and triangulate share -> (matches, counts, kpts0, kpts1, intrinsics, R, t, inliers)
+    contiguous, P, Kmax."""
+    (matches, counts, kpts0, kpts1), pr, kmax = _Ransac._inputs(result, kpts0, kpts1)
+    require_gpu("intrinsics", intrinsics, _STAGE, (torch.float32,), 3)
+    require_gpu("R", pose.R, _STAGE, (torch.float32,), 3)
+    require_gpu("t", pose.t, _STAGE, (torch.float32,), 2)
+    require_gpu("inliers", pose.inliers, _STAGE, (torch.uint8,), 2)
+    for name, t, shape in (("intrinsics", intrinsics, (pr, 2, 4)), ("R", pose.R, (pr, 3, 3)), ("t", pose.t, (pr, 3)),
+                           ("inliers", pose.inliers, (pr, kmax))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected {list(shape)}, got {tuple(t.shape)}")
+        if t.device != matches.device:
+            raise ValueError(f"{name}: on {t.device}, the matches on {matches.device}")
+    return (matches, counts, kpts0, kpts1) + tuple(t.contiguous() for t in (intrinsics, pose.R, pose.t, pose.inliers)), pr, kmax
+
+
+def _polish_call(matches, counts, kpts0, kpts1, intrinsics, pose, threshold: float, iterations: int, stream) -> PolishResult:
+    pr, kmax, dev = int(matches.shape[0]), int(matches.shape[1]), matches.device
+
+    def i32():
+        return torch.empty((pr,), dtype=torch.int32, device=dev)
+
+    out = PolishResult(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
+                       torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
+                       torch.empty((pr, 3), dtype=torch.float32, device=dev),
+                       torch.empty((pr, kmax), dtype=torch.uint8, device=dev), i32(), i32(),
+                       torch.empty((pr, 2), dtype=torch.float32, device=dev), i32())
+    if pr:
+        call("lg_pose_polish", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), intrinsics.data_ptr(),
+             pr, kmax, int(kpts0.shape[1]), int(kpts1.shape[1]), pose.R.data_ptr(), pose.t.data_ptr(), pose.inliers.data_ptr(),
+             pose.valid.data_ptr(), threshold, iterations, *(t.data_ptr() for t in out), stream)
+    return out
+
+
+class PosePolish:
+    """The non-linear polish of a calibrated pose (csrc/lightglue_polish.hip; what cv::findEssentialMat's callers add
+    by hand): `iterations` rounds in [1, 16] of Levenberg-Marquardt on the 5 parameters of (R, t) over the squared
+    Sampson distance in pixels of the pose's inliers, then the mask recomputed at `threshold` pixels over all the
+    pair's correspondences; the polished pose is kept where it has at least as many inliers as the given one.
+    refine -> PolishResult. EssentialRansac(polish=N) appends it to the RANSAC."""
+
+    def __init__(self, threshold: float = 3.0, iterations: int = 10) -> None:
+        if not 0.0 < float(threshold) <= 1e6:
+            raise ValueError(f"threshold must be in (0, 1e6] pixels, got {threshold}")
+        if not 1 <= int(iterations) <= MAX_POLISH:
+            raise ValueError(f"iterations must be in [1, {MAX_POLISH}], got {iterations}")
+        self.threshold, self.iterations = float(threshold), int(iterations)
+
+    def refine(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor, intrinsics: torch.Tensor, pose) -> PolishResult:
+        """EssentialRansac.verify's inputs and its PoseResult (or any tuple with R [P, 3, 3], t [P, 3] fp32, inliers
+        [P, Kmax] uint8 and valid [P] int32 on the device) -> PolishResult. One launch on the current stream, nothing
+        read back."""
+        (matches, counts, kpts0, kpts1, intrinsics, r, t, inliers), pr, _ = _calibrated_inputs(result, kpts0, kpts1, intrinsics, pose)
+        require_gpu("valid", pose.valid, _STAGE, (torch.int32,), 1)
+        if tuple(pose.valid.shape) != (pr,) or pose.valid.device != matches.device:
+            raise ValueError(f"valid: expected [{pr}] on {matches.device}, got {tuple(pose.valid.shape)} on {pose.valid.device}")
+        given = PoseResult(None, r, t, inliers, None, None, pose.valid.contiguous(), None)
+        return _polish_call(matches, counts, kpts0, kpts1, intrinsics, given, self.threshold, self.iterations, stream_of(matches))
+
+
+def triangulate(result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor, intrinsics: torch.Tensor, pose):
+    """The 3D point of every inlier of a pose (a PoseResult or a PolishResult: R, t, inliers): (points [P, Kmax, 3] fp32
+    in camera 0's frame at the scale |t| = 1, ok [P, Kmax] uint8), by the midpoint method the cheirality count uses
+    (triangulate_reference); ok = 1 where both depths are positive and the point is finite, every other entry zeros.
+    One launch on the current stream, nothing read back."""
+    (matches, counts, kpts0, kpts1, intrinsics, r, t, inliers), pr, kmax = _calibrated_inputs(result, kpts0, kpts1, intrinsics, pose)
+    points = torch.empty((pr, kmax, 3), dtype=torch.float32, device=matches.device)
+    ok = torch.empty((pr, kmax), dtype=torch.uint8, device=matches.device)
+    if pr:
+        call("lg_triangulate", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), intrinsics.data_ptr(), pr,
+             kmax, int(kpts0.shape[1]), int(kpts1.shape[1]), r.data_ptr(), t.data_ptr(), inliers.data_ptr(), points.data_ptr(),
+             ok.data_ptr(), stream_of(matches))
+    return points, ok
 
 
 
 class HomographyRansac(_Ransac):
     """RANSAC for the homography x1 ~ H x0 of every pair of a MatchResult (planar scenes, a rotating camera; what
-    cv::findHomography(pts0, pts1, cv::RANSAC, 3) does on the host, without its final Levenberg-Marquardt polish).
+    cv::findHomography(pts0, pts1, cv::RANSAC, 3) does on the host, without its final Levenberg-Marquardt polish: on
+    the planar scenes a float64 prototype of it lowered the transfer cost by 3e-6 to 8e-5 relative).
     The parameters are FundamentalRansac's; verify -> HomographyResult. A pair is valid from 4 inliers on, and a
     4-inlier winner is only its own sample: threshold num_inliers before trusting H."""
     _ENTRY, _RESULT = "lg_ransac_homography", HomographyResult

@@ -24,8 +24,14 @@ lg_ransac_solve5 hook alone on the call's own samples under the same method (sol
 candidates of every hypothesis without the scoring pass, the finalize launch and the pose). No framework arm: batched
 framework ops have no five-point solve to put next to it.
 
+--model essential --polish N: what the pose polish adds. EssentialRansac.verify at polish = 0 and at polish = N on
+calibrated_scene's pairs at 1 px of noise, alternating in the same repeats, and the PosePolish.refine hook alone on
+the call's own pose at N rounds and at 1 round (added_us: the medians' difference of the two verify arms;
+per_round_us: the hook's (N rounds - 1 round) / (N - 1); hook_one_round_us holds the launch, the staging, the first
+pass, the mask and the outputs). Written to profiles/geometry/ab_polish.jsonl unless --out is given.
+
     python tools/geometry_ab.py [--model fundamental|homography|essential] [--repeats 5] [--part all|verify|pipeline]
-                                [--out profiles/geometry/ab.jsonl]
+                                [--polish N] [--out profiles/geometry/ab.jsonl]
 """
 import argparse
 import json
@@ -38,7 +44,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "lightglue-with-flashattentionv2-tensorrt_amd")]
 import torch  # noqa: E402
 
-from lightglue_amd import (EssentialRansac, FundamentalRansac, HomographyRansac, ImageInput, KeypointFrontend, SuperPointEncoder,  # noqa: E402
+from lightglue_amd import (EssentialRansac, FundamentalRansac, HomographyRansac, ImageInput, KeypointFrontend, PosePolish,  # noqa: E402
+                           SuperPointEncoder,
                            calibrated_scene, match_source_images, matcher, planar_scene, ransac_samples, ransac_samples5,
                            seeded_superpoint_state_dict, two_view_scene, verify_source_images)
 from lightglue_amd._host import call  # noqa: E402
@@ -219,10 +226,15 @@ def spread(v):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "geometry", "ab.jsonl"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--polish", type=int, default=0, help="with --model essential: the A/B of verify at polish 0 and N")
     ap.add_argument("--part", choices=("all", "verify", "pipeline"), default="all")
     ap.add_argument("--model", choices=("fundamental", "homography", "essential"), default="fundamental")
     args = ap.parse_args()
+    if args.polish and args.model != "essential":
+        sys.exit("geometry_ab.py: --polish goes with --model essential")
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "geometry", "ab_polish.jsonl" if args.polish else "ab.jsonl")
     if not torch.cuda.is_available():
         sys.exit("geometry_ab.py: needs a GPU (timings from anywhere else mean nothing)")
     dev = torch.device("cuda:0")
@@ -241,7 +253,10 @@ def main():
         homography_part(args, dev, stream, base, emit, fr)
         return
     if args.model == "essential":
-        essential_part(args, dev, stream, base, emit, fr)
+        if args.polish:
+            polish_part(args, dev, stream, base, emit)
+        else:
+            essential_part(args, dev, stream, base, emit, fr)
         return
     for k in (256, 1024, 2048) if args.part != "pipeline" else ():
         k0, k1, gt, _ = two_view_scene(k, k, 0.25, 0.25)
@@ -366,6 +381,43 @@ def essential_part(args, dev, stream, base, emit, fr):
                            solve5_share_of_verify=round(statistics.median(t_solve) / statistics.median(t_ours), 3))
             emit(rec)
             del g, gf, gs
+
+
+def polish_part(args, dev, stream, base, emit):
+    n = args.polish
+    plain, fine = EssentialRansac(THR, H, R, SEED), EssentialRansac(THR, H, R, SEED, polish=n)
+    hook, hook1 = PosePolish(THR, n), PosePolish(THR, 1)
+    for k in (256, 1024, 2048):
+        k0, k1, gt, _, kk, _, _ = calibrated_scene(k, k, 0.25, 1.0)
+        for pr in (1, 16):
+            x0, x1 = k0.to(dev)[None].repeat(pr, 1, 1), k1.to(dev)[None].repeat(pr, 1, 1)
+            m = torch.arange(k, dtype=torch.int32, device=dev)[None, :, None].repeat(pr, 1, 2).contiguous()
+            counts = torch.full((pr,), k, dtype=torch.int32, device=dev)
+            intr = torch.tensor([[kk[0, 0], kk[1, 1], kk[0, 2], kk[1, 2]]] * 2, dtype=torch.float32, device=dev)[None].repeat(pr, 1, 1)
+            res = MatchResult(None, None, None, None, m, None, counts)
+            with torch.no_grad():
+                a = lambda: plain.verify(res, x0, x1, intr)  # noqa: E731
+                b = lambda: fine.verify(res, x0, x1, intr)   # noqa: E731
+                pose = a()
+                c = lambda: hook.refine(res, x0, x1, intr, pose)    # noqa: E731
+                d = lambda: hook1.refine(res, x0, x1, intr, pose)   # noqa: E731
+                out = c()
+                torch.cuda.synchronize()
+                cost = out.cost.cpu()
+                rec = dict(base, part="polish", model="essential", K=k, P=pr, polish=n, noise_px=1.0, kept=int(out.kept.sum()),
+                           inliers=[int(pose.num_inliers[0]), int(out.num_inliers[0])],
+                           cost_px2=[round(float(cost[0, 0]), 3), round(float(cost[0, 1]), 3)])
+                graphs = [graph_of(f, stream, CALLS) for f in (a, b, c, d)]
+                times = [[], [], [], []]
+                for _ in range(args.repeats):
+                    for g, t in zip(graphs, times):
+                        t.append(time_graph(g, stream, CALLS))
+                med = [statistics.median(t) for t in times]
+                rec.update(verify_us=spread(times[0]), verify_polish_us=spread(times[1]), hook_us=spread(times[2]),
+                           hook_one_round_us=spread(times[3]), added_us=round(med[1] - med[0], 2),
+                           per_round_us=round((med[2] - med[3]) / max(n - 1, 1), 2))
+            emit(rec)
+            del graphs
 
 
 if __name__ == "__main__":
