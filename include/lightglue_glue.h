@@ -445,7 +445,7 @@ int32_t lg_kp_to_source(const int32_t* kpts_px, const int32_t* counts, const int
  * device, from the matcher's outputs as they are. New symbols only: LG_GLUE_ABI_VERSION stays 4. Every call
  * checks its arguments before any device call, runs on `stream`, is a no-op for pairs == 0, keeps no state, uses
  * no atomics and allocates nothing; no workgroup reads what another wrote within a launch; every output entry is
- * written on every call. lightglue_amd/geometry.py restates the contract in float64 (ransac_reference).
+ * written on every call. lightglue_amd/geometry_contract.py restates the contract in float64 (ransac_reference).
  *
  * Inputs (shared by the four calls): matches [pairs, kmax, 2] int32 and counts [pairs] int32 (MatchResult's),
  * kpts0 [pairs, k0, 2], kpts1 [pairs, k1, 2] fp32 (x, y) in any pixel frame (lg_kp_to_source's output is the
@@ -460,7 +460,7 @@ int32_t lg_kp_to_source(const int32_t* kpts_px, const int32_t* counts, const int
  *   1. Hartley normalisation per image over all `count` correspondences (centroid to 0, mean distance sqrt 2;
  *      sums in fp64 in a fixed order).
  *   2. Hypothesis h samples 7 distinct indices: draw j = hash32(seed, h, j) % (count - j), moved past the earlier
- *      draws in ascending order (ransac_samples in geometry.py is the definition; the pair is not in the key).
+ *      draws in ascending order (ransac_samples in geometry_contract.py is the definition; the pair is not in the key).
  *   3. The 7-point solve in normalised coordinates, fp64 (an fp32 solve leaves its own sample points up to 0.5 px
  *      off their lines): Gauss-Jordan with row pivoting on the 7 x 9 system (a pivot below 1e-6: no
  *      candidate), the canonical null vectors f1 = (.., 1, 0), f2 = (.., 0, 1), the real roots l of
@@ -507,7 +507,7 @@ int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const flo
  * the epipolar constraint is degenerate (a planar scene, a purely rotating camera). The same kernels, templates on
  * the model. Inputs, clamping, limits and alignment are lg_ransac_fundamental's, and so is every general
  * statement above (arguments checked first, a no-op for pairs == 0, no atomics, no allocation, every output
- * entry written). lightglue_amd/geometry.py restates the contract in float64 (homography_reference).
+ * entry written). lightglue_amd/geometry_contract.py restates the contract in float64 (homography_reference).
  *
  * Model: x1 ~ H x0 with x = (x, y, 1), H row-major. Error of a correspondence (OpenCV's for findHomography with
  * RANSAC): (X, Y, W) = H x0, err = (x1 - X/W)² + (y1 - Y/W)²; an inlier iff err <= threshold². A non-finite err is
@@ -515,7 +515,7 @@ int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const flo
  * dx = x1 W - X, dy = y1 W - Y, W² > 0 and the left side finite. Per pair, independently:
  *   1. Hartley normalisation, as step 1 above.
  *   2. Hypothesis h samples 4 distinct indices: the first four draws of step 2 above (for count >= 7 the first
- *      four columns of the 7-sample; defined from count = 4 on; ransac_samples(size=4) in geometry.py).
+ *      four columns of the 7-sample; defined from count = 4 on; ransac_samples(size=4) in geometry_contract.py).
  *   3. The 4-point solve in normalised coordinates, fp64 (for the reason of the 7-point solve; the fp32 figures
  *      are in profiles/geometry/INDEX.md): the 8 x 9 system of two rows a point,
  *      (-x0, -y0, -1, 0, 0, 0, x1 x0, x1 y0, x1) and (0, 0, 0, -x0, -y0, -1, y1 x0, y1 y0, y1), by Gauss-Jordan with
@@ -561,7 +561,7 @@ int32_t lg_ransac_score_homography(const int32_t* matches, const int32_t* counts
  * degenerate on planar scenes, which the 7- and 8-point solves are. Inputs, clamping, limits and alignment are
  * lg_ransac_fundamental's, and so is every general statement above (arguments checked first, a no-op for
  * pairs == 0, counts and indices clamped, no atomics, no allocation, every output entry written).
- * lightglue_amd/geometry.py restates the contract in float64 (essential_reference).
+ * lightglue_amd/geometry_contract.py restates the contract in float64 (essential_reference).
  *
  * Extra input: intrinsics [pairs, 2, 4] fp32, (fx, fy, cx, cy) of image 0 then image 1 in the pixel frame of the
  * keypoints. Model: x1ᵀ E x0 = 0 in camera coordinates q = ((x - cx) / fx, (y - cy) / fy) (fp64), E row-major;
@@ -623,7 +623,7 @@ int32_t lg_pose_from_essential(const int32_t* matches, const int32_t* counts, co
  * the inliers. lg_pose_polish does, and lg_triangulate writes the points of the result. New symbols only:
  * LG_GLUE_ABI_VERSION stays 4. The general statements of lg_ransac_fundamental hold (arguments checked before any
  * device call, a no-op for pairs == 0, counts and indices clamped, no atomics, no allocation, no workspace, every output
- * entry written). lightglue_amd/geometry.py restates the contract in float64 by another route (polish_reference:
+ * entry written). lightglue_amd/geometry_contract.py restates the contract in float64 by another route (polish_reference:
  * scipy's least squares to convergence in another parameterisation; the converged minimiser is what is compared).
  *
  * Inputs: lg_ransac_essential's pair arguments and intrinsics; r [pairs, 3, 3], t [pairs, 3] fp32; inliers

@@ -1,8 +1,9 @@
 // lightglue_essential.hip — calibrated relative pose (include/lightglue_glue.h, "geometric verification"): an
 // essential matrix per image pair by five-point RANSAC over the matcher's matches, and (R, t) from it, by the scheme
 // of lightglue_geometry.hip, whose launch shapes and helpers (lightglue_geometry_device.h) this file shares. The
-// contract is restated in float64 in lightglue_amd/geometry.py; the arithmetic is in lightglue_essential_math.h, and what
-// the pose polish (lightglue_polish.hip) shares with this file in lightglue_essential_device.h.
+// contract is restated in float64 in lightglue_amd/geometry_contract.py; the arithmetic is in
+// lightglue_essential_math.h, and what the pose polish (lightglue_polish.hip) shares with this file in
+// lightglue_essential_device.h.
 //
 // Two launches. essential_hypothesis_kernel: grid (hypothesis blocks, pairs), 64 hypotheses a workgroup, four
 // adjacent lanes a hypothesis. The workgroup gathers the pair's correspondences into LDS once. The four lanes hash
@@ -254,27 +255,7 @@ __global__ __launch_bounds__(kFinThreads) void essential_finalize_kernel(PairArg
         for (int round = 0; round < refits && num >= kMinInliers; ++round) {
             // normalised least squares over the inliers in camera coordinates (8-point)
             double c[4], s[2];
-            {
-                double sum[4] = {0.0, 0.0, 0.0, 0.0}, dist[2] = {0.0, 0.0};
-                for (int k = tid; k < count; k += kFinThreads) {
-                    if (!mask[k]) continue;
-                    double q[4];
-                    camera(pts[k], kk, q);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) sum[i] += q[i];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) c[i] = block_sum<kFinThreads>(sum[i], buf, tid) / (double)num;
-                for (int k = tid; k < count; k += kFinThreads) {
-                    if (!mask[k]) continue;
-                    double q[4];
-                    camera(pts[k], kk, q);
-                    const double ax = q[0] - c[0], ay = q[1] - c[1], bx = q[2] - c[2], by = q[3] - c[3];
-                    dist[0] += sqrt(ax * ax + ay * ay), dist[1] += sqrt(bx * bx + by * by);
-                }
-#pragma unroll
-                for (int i = 0; i < 2; ++i) s[i] = 1.4142135623730951 / (block_sum<kFinThreads>(dist[i], buf, tid) / (double)num);
-            }
+            hartley<kFinThreads>(pts, mask, count, (double)num, buf, tid, c, s, CameraCoord{kk});
             {
                 double acc[45];
 #pragma unroll
@@ -285,18 +266,8 @@ __global__ __launch_bounds__(kFinThreads) void essential_finalize_kernel(PairArg
                     camera(pts[k], kk, q);
                     normal_accumulate_f(acc, (q[0] - c[0]) * s[0], (q[1] - c[1]) * s[0], (q[2] - c[2]) * s[1], (q[3] - c[3]) * s[1]);
                 }
-                wave_sums(acc, part, tid);
+                normal_eigenvector(acc, part, am, vm, rot, tid);
             }
-            __syncthreads();
-            if (tid < 45) {
-                int i, j;
-                tri_index(tid, i, j);
-                const double v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-                am[9 * i + j] = v, am[9 * j + i] = v;
-            }
-            if (tid < 81) vm[tid] = tid / 9 == tid % 9 ? 1.0 : 0.0;
-            __syncthreads();
-            jacobi9(am, vm, rot, tid);
             if (tid == 0) {
                 int lo = 0;
                 for (int k = 1; k < 9; ++k) lo = am[10 * k] < am[10 * lo] ? k : lo;
@@ -378,10 +349,9 @@ int32_t lg_ransac_essential(const int32_t* matches, const int32_t* counts, const
                             int32_t* best, hipStream_t stream) {
     const char* who = "lg_ransac_essential";
     if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !intrinsics || !aligned4(intrinsics) ||
-        !threshold_ok(threshold) || hypotheses < 1 || hypotheses > kMaxHypotheses || refits < 0 || refits > kMaxRefits ||
-        !workspace || !aligned16(workspace) || workspace_bytes < pose_bytes(pairs, hypotheses) || !e || !r || !t || !inliers ||
-        !num_inliers || !num_front || !valid || !best || !aligned4(e) || !aligned4(r) || !aligned4(t) || !aligned4(num_inliers) ||
-        !aligned4(num_front) || !aligned4(valid) || !aligned4(best))
+        !ransac_args_ok(threshold, hypotheses, refits, workspace, workspace_bytes, pose_bytes(pairs, hypotheses), e, inliers,
+                        num_inliers, valid, best) ||
+        !r || !t || !num_front || !aligned4(r) || !aligned4(t) || !aligned4(num_front))
         return bad(who);
     if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
     const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
@@ -395,12 +365,7 @@ int32_t lg_ransac_essential(const int32_t* matches, const int32_t* counts, const
 }
 
 int32_t lg_ransac_samples5(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream) {
-    const char* who = "lg_ransac_samples5";
-    if (count < 5 || count > kMaxPoints || hypotheses < 1 || hypotheses > kMaxHypotheses || !samples || !aligned4(samples))
-        return bad(who);
-    hipLaunchKernelGGL(ransac_samples_kernel<5>, dim3((hypotheses + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, stream, count,
-                       hypotheses, (uint32_t)seed, samples);
-    return launched(who);
+    return samples_call<5>("lg_ransac_samples5", count, hypotheses, seed, samples, stream);
 }
 
 int32_t lg_ransac_solve5(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
@@ -408,8 +373,7 @@ int32_t lg_ransac_solve5(const int32_t* matches, const int32_t* counts, const fl
                          int32_t hypotheses, float* candidates, int32_t* num, hipStream_t stream) {
     const char* who = "lg_ransac_solve5";
     if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !intrinsics || !aligned4(intrinsics) ||
-        hypotheses < 1 || hypotheses > kMaxHypotheses || !samples || !candidates || !num || !aligned4(samples) ||
-        !aligned4(candidates) || !aligned4(num))
+        !solve_args_ok(hypotheses, samples, candidates, num))
         return bad(who);
     if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
     const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};

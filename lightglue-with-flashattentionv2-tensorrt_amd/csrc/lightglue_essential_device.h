@@ -18,6 +18,12 @@ __device__ __forceinline__ void camera(const float4 q, const Intrinsics& k, doub
     c[2] = ((double)q.z - k.cx1) / k.fx1, c[3] = ((double)q.w - k.cy1) / k.fy1;
 }
 
+// hartley's coordinates for the essential matrix's refit: camera(q, kk, ·).
+struct CameraCoord {
+    const Intrinsics& kk;
+    __device__ __forceinline__ void operator()(const float4 q, double c[4]) const { camera(q, kk, c); }
+};
+
 // Marks the inliers of f into m and returns their number (every thread).
 __device__ __forceinline__ int mark_inliers(const float f[9], const float4* pts, int count, float thr2, uint8_t* m, double* buf,
                                             int tid) {

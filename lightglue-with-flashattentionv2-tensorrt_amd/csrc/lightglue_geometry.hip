@@ -3,7 +3,7 @@
 // host with cv::findFundamentalMat(points0, points1, cv::FM_RANSAC, 3, 0.99, inliers) after PostProcess
 // (demo/demo_mono.cpp:326-366), and a homography by the same scheme (cv::findHomography(points0, points1,
 // cv::RANSAC, 3) without its final Levenberg-Marquardt polish). The contract is restated in float64 in
-// lightglue_amd/geometry.py. The kernels are templates on the model (FundamentalModel, HomographyModel below):
+// lightglue_amd/geometry_contract.py. The kernels are templates on the model (FundamentalModel, HomographyModel below):
 // the sample size, the minimal solve, the error, the refit's rows and its last step are the model's, the rest
 // is shared. The description that follows is in the fundamental matrix's numbers (the homography's: 4 indices,
 // the 4-point system, one candidate, no rank step).
@@ -19,8 +19,8 @@
 // inliers, runs the refits in fp64 (normal matrix, a round-robin Jacobi on the 9 x 9, rank 2, de-normalise) and
 // writes every output. No atomics, no allocation, no host synchronisation; no workgroup reads what another
 // wrote within a launch. The arithmetic is in lightglue_geometry_math.h; what the kernels share with the five-point
-// RANSAC of lightglue_essential.hip (launch shapes, a pair's staging, the ordered sums, the Jacobi loop, the argument
-// checks) is in lightglue_geometry_device.h.
+// RANSAC of lightglue_essential.hip (launch shapes, a pair's staging, the ordered sums, the Hartley
+// normalisation, the normal matrix's eigenvectors, the argument checks) is in lightglue_geometry_device.h.
 #include "lightglue_geometry_device.h"
 
 namespace {
@@ -28,31 +28,6 @@ namespace {
 using namespace lg_geom;
 
 constexpr int kHypRecord = 12;   // floats per hypothesis in the workspace: F[9], count, root, pad
-
-// Hartley normalisation over the correspondences k < count with use[k] != 0 (use == nullptr: all): centroid
-// and sqrt(2) / mean distance per image, each thread's share summed in ascending k, the shares by block_sum.
-// n: the number of correspondences used (> 0).
-template <int NT>
-__device__ __forceinline__ void hartley(const float4* pts, const uint8_t* use, int count, double n, double* buf, int tid,
-                                        double c[4], double s[2]) {
-    double sum[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int k = tid; k < count; k += NT) {
-        if (use && !use[k]) continue;
-        const float4 q = pts[k];
-        sum[0] += (double)q.x, sum[1] += (double)q.y, sum[2] += (double)q.z, sum[3] += (double)q.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = block_sum<NT>(sum[i], buf, tid) / n;
-    double dist[2] = {0.0, 0.0};
-    for (int k = tid; k < count; k += NT) {
-        if (use && !use[k]) continue;
-        const float4 q = pts[k];
-        const double ax = (double)q.x - c[0], ay = (double)q.y - c[1], bx = (double)q.z - c[2], by = (double)q.w - c[3];
-        dist[0] += sqrt(ax * ax + ay * ay), dist[1] += sqrt(bx * bx + by * by);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) s[i] = 1.4142135623730951 / (block_sum<NT>(dist[i], buf, tid) / n);
-}
 
 // ---- the models ---------------------------------------------------------------------------------------------------
 // kSample: indices a hypothesis; kCands: candidates a hypothesis at most; kMin: correspondences a model, a winner
@@ -116,7 +91,7 @@ __global__ __launch_bounds__(kHypThreads) void ransac_hypothesis_kernel(PairArgs
     if (count >= M::kMin) {  // (the same for the whole workgroup)
         stage_pair(a, p, count, pts, tid, kHypThreads);
         double c[4], s[2];
-        hartley<kHypThreads>(pts, nullptr, count, (double)count, buf, tid, c, s);
+        hartley<kHypThreads>(pts, nullptr, count, (double)count, buf, tid, c, s, PixelCoord{});
         const NormT<double> t{c[0], c[1], s[0], c[2], c[3], s[1]};
         if (live) {  // (the lanes of a hypothesis solve it alike: the same statements on the same values)
             int idx[NS];
@@ -256,9 +231,9 @@ __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a
             if (round >= refits || num < M::kMin) break;
             // normalised least squares over the inliers (8-point; the homography's DLT)
             double c[4], s[2];
-            hartley<kFinThreads>(pts, mask, count, (double)num, buf, tid, c, s);
+            hartley<kFinThreads>(pts, mask, count, (double)num, buf, tid, c, s, PixelCoord{});
             {   // the upper triangle of the normal matrix: a thread sums its inliers (every 256th from tid on, in
-                // ascending order) into 45 registers, a wave adds its lanes in a tree, the four waves in order
+                // ascending order) into 45 registers
                 double acc[45];
 #pragma unroll
                 for (int e = 0; e < 45; ++e) acc[e] = 0.0;
@@ -269,18 +244,8 @@ __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a
                     const double x1 = ((double)q.z - c[2]) * s[1], y1 = ((double)q.w - c[3]) * s[1];
                     M::accumulate(acc, x0, y0, x1, y1);
                 }
-                wave_sums(acc, part, tid);
+                normal_eigenvector(acc, part, am, vm, rot, tid);
             }
-            __syncthreads();
-            if (tid < 45) {
-                int i, j;
-                tri_index(tid, i, j);
-                const double v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-                am[9 * i + j] = v, am[9 * j + i] = v;
-            }
-            if (tid < 81) vm[tid] = tid / 9 == tid % 9 ? 1.0 : 0.0;
-            __syncthreads();
-            jacobi9(am, vm, rot, tid);
             if (tid == 0) {
                 int lo = 0;
                 for (int k = 1; k < 9; ++k) lo = am[10 * k] < am[10 * lo] ? k : lo;
@@ -304,6 +269,54 @@ __global__ __launch_bounds__(kFinThreads) void ransac_finalize_kernel(PairArgs a
 
 size_t hyp_bytes(int32_t pairs, int32_t hypotheses) { return (size_t)pairs * hypotheses * kHypRecord * sizeof(float); }
 
+// The entry points below, one per model M.
+template <class M>
+int32_t ransac_call(const char* who, const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                    int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold, int32_t hypotheses, int32_t refits,
+                    int32_t seed, void* workspace, size_t workspace_bytes, float* m, uint8_t* inliers, int32_t* num_inliers,
+                    int32_t* valid, int32_t* best, hipStream_t stream) {
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) ||
+        !ransac_args_ok(threshold, hypotheses, refits, workspace, workspace_bytes, hyp_bytes(pairs, hypotheses), m, inliers,
+                        num_inliers, valid, best))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    const float thr2 = threshold * threshold;
+    hipLaunchKernelGGL((ransac_hypothesis_kernel<M, false>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream, a,
+                       hypotheses, (uint32_t)seed, thr2, (const int32_t*)nullptr, (float*)workspace, (float*)nullptr,
+                       (int32_t*)nullptr);
+    hipLaunchKernelGGL(ransac_finalize_kernel<M>, dim3(pairs), dim3(kFinThreads), 0, stream, a, hypotheses, refits, thr2,
+                       (const float*)workspace, m, inliers, num_inliers, valid, best);
+    return launched(who);
+}
+
+template <class M>
+int32_t solve_call(const char* who, const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                   int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses,
+                   float* candidates, int32_t* num, hipStream_t stream) {
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !solve_args_ok(hypotheses, samples, candidates, num))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    hipLaunchKernelGGL((ransac_hypothesis_kernel<M, true>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream, a,
+                       hypotheses, 0u, 1.f, samples, (float*)nullptr, candidates, num);
+    return launched(who);
+}
+
+template <class M>
+int32_t score_call(const char* who, const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
+                   int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* candidates, int32_t num_candidates,
+                   float threshold, int32_t* inlier_counts, hipStream_t stream) {
+    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) ||
+        !score_args_ok(threshold, num_candidates, candidates, inlier_counts))
+        return bad(who);
+    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
+    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
+    hipLaunchKernelGGL(ransac_score_kernel<M>, hyp_grid(num_candidates, pairs), dim3(kHypLanes), 0, stream, a, candidates,
+                       num_candidates, threshold * threshold, inlier_counts);
+    return launched(who);
+}
+
 }  // namespace
 
 extern "C" {
@@ -317,116 +330,54 @@ int32_t lg_ransac_fundamental(const int32_t* matches, const int32_t* counts, con
                               int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold, int32_t hypotheses,
                               int32_t refits, int32_t seed, void* workspace, size_t workspace_bytes, float* f,
                               uint8_t* inliers, int32_t* num_inliers, int32_t* valid, int32_t* best, hipStream_t stream) {
-    const char* who = "lg_ransac_fundamental";
-    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || hypotheses < 1 ||
-        hypotheses > kMaxHypotheses || refits < 0 || refits > kMaxRefits || !workspace || !aligned16(workspace) ||
-        workspace_bytes < hyp_bytes(pairs, hypotheses) || !f || !inliers || !num_inliers || !valid || !best || !aligned4(f) ||
-        !aligned4(num_inliers) || !aligned4(valid) || !aligned4(best))
-        return bad(who);
-    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
-    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    const float thr2 = threshold * threshold;
-    hipLaunchKernelGGL((ransac_hypothesis_kernel<FundamentalModel, false>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0,
-                       stream, a, hypotheses, (uint32_t)seed, thr2, (const int32_t*)nullptr, (float*)workspace, (float*)nullptr,
-                       (int32_t*)nullptr);
-    hipLaunchKernelGGL(ransac_finalize_kernel<FundamentalModel>, dim3(pairs), dim3(kFinThreads), 0, stream, a, hypotheses, refits,
-                       thr2, (const float*)workspace, f, inliers, num_inliers, valid, best);
-    return launched(who);
-}
-
-int32_t lg_ransac_samples(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream) {
-    const char* who = "lg_ransac_samples";
-    if (count < 7 || count > kMaxPoints || hypotheses < 1 || hypotheses > kMaxHypotheses || !samples || !aligned4(samples))
-        return bad(who);
-    hipLaunchKernelGGL(ransac_samples_kernel<7>, dim3((hypotheses + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, stream, count,
-                       hypotheses, (uint32_t)seed, samples);
-    return launched(who);
-}
-
-int32_t lg_ransac_solve7(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
-                         int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses, float* candidates,
-                         int32_t* num_roots, hipStream_t stream) {
-    const char* who = "lg_ransac_solve7";
-    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || hypotheses < 1 || hypotheses > kMaxHypotheses ||
-        !samples || !candidates || !num_roots || !aligned4(samples) || !aligned4(candidates) || !aligned4(num_roots))
-        return bad(who);
-    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
-    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    hipLaunchKernelGGL((ransac_hypothesis_kernel<FundamentalModel, true>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0,
-                       stream, a, hypotheses, 0u, 1.f, samples, (float*)nullptr, candidates, num_roots);
-    return launched(who);
-}
-
-int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
-                        int32_t kmax, int32_t k0, int32_t k1, const float* candidates, int32_t num_candidates, float threshold,
-                        int32_t* inlier_counts, hipStream_t stream) {
-    const char* who = "lg_ransac_score";
-    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || num_candidates < 1 ||
-        num_candidates > kMaxHypotheses || !candidates || !inlier_counts || !aligned4(candidates) || !aligned4(inlier_counts))
-        return bad(who);
-    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
-    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    hipLaunchKernelGGL(ransac_score_kernel<FundamentalModel>, hyp_grid(num_candidates, pairs), dim3(kHypLanes), 0, stream, a,
-                       candidates, num_candidates, threshold * threshold, inlier_counts);
-    return launched(who);
+    return ransac_call<FundamentalModel>("lg_ransac_fundamental", matches, counts, kpts0, kpts1, pairs, kmax, k0, k1, threshold,
+                                         hypotheses, refits, seed, workspace, workspace_bytes, f, inliers, num_inliers, valid,
+                                         best, stream);
 }
 
 int32_t lg_ransac_homography(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
                              int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, float threshold, int32_t hypotheses,
                              int32_t refits, int32_t seed, void* workspace, size_t workspace_bytes, float* h,
                              uint8_t* inliers, int32_t* num_inliers, int32_t* valid, int32_t* best, hipStream_t stream) {
-    const char* who = "lg_ransac_homography";
-    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || hypotheses < 1 ||
-        hypotheses > kMaxHypotheses || refits < 0 || refits > kMaxRefits || !workspace || !aligned16(workspace) ||
-        workspace_bytes < hyp_bytes(pairs, hypotheses) || !h || !inliers || !num_inliers || !valid || !best || !aligned4(h) ||
-        !aligned4(num_inliers) || !aligned4(valid) || !aligned4(best))
-        return bad(who);
-    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
-    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    const float thr2 = threshold * threshold;
-    hipLaunchKernelGGL((ransac_hypothesis_kernel<HomographyModel, false>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0,
-                       stream, a, hypotheses, (uint32_t)seed, thr2, (const int32_t*)nullptr, (float*)workspace, (float*)nullptr,
-                       (int32_t*)nullptr);
-    hipLaunchKernelGGL(ransac_finalize_kernel<HomographyModel>, dim3(pairs), dim3(kFinThreads), 0, stream, a, hypotheses, refits,
-                       thr2, (const float*)workspace, h, inliers, num_inliers, valid, best);
-    return launched(who);
+    return ransac_call<HomographyModel>("lg_ransac_homography", matches, counts, kpts0, kpts1, pairs, kmax, k0, k1, threshold,
+                                        hypotheses, refits, seed, workspace, workspace_bytes, h, inliers, num_inliers, valid, best,
+                                        stream);
+}
+
+int32_t lg_ransac_samples(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream) {
+    return samples_call<7>("lg_ransac_samples", count, hypotheses, seed, samples, stream);
 }
 
 int32_t lg_ransac_samples4(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream) {
-    const char* who = "lg_ransac_samples4";
-    if (count < 4 || count > kMaxPoints || hypotheses < 1 || hypotheses > kMaxHypotheses || !samples || !aligned4(samples))
-        return bad(who);
-    hipLaunchKernelGGL(ransac_samples_kernel<4>, dim3((hypotheses + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, stream, count,
-                       hypotheses, (uint32_t)seed, samples);
-    return launched(who);
+    return samples_call<4>("lg_ransac_samples4", count, hypotheses, seed, samples, stream);
+}
+
+int32_t lg_ransac_solve7(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                         int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses, float* candidates,
+                         int32_t* num_roots, hipStream_t stream) {
+    return solve_call<FundamentalModel>("lg_ransac_solve7", matches, counts, kpts0, kpts1, pairs, kmax, k0, k1, samples, hypotheses,
+                                        candidates, num_roots, stream);
 }
 
 int32_t lg_ransac_solve4(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
                          int32_t kmax, int32_t k0, int32_t k1, const int32_t* samples, int32_t hypotheses, float* candidates,
                          int32_t* num, hipStream_t stream) {
-    const char* who = "lg_ransac_solve4";
-    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || hypotheses < 1 || hypotheses > kMaxHypotheses ||
-        !samples || !candidates || !num || !aligned4(samples) || !aligned4(candidates) || !aligned4(num))
-        return bad(who);
-    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
-    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    hipLaunchKernelGGL((ransac_hypothesis_kernel<HomographyModel, true>), hyp_grid(hypotheses, pairs), dim3(kHypThreads), 0, stream,
-                       a, hypotheses, 0u, 1.f, samples, (float*)nullptr, candidates, num);
-    return launched(who);
+    return solve_call<HomographyModel>("lg_ransac_solve4", matches, counts, kpts0, kpts1, pairs, kmax, k0, k1, samples, hypotheses,
+                                       candidates, num, stream);
+}
+
+int32_t lg_ransac_score(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1, int32_t pairs,
+                        int32_t kmax, int32_t k0, int32_t k1, const float* candidates, int32_t num_candidates, float threshold,
+                        int32_t* inlier_counts, hipStream_t stream) {
+    return score_call<FundamentalModel>("lg_ransac_score", matches, counts, kpts0, kpts1, pairs, kmax, k0, k1, candidates,
+                                        num_candidates, threshold, inlier_counts, stream);
 }
 
 int32_t lg_ransac_score_homography(const int32_t* matches, const int32_t* counts, const float* kpts0, const float* kpts1,
                                    int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* candidates,
                                    int32_t num_candidates, float threshold, int32_t* inlier_counts, hipStream_t stream) {
-    const char* who = "lg_ransac_score_homography";
-    if (!pair_args_ok(matches, counts, kpts0, kpts1, pairs, kmax, k0, k1) || !threshold_ok(threshold) || num_candidates < 1 ||
-        num_candidates > kMaxHypotheses || !candidates || !inlier_counts || !aligned4(candidates) || !aligned4(inlier_counts))
-        return bad(who);
-    if (pairs == 0) return MHA_HD64_STATUS_SUCCESS;
-    const PairArgs a{matches, counts, kpts0, kpts1, kmax, k0, k1};
-    hipLaunchKernelGGL(ransac_score_kernel<HomographyModel>, hyp_grid(num_candidates, pairs), dim3(kHypLanes), 0, stream, a,
-                       candidates, num_candidates, threshold * threshold, inlier_counts);
-    return launched(who);
+    return score_call<HomographyModel>("lg_ransac_score_homography", matches, counts, kpts0, kpts1, pairs, kmax, k0, k1, candidates,
+                                       num_candidates, threshold, inlier_counts, stream);
 }
 
 }  // extern "C"

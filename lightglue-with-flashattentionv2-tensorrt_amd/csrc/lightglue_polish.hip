@@ -2,7 +2,7 @@
 // caller does with lg_ransac_essential's (R, t) next. lg_pose_polish minimises the squared Sampson distance in pixels
 // over the pose's inliers by Levenberg-Marquardt on the 5 parameters of (R, t), recomputes the mask and keeps the
 // result where it loses no inlier; lg_triangulate writes the 3D point of every inlier. The contract is restated in
-// float64 in lightglue_amd/geometry.py (by another route: scipy's least squares in another parameterisation); the
+// float64 in lightglue_amd/geometry_contract.py (by another route: scipy's least squares in another parameterisation); the
 // arithmetic is in lightglue_polish_math.h.
 //
 // pose_polish_kernel: one workgroup of kFinThreads per pair, the shape of essential_finalize_kernel. The pair's

@@ -7,1053 +7,76 @@ inliers (demo/demo_mono.cpp:326-366). ``FundamentalRansac.verify`` is that step 
 ``MatchResult`` in two launches, with nothing read back: ``verify_source_images`` is ``match_source_images``
 followed by it, still one capturable piece.
 
-The contract is pinned here in float64 on the CPU: ``ransac_samples`` (the minimal samples, which the kernel
-equals bitwise), ``epipolar_error``, ``solve7_reference`` (an SVD null space and ``numpy.roots``, deliberately
-not the kernel's elimination and closed form), ``fundamental_refit`` and ``ransac_reference`` (the whole).
-``two_view_scene`` makes the synthetic pairs the tests use.
-
 ``HomographyRansac.verify`` is the same scheme for the homography x1 ~ H x0 (planar scenes and rotating cameras,
 where the epipolar constraint is degenerate): ``cv::findHomography(pts0, pts1, cv::RANSAC, 3)`` without its final
-Levenberg-Marquardt polish. Its float64 contract: ``ransac_samples(size=4)``, ``transfer_error``,
-``solve4_reference`` (an SVD null vector scaled to the canonical one, not the kernel's elimination),
-``homography_refit`` and ``homography_reference``; ``planar_scene`` makes its pairs.
+Levenberg-Marquardt polish.
 
 ``EssentialRansac.verify`` is the calibrated case (csrc/lightglue_essential.hip): five-point RANSAC for the essential
-matrix and the relative pose (R, t) from it, given each image's (fx, fy, cx, cy). Its float64 contract:
-``ransac_samples5``, ``solve5_reference`` (an SVD null space, the ten constraints by generic polynomial products, the
-eigenvalues of the cubic matrix pencil in the hidden variable: not the kernel's elimination and degree-10
-polynomial), ``essential_refit``, ``pose_from_essential_reference`` and ``essential_reference``;
-``calibrated_scene`` and ``calibrated_planar_scene`` are the scenes above with their cameras.
+matrix and the relative pose (R, t) from it, given each image's (fx, fy, cx, cy).
 
 ``PosePolish.refine`` (csrc/lightglue_polish.hip; ``EssentialRansac(polish=N)`` appends it) minimises the squared
 Sampson distance in pixels over the pose's inliers by N rounds of Levenberg-Marquardt on the 5 parameters of (R, t),
 recomputes the mask and keeps the result where it loses no inlier; ``triangulate`` writes every inlier's 3D point.
-Their float64 contract: ``sampson_error``, ``polish_pose_reference`` (``scipy.optimize.least_squares(method="lm")``
-on a global rotation vector and two angles of t with a numeric Jacobian, deliberately not the kernel's route: the
-converged minimiser is what is compared), ``polish_reference`` (a batch of it) and ``triangulate_reference``.
+
+This module is the kernel side only. What each call computes is pinned in float64 in geometry_contract.py, and the
+synthetic pairs of the tests are in geometry_scenes.py; both are re-exported here.
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Tuple
-
-import numpy as np
 import torch
 
-from . import _lib, synth
+from . import _lib
 from ._host import call, carve, require_gpu, stream_of
+from .geometry_contract import (  # noqa: F401  (the public names this module had before the contract was split off)
+    _M32, MAX_HYPOTHESES, MAX_REFITS, MIN_INLIERS, MIN_INLIERS_E, MIN_INLIERS_H, MIN_POLISH_ROWS, PIVOT_EPS, GeometryResult,
+    HomographyResult, PolishResult, PoseResult, Solve4, Solve5, Solve7, _check_params, _rows, camera_coordinates, direction_angle_deg,
+    elimination_pivots, epipolar_error, essential_constraints, essential_reference, essential_refit, essential_residuals,
+    essential_to_fundamental, fundamental_refit, gather_correspondences, homography_reference, homography_refit,
+    polish_pose_reference, polish_reference, pose_candidates, pose_from_essential_reference, ransac_reference, ransac_samples,
+    ransac_samples5, rotation_angle_deg, sampson_error, solve4_reference, solve5_reference, solve7_reference, transfer_error,
+    triangulate_reference)
+from .geometry_scenes import calibrated_planar_scene, calibrated_scene, planar_scene, two_view_scene  # noqa: F401
 from .image import ImageInput, match_source_images
 from .matches import MatchResult
 
 _STAGE = "the geometric verification"
 MAX_POINTS = 2048       # kmax: the plugin's N limit
-MAX_HYPOTHESES = 4096
-MAX_REFITS = 8
 MAX_POLISH = 16         # rounds of the pose polish
-MIN_POLISH_ROWS = 5     # the polish's fixed set needs as many rows as there are parameters
-MIN_INLIERS = 8         # a fundamental matrix, and its refit, needs 8 correspondences
-MIN_INLIERS_H = 4       # a homography, and its refit, needs 4
-MIN_INLIERS_E = 5       # an essential matrix needs 5 (its refit 8, as the fundamental matrix's)
-PIVOT_EPS = 1e-6        # a pivot of the 7 x 9 (8 x 9) elimination below this: no candidate
-_M32 = 0xFFFFFFFF
 
+# A result field's shape after [P] (None: Kmax) and dtype on the device; every field not named here is [P] int32.
+_FIELDS = {"F": ((3, 3), torch.float32), "H": ((3, 3), torch.float32), "E": ((3, 3), torch.float32),
+           "R": ((3, 3), torch.float32), "t": ((3,), torch.float32), "cost": ((2,), torch.float32),
+           "inliers": ((None,), torch.uint8)}
 
-class GeometryResult(NamedTuple):
-    """F [P, 3, 3] (x1ᵀ F x0 = 0, unit Frobenius norm, the entry of the largest magnitude positive; zeros where
-    valid == 0), inliers [P, Kmax] uint8 aligned with the rows of MatchResult.matches (0 past the count),
-    num_inliers, valid, best [P] int32 (best: the winning hypothesis, -1 where valid == 0)."""
-    F: torch.Tensor
-    inliers: torch.Tensor
-    num_inliers: torch.Tensor
-    valid: torch.Tensor
-    best: torch.Tensor
 
+def _empty(result, pr: int, kmax: int, dev):
+    """The result tuple's tensors for P pairs, uninitialised on dev."""
+    def one(name):
+        shape, dtype = _FIELDS.get(name, ((), torch.int32))
+        return torch.empty((pr,) + tuple(kmax if s is None else s for s in shape), dtype=dtype, device=dev)
 
-class HomographyResult(NamedTuple):
-    """H [P, 3, 3] (x1 ~ H x0, unit Frobenius norm, the entry of the largest magnitude positive; zeros where
-    valid == 0), inliers [P, Kmax] uint8 aligned with the rows of MatchResult.matches (0 past the count),
-    num_inliers, valid, best [P] int32 (best: the winning hypothesis, -1 where valid == 0). A pair is valid from 4
-    inliers on, and a 4-inlier winner is only its own sample: threshold num_inliers before trusting H."""
-    H: torch.Tensor
-    inliers: torch.Tensor
-    num_inliers: torch.Tensor
-    valid: torch.Tensor
-    best: torch.Tensor
+    return result(*(one(name) for name in result._fields))
 
 
-class PoseResult(NamedTuple):
-    """E [P, 3, 3] (x1ᵀ E x0 = 0 in camera coordinates, canonical: unit Frobenius norm, the entry of the largest
-    magnitude positive), R [P, 3, 3] and t [P, 3] (X1 = R X0 + t, det R = +1, |t| = 1, E ∝ [t]× R), inliers [P, Kmax]
-    uint8 aligned with the rows of MatchResult.matches (0 past the count), num_inliers, num_front (the inliers that
-    triangulate in front of both cameras under (R, t)), valid, best [P] int32 (best: the winning hypothesis, -1 where
-    valid == 0; every other output is zeros there). A pair is valid from 5 inliers on, and a 5-inlier winner is
-    only its own sample: threshold num_inliers (and num_front) before trusting the pose."""
-    E: torch.Tensor
-    R: torch.Tensor
-    t: torch.Tensor
-    inliers: torch.Tensor
-    num_inliers: torch.Tensor
-    num_front: torch.Tensor
-    valid: torch.Tensor
-    best: torch.Tensor
+def _like_matches(name: str, t: torch.Tensor, shape, matches: torch.Tensor) -> None:
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name}: expected {list(shape)}, got {tuple(t.shape)}")
+    if t.device != matches.device:
+        raise ValueError(f"{name}: on {t.device}, the matches on {matches.device}")
 
 
-class PolishResult(NamedTuple):
-    """The pose polish's outputs. E, R, t, inliers, num_inliers, num_front as PoseResult's; cost [P, 2] fp32: the sum of
-    squared Sampson residuals (px²) over the fixed set (the given inliers with a finite residual) under the given
-    and under the returned pose; kept [P] int32: 1 where the polished pose is returned (its mask, recomputed over all
-    the pair's correspondences, has at least as many inliers as the given one), 0 where the given pose and mask are
-    passed through (both costs are then the entering one; every output but R, t and the mask is zeros where the
-    given pose was invalid)."""
-    E: torch.Tensor
-    R: torch.Tensor
-    t: torch.Tensor
-    inliers: torch.Tensor
-    num_inliers: torch.Tensor
-    num_front: torch.Tensor
-    cost: torch.Tensor
-    kept: torch.Tensor
-
-
-# ---- the minimal samples --------------------------------------------------------------------------------------
-def _hash32(seed: int, h: np.ndarray, j: int) -> np.ndarray:
-    """The counter-based hash of (seed, hypothesis, draw), uint32 arithmetic: the key folded by odd multipliers,
-    then the lowbias32 finaliser."""
-    x = ((seed & _M32) * 0x9E3779B1 + h.astype(np.uint64) * 0x85EBCA77 + j * 0xC2B2AE3D + 0x27D4EB2F) & _M32
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & _M32
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & _M32
-    x ^= x >> 16
-    return x
-
-
-def ransac_samples(seed: int, hypotheses: int, count: int, size: int = 7) -> torch.Tensor:
-    """[H, size] int32: hypothesis h's `size` (7: the fundamental matrix, 4: the homography) distinct indices in
-    [0, count), in draw order. Draw j is hash32(seed, h, j) % (count - j), moved past the earlier draws in
-    ascending order (one more for each earlier draw <= it, the smallest first): for count >= 7 the 4-sample is the
-    first four columns of the 7-sample. The pair is not in the key: a pair's result does not depend on its place
-    in a batch."""
-    seed, hypotheses, count, size = int(seed), int(hypotheses), int(count), int(size)
-    if size not in (4, 7):
-        raise ValueError(f"ransac_samples: size is 4 or 7, got {size}")
-    if count < size or hypotheses < 1:
-        raise ValueError(f"ransac_samples: count >= {size} and hypotheses >= 1, got {count} and {hypotheses}")
-    return _samples(seed, hypotheses, count, size)
-
-
-def _samples(seed: int, hypotheses: int, count: int, size: int) -> torch.Tensor:
-    h = np.arange(hypotheses, dtype=np.uint64)
-    out = np.zeros((hypotheses, size), dtype=np.int64)
-    for j in range(size):
-        r = (_hash32(seed, h, j) % np.uint64(count - j)).astype(np.int64)
-        earlier = np.sort(out[:, :j], axis=1)
-        for e in range(j):
-            r = r + (r >= earlier[:, e])
-        out[:, j] = r
-    return torch.from_numpy(out.astype(np.int32))
-
-
-def ransac_samples5(seed: int, hypotheses: int, count: int) -> torch.Tensor:
-    """[H, 5] int32: hypothesis h's five distinct indices in [0, count) for the essential matrix, by
-    ransac_samples' rule (count >= 5): for count >= 7 the first five columns of its 7-sample."""
-    seed, hypotheses, count = int(seed), int(hypotheses), int(count)
-    if count < 5 or hypotheses < 1:
-        raise ValueError(f"ransac_samples5: count >= 5 and hypotheses >= 1, got {count} and {hypotheses}")
-    return _samples(seed, hypotheses, count, 5)
-
-
-# ---- the contract's pieces in float64 ---------------------------------------------------------------------------
-def _np(t) -> np.ndarray:
-    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.float64)
-
-
-def _epi(f: np.ndarray, x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
-    with np.errstate(all="ignore"):
-        h0 = np.concatenate([x0, np.ones((len(x0), 1))], 1)
-        h1 = np.concatenate([x1, np.ones((len(x1), 1))], 1)
-        l1, l0 = h0 @ f.T, h1 @ f
-        d2 = (h1 * l1).sum(1) ** 2
-        return np.maximum(d2 / (l1[:, 0] ** 2 + l1[:, 1] ** 2), d2 / (l0[:, 0] ** 2 + l0[:, 1] ** 2))
-
-
-def epipolar_error(F, x0, x1) -> torch.Tensor:
-    """The error of each correspondence (x0 [n, 2], x1 [n, 2]) under F [3, 3], in squared pixels, float64 [n]:
-    l1 = F x0, l0 = Fᵀ x1, d = x1 · l1, max(d² / (l1x² + l1y²), d² / (l0x² + l0y²)) (OpenCV's for FM_RANSAC).
-    An inlier has error <= threshold²; NaN (a degenerate line, a non-finite coordinate) is none."""
-    return torch.from_numpy(_epi(_np(F).reshape(3, 3), _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)))
-
-
-def _hartley(pts: np.ndarray) -> np.ndarray:
-    """T [3, 3]: centroid to 0, mean distance sqrt 2."""
-    with np.errstate(all="ignore"):
-        c = pts.mean(0)
-        s = np.sqrt(2.0) / np.sqrt(((pts - c) ** 2).sum(1)).mean()
-    return np.array([[s, 0.0, -s * c[0]], [0.0, s, -s * c[1]], [0.0, 0.0, 1.0]])
-
-
-def _apply(t: np.ndarray, pts: np.ndarray) -> np.ndarray:
-    return pts * t[0, 0] + t[:2, 2]
-
-
-def _rows(x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
-    """The rows of x1ᵀ F x0 = 0 for F row-major: (x1 x0, x1 y0, x1, y1 x0, y1 y0, y1, x0, y0, 1)."""
-    one = np.ones(len(x0))
-    return np.stack([x1[:, 0] * x0[:, 0], x1[:, 0] * x0[:, 1], x1[:, 0], x1[:, 1] * x0[:, 0], x1[:, 1] * x0[:, 1],
-                     x1[:, 1], x0[:, 0], x0[:, 1], one], 1)
-
-
-def _unit(f: np.ndarray):
-    """f at unit Frobenius norm with the sign rule (the entry of the largest magnitude positive, the lowest index
-    among equals), or None where it is zero or not finite."""
-    with np.errstate(all="ignore"):
-        n = np.sqrt((f * f).sum())
-        if not np.isfinite(n) or n == 0.0 or not np.isfinite(1.0 / n):
-            return None
-        f = f / n
-    return -f if f.flat[int(np.argmax(np.abs(f)))] < 0 else f
-
-
-def elimination_pivots(a: np.ndarray) -> float:
-    """The smallest pivot magnitude of the Gauss-Jordan elimination with partial (row) pivoting on the n x 9
-    system (7 rows: the 7-point solve, 8: the 4-point), columns 0..n-1 in order: the quantity the contract's
-    epsilon is about. NaN where not finite."""
-    a = np.array(a, dtype=np.float64)
-    low = np.inf
-    rows = len(a)
-    with np.errstate(all="ignore"):
-        for c in range(rows):
-            piv = c + int(np.argmax(np.abs(a[c:, c])))
-            best = abs(a[piv, c])
-            if not best > 0.0:
-                return float(best)
-            low = min(low, best)
-            a[[c, piv]] = a[[piv, c]]
-            a[c] /= a[c, c]
-            for r in range(rows):
-                if r != c:
-                    a[r] -= a[r, c] * a[c]
-    return float(low)
-
-
-class Solve7(NamedTuple):
-    """candidates [n, 3, 3] float64 in pixels (unit norm, sign rule), in ascending root; roots: the cubic's three
-    complex roots (fewer where its leading coefficients vanish); pivot: elimination_pivots of the system."""
-    candidates: np.ndarray
-    roots: np.ndarray
-    pivot: float
-
-
-def _det_poly(g: np.ndarray, d: np.ndarray) -> np.ndarray:
-    """Coefficients (highest first) of det(g + l d) for 3 x 3 g, d: each a sum of determinants of mixed rows."""
-    det = np.linalg.det
-
-    def mixed(mask):
-        return det(np.stack([d[i] if mask >> i & 1 else g[i] for i in range(3)]))
-
-    return np.array([mixed(7), mixed(3) + mixed(5) + mixed(6), mixed(1) + mixed(2) + mixed(4), mixed(0)])
-
-
-def solve7_reference(x0, x1, sample) -> Solve7:
-    """The 7-point solve of the contract in float64: x0, x1 [n, 2] all correspondences of the pair (the Hartley
-    normalisation is over all of them), sample 7 indices. The null space by SVD, brought to the canonical basis
-    f1 = (.., 1, 0), f2 = (.., 0, 1) (which fixes the parameter l whatever found the null space), the roots of
-    det(l f1 + (1 - l) f2) by numpy.roots, the real ones in ascending order de-normalised to unit norm. A pivot
-    below PIVOT_EPS, or anything non-finite, gives no candidate."""
-    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
-    idx = np.asarray(sample, dtype=np.int64).reshape(7)
-    t0, t1 = _hartley(x0), _hartley(x1)
-    a = _rows(_apply(t0, x0[idx]), _apply(t1, x1[idx]))
-    none = Solve7(np.zeros((0, 3, 3)), np.zeros((0,), dtype=complex), float("nan"))
-    if not np.isfinite(a).all():
-        return none
-    pivot = elimination_pivots(a)
-    null = np.linalg.svd(a)[2][7:9]
-    with np.errstate(all="ignore"):
-        try:
-            basis = np.linalg.solve(null[:, 7:9], null)  # rows end (1, 0) and (0, 1)
-        except np.linalg.LinAlgError:
-            return Solve7(none.candidates, none.roots, pivot)
-    if not np.isfinite(basis).all():
-        return Solve7(none.candidates, none.roots, pivot)
-    g, d = basis[1].reshape(3, 3), (basis[0] - basis[1]).reshape(3, 3)
-    roots = np.roots(_det_poly(g, d)).astype(complex)
-    real = sorted(float(r.real) for r in roots if abs(r.imag) <= 1e-12 * max(1.0, abs(r)))
-    cands = []
-    if pivot >= PIVOT_EPS:
-        for lam in real:
-            f = _unit(t1.T @ (g + lam * d) @ t0)
-            if f is not None:
-                cands.append(f)
-    return Solve7(np.array(cands).reshape(-1, 3, 3), roots, pivot)
-
-
-def _refit(x0: np.ndarray, x1: np.ndarray):
-    t0, t1 = _hartley(x0), _hartley(x1)
-    a = _rows(_apply(t0, x0), _apply(t1, x1))
-    if not (np.isfinite(a).all() and np.isfinite(t0).all() and np.isfinite(t1).all()):
-        return None
-    f = np.linalg.eigh(a.T @ a)[1][:, 0].reshape(3, 3)
-    v = np.linalg.svd(f)[2][2]
-    return _unit(t1.T @ (f - np.outer(f @ v, v)) @ t0)
-
-
-def fundamental_refit(x0, x1) -> torch.Tensor:
-    """One refit round of the contract on the given correspondences (x0, x1 [n, 2], n >= 8), float64 [3, 3]:
-    Hartley normalisation over them, the eigenvector of the smallest eigenvalue of the 9 x 9 normal matrix, rank
-    2 by F <- F (I - v vᵀ) with v the smallest right-singular direction, de-normalised to unit norm with the
-    sign rule."""
-    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
-    if len(x0) < MIN_INLIERS or len(x0) != len(x1):
-        raise ValueError(f"fundamental_refit: two sets of n >= {MIN_INLIERS} points, got {len(x0)} and {len(x1)}")
-    f = _refit(x0, x1)
-    if f is None:
-        raise ValueError("fundamental_refit: the correspondences give no finite matrix")
-    return torch.from_numpy(f)
-
-
-# ---- the homography's pieces in float64 -------------------------------------------------------------------------
-def _transfer(h: np.ndarray, x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
-    with np.errstate(all="ignore"):
-        q = np.concatenate([x0, np.ones((len(x0), 1))], 1) @ h.T
-        return (x1[:, 0] - q[:, 0] / q[:, 2]) ** 2 + (x1[:, 1] - q[:, 1] / q[:, 2]) ** 2
-
-
-def transfer_error(H, x0, x1) -> torch.Tensor:
-    """The error of each correspondence (x0 [n, 2], x1 [n, 2]) under H [3, 3] (x1 ~ H x0), in squared pixels,
-    float64 [n]: (X, Y, W) = H x0, (x1 - X/W)² + (y1 - Y/W)² (OpenCV's for findHomography with RANSAC). An inlier
-    has error <= threshold²; a non-finite error (W = 0, a non-finite coordinate, a zero or NaN H) is none."""
-    return torch.from_numpy(_transfer(_np(H).reshape(3, 3), _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)))
-
-
-def _rows_h(x0: np.ndarray, x1: np.ndarray) -> np.ndarray:
-    """The two rows a point of x1 ~ H x0 for H row-major: (-x0, -y0, -1, 0, 0, 0, x1 x0, x1 y0, x1) and
-    (0, 0, 0, -x0, -y0, -1, y1 x0, y1 y0, y1); [2 n, 9], a point's pair adjacent."""
-    one, zero = np.ones(len(x0)), np.zeros(len(x0))
-    ra = np.stack([-x0[:, 0], -x0[:, 1], -one, zero, zero, zero, x1[:, 0] * x0[:, 0], x1[:, 0] * x0[:, 1], x1[:, 0]], 1)
-    rb = np.stack([zero, zero, zero, -x0[:, 0], -x0[:, 1], -one, x1[:, 1] * x0[:, 0], x1[:, 1] * x0[:, 1], x1[:, 1]], 1)
-    return np.stack([ra, rb], 1).reshape(-1, 9)
-
-
-_TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
-
-
-def _orientations(p: np.ndarray) -> np.ndarray:
-    """The 2 x 2 orientation determinant of each of the four triples of four points [4, 2]."""
-    return np.array([(p[j, 0] - p[i, 0]) * (p[k, 1] - p[i, 1]) - (p[j, 1] - p[i, 1]) * (p[k, 0] - p[i, 0])
-                     for i, j, k in _TRIPLES])
-
-
-class Solve4(NamedTuple):
-    """candidates [n, 3, 3] float64 in pixels (unit norm, sign rule), n 0 or 1; pivot: elimination_pivots of the
-    8 x 9 system; orientation: the smallest magnitude of the eight orientation determinants (four triples, two
-    images) in normalised coordinates."""
-    candidates: np.ndarray
-    pivot: float
-    orientation: float
-
-
-def solve4_reference(x0, x1, sample) -> Solve4:
-    """The 4-point solve of the contract in float64: x0, x1 [n, 2] all correspondences of the pair (the Hartley
-    normalisation is over all of them), sample 4 indices. The null vector of the 8 x 9 system by SVD, scaled to
-    the canonical one (h8 = 1 in the normalised frame, which fixes it whatever found the null space),
-    de-normalised by T1⁻¹ Hn T0 to unit norm with the sign rule. A pivot of the elimination below PIVOT_EPS (three
-    collinear points, a repeated index, a true h8 of 0), a sample whose four triples are not oriented alike in
-    both images (the products of the two orientation determinants all positive or all negative: OpenCV's
-    checkSubset), or anything non-finite gives no candidate."""
-    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
-    idx = np.asarray(sample, dtype=np.int64).reshape(4)
-    t0, t1 = _hartley(x0), _hartley(x1)
-    n0, n1 = _apply(t0, x0[idx]), _apply(t1, x1[idx])
-    a = _rows_h(n0, n1)
-    none = np.zeros((0, 3, 3))
-    if not np.isfinite(a).all():
-        return Solve4(none, float("nan"), float("nan"))
-    pivot = elimination_pivots(a)
-    d0, d1 = _orientations(n0), _orientations(n1)
-    orientation = float(min(np.abs(d0).min(), np.abs(d1).min()))
-    prod = np.sign(d0) * np.sign(d1)
-    if not (pivot >= PIVOT_EPS and ((prod > 0).all() or (prod < 0).all())):
-        return Solve4(none, pivot, orientation)
-    v = np.linalg.svd(a)[2][8]
-    with np.errstate(all="ignore"):
-        hn = (v / v[8]).reshape(3, 3)
-        h = _unit(np.linalg.inv(t1) @ hn @ t0) if np.isfinite(hn).all() else None
-    return Solve4(none if h is None else h[None], pivot, orientation)
-
-
-def _refit_h(x0: np.ndarray, x1: np.ndarray):
-    t0, t1 = _hartley(x0), _hartley(x1)
-    a = _rows_h(_apply(t0, x0), _apply(t1, x1))
-    if not (np.isfinite(a).all() and np.isfinite(t0).all() and np.isfinite(t1).all()):
-        return None
-    hn = np.linalg.eigh(a.T @ a)[1][:, 0].reshape(3, 3)
-    with np.errstate(all="ignore"):
-        return _unit(np.linalg.inv(t1) @ hn @ t0)
-
-
-def homography_refit(x0, x1) -> torch.Tensor:
-    """One refit round of the homography's contract on the given correspondences (x0, x1 [n, 2], n >= 4), float64
-    [3, 3]: Hartley normalisation over them, two rows a point, the eigenvector of the smallest eigenvalue of the
-    9 x 9 normal matrix (no rank step), de-normalised by T1⁻¹ Hn T0 to unit norm with the sign rule."""
-    x0, x1 = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2)
-    if len(x0) < MIN_INLIERS_H or len(x0) != len(x1):
-        raise ValueError(f"homography_refit: two sets of n >= {MIN_INLIERS_H} points, got {len(x0)} and {len(x1)}")
-    h = _refit_h(x0, x1)
-    if h is None:
-        raise ValueError("homography_refit: the correspondences give no finite matrix")
-    return torch.from_numpy(h)
-
-
-# ---- the essential matrix's pieces in float64 -------------------------------------------------------------------
-def _intrinsics_ok(k: np.ndarray) -> bool:
-    return bool(np.isfinite(k).all() and (k[:, :2] > 0).all())
-
-
-def camera_coordinates(pts, intrinsics) -> np.ndarray:
-    """pts [n, 2] in pixels under (fx, fy, cx, cy) -> ((x - cx) / fx, (y - cy) / fy), float64 [n, 2]."""
-    p, k = _np(pts).reshape(-1, 2), _np(intrinsics).reshape(4)
-    with np.errstate(all="ignore"):
-        return (p - k[2:4]) / k[0:2]
-
-
-def _kinv(k: np.ndarray) -> np.ndarray:
-    return np.array([[1.0 / k[0], 0.0, -k[2] / k[0]], [0.0, 1.0 / k[1], -k[3] / k[1]], [0.0, 0.0, 1.0]])
-
-
-def essential_to_fundamental(E, intrinsics) -> torch.Tensor:
-    """F = K1⁻ᵀ E K0⁻¹ at unit Frobenius norm with the sign rule, float64 [3, 3]: the matrix a candidate E (camera
-    coordinates, intrinsics [2, 4] = (fx, fy, cx, cy) of image 0 then image 1) is scored with in pixels."""
-    k = _np(intrinsics).reshape(2, 4)
-    f = _unit(_kinv(k[1]).T @ _np(E).reshape(3, 3) @ _kinv(k[0]))
-    if f is None:
-        raise ValueError("essential_to_fundamental: the matrix is zero or not finite")
-    return torch.from_numpy(f)
-
-
-def _f_of_e(e: np.ndarray, k: np.ndarray):
-    with np.errstate(all="ignore"):
-        return _unit(_kinv(k[1]).T @ e @ _kinv(k[0]))
-
-
-def _pmul(a: np.ndarray, b: np.ndarray) -> np.ndarray:
-    """The product of two polynomials in (x, y, z), each an array indexed by the three exponents."""
-    out = np.zeros(tuple(i + j - 1 for i, j in zip(a.shape, b.shape)))
-    for idx in np.ndindex(*a.shape):
-        if a[idx] != 0.0:
-            out[idx[0]:idx[0] + b.shape[0], idx[1]:idx[1] + b.shape[1], idx[2]:idx[2] + b.shape[2]] += a[idx] * b
-    return out
-
-
-def essential_constraints(basis: np.ndarray):
-    """The ten cubic constraints on E = x basis[0] + y basis[1] + z basis[2] + basis[3] (basis [4, 3, 3]): det E = 0
-    and the nine entries of 2 E Eᵀ E - tr(E Eᵀ) E = 0, each a polynomial [4, 4, 4] indexed by the exponents of
-    (x, y, z), by generic polynomial products."""
-    e = [[None] * 3 for _ in range(3)]
-    for i in range(3):
-        for j in range(3):
-            p = np.zeros((2, 2, 2))
-            p[1, 0, 0], p[0, 1, 0], p[0, 0, 1], p[0, 0, 0] = basis[0, i, j], basis[1, i, j], basis[2, i, j], basis[3, i, j]
-            e[i][j] = p
-    eet = [[sum(_pmul(e[i][k], e[j][k]) for k in range(3)) for j in range(3)] for i in range(3)]
-    tr = eet[0][0] + eet[1][1] + eet[2][2]
-    out = [_pmul(e[0][0], _pmul(e[1][1], e[2][2]) - _pmul(e[1][2], e[2][1]))
-           - _pmul(e[0][1], _pmul(e[1][0], e[2][2]) - _pmul(e[1][2], e[2][0]))
-           + _pmul(e[0][2], _pmul(e[1][0], e[2][1]) - _pmul(e[1][1], e[2][0]))]
-    for i in range(3):
-        for j in range(3):
-            out.append(sum(_pmul(2.0 * eet[i][k] - (tr if i == k else 0.0), e[k][j]) for k in range(3)))
-    return out
-
-
-def essential_residuals(E) -> Tuple[float, float]:
-    """(|det E|, the largest magnitude among the entries of 2 E Eᵀ E - tr(E Eᵀ) E) of a 3 x 3 matrix."""
-    e = _np(E).reshape(3, 3)
-    return float(abs(np.linalg.det(e))), float(np.abs(2.0 * e @ e.T @ e - np.trace(e @ e.T) * e).max())
-
-
-_XY_MONOMIALS = ((3, 0), (2, 1), (1, 2), (0, 3), (2, 0), (1, 1), (0, 2), (1, 0), (0, 1), (0, 0))
-
-
-class Solve5(NamedTuple):
-    """candidates [n, 3, 3] float64 in camera coordinates (canonical: unit norm, sign rule), ascending in their
-    entry [0, 0]; eigenvalues: the finite eigenvalues of the pencil, complex (the hidden variable at every
-    solution, real or not); pivot: elimination_pivots of the 5 x 9 system; ratio: its smallest singular value over
-    its largest."""
-    candidates: np.ndarray
-    eigenvalues: np.ndarray
-    pivot: float
-    ratio: float
-
-
-def solve5_reference(q0, q1, sample) -> Solve5:
-    """The five-point solve of the contract in float64: q0, q1 [n, 2] the pair's correspondences in camera
-    coordinates, sample 5 indices. The 4-dimensional null space by SVD; the ten cubic constraints by generic
-    polynomial products (essential_constraints); z hidden: C(z) m = 0 for the ten monomials m of (x, y) up to degree
-    3, a cubic matrix pencil whose real finite eigenvalues (scipy.linalg.eig on its linearisation) are the
-    solutions' z, with (x, y) read off the eigenvector. Deliberately not the kernel's elimination and degree-10
-    polynomial. A pivot of the 5 x 9 elimination below PIVOT_EPS, or anything non-finite, gives no candidate."""
-    from scipy.linalg import eig
-
-    q0, q1 = _np(q0).reshape(-1, 2), _np(q1).reshape(-1, 2)
-    idx = np.asarray(sample, dtype=np.int64).reshape(5)
-    a = _rows(q0[idx], q1[idx])
-    none = np.zeros((0, 3, 3))
-    if not np.isfinite(a).all():
-        return Solve5(none, np.zeros((0,), dtype=complex), float("nan"), float("nan"))
-    pivot = elimination_pivots(a)
-    _, sv, vt = np.linalg.svd(a)
-    ratio = float(sv[4] / sv[0]) if sv[0] > 0 else 0.0
-    basis = vt[5:9].reshape(4, 3, 3)
-    cons = essential_constraints(basis)
-    c = np.zeros((4, 10, 10))
-    for r, poly in enumerate(cons):
-        for m, (ex, ey) in enumerate(_XY_MONOMIALS):
-            for d in range(4 - ex - ey):
-                c[d, r, m] = poly[ex, ey, d]
-    eye, zero = np.eye(10), np.zeros((10, 10))
-    lhs = np.block([[zero, eye, zero], [zero, zero, eye], [-c[0], -c[1], -c[2]]])
-    rhs = np.block([[eye, zero, zero], [zero, eye, zero], [zero, zero, c[3]]])
-    with np.errstate(all="ignore"):
-        (alpha, beta), vec = eig(lhs, rhs, homogeneous_eigvals=True)
-        finite = np.abs(beta) > 1e-9 * np.abs(alpha)
-        values = (alpha[finite] / beta[finite]).astype(complex)
-        vec = vec[:, finite]
-    cands = []
-    if pivot >= PIVOT_EPS:
-        for z, v in zip(values, vec.T):
-            if abs(z.imag) > 1e-9 * max(1.0, abs(z)):
-                continue
-            with np.errstate(all="ignore"):
-                m = v[:10] / v[9]
-                x, y = float(m[7].real), float(m[8].real)
-                e = _unit(x * basis[0] + y * basis[1] + float(z.real) * basis[2] + basis[3])
-            if e is not None:
-                cands.append(e)
-    cands.sort(key=lambda e: e[0, 0])
-    return Solve5(np.array(cands).reshape(-1, 3, 3), values, pivot, ratio)
-
-
-def _project_essential(e: np.ndarray) -> np.ndarray:
-    u, _, vt = np.linalg.svd(e)
-    return u @ np.diag([1.0, 1.0, 0.0]) @ vt
-
-
-def _refit_e(q0: np.ndarray, q1: np.ndarray):
-    t0, t1 = _hartley(q0), _hartley(q1)
-    a = _rows(_apply(t0, q0), _apply(t1, q1))
-    if not (np.isfinite(a).all() and np.isfinite(t0).all() and np.isfinite(t1).all()):
-        return None
-    e = t1.T @ np.linalg.eigh(a.T @ a)[1][:, 0].reshape(3, 3) @ t0
-    if not np.isfinite(e).all():
-        return None
-    return _unit(_project_essential(e))
-
-
-def essential_refit(q0, q1) -> torch.Tensor:
-    """One refit round of the essential matrix's contract on the given correspondences in camera coordinates (q0,
-    q1 [n, 2], n >= 8), float64 [3, 3]: Hartley normalisation over them, the eigenvector of the smallest eigenvalue
-    of the 9 x 9 normal matrix, de-normalised, then the nearest essential matrix (singular values (1, 1, 0)),
-    canonical (unit norm, sign rule)."""
-    q0, q1 = _np(q0).reshape(-1, 2), _np(q1).reshape(-1, 2)
-    if len(q0) < MIN_INLIERS or len(q0) != len(q1):
-        raise ValueError(f"essential_refit: two sets of n >= {MIN_INLIERS} points, got {len(q0)} and {len(q1)}")
-    e = _refit_e(q0, q1)
-    if e is None:
-        raise ValueError("essential_refit: the correspondences give no finite matrix")
-    return torch.from_numpy(e)
-
-
-def _depths(r: np.ndarray, t: np.ndarray, q0: np.ndarray, q1: np.ndarray):
-    """The depths (d0, d1) of each correspondence's midpoint triangulation under X1 = R X0 + t: the least-squares
-    solution of d0 R a - d1 b = -t for the rays a = (q0, 1), b = (q1, 1)."""
-    a = np.concatenate([q0, np.ones((len(q0), 1))], 1) @ r.T
-    b = np.concatenate([q1, np.ones((len(q1), 1))], 1)
-    with np.errstate(all="ignore"):
-        aa, bb, ab, at, bt = (a * a).sum(1), (b * b).sum(1), (a * b).sum(1), a @ t, b @ t
-        det = aa * bb - ab * ab
-        return (ab * bt - bb * at) / det, (aa * bt - ab * at) / det
-
-
-def pose_candidates(E):
-    """The four (R, t) of an essential matrix: E = U diag(1, 1, 0) Vᵀ with det U and det V positive, W the quarter
-    turn about z: (U W Vᵀ, +u3), (U W Vᵀ, -u3), (U Wᵀ Vᵀ, +u3), (U Wᵀ Vᵀ, -u3)."""
-    u, _, vt = np.linalg.svd(_np(E).reshape(3, 3))
-    if np.linalg.det(u) < 0:
-        u[:, 2] = -u[:, 2]
-    if np.linalg.det(vt) < 0:
-        vt[2] = -vt[2]
-    w = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
-    ra, rb, u3 = u @ w @ vt, u @ w.T @ vt, u[:, 2].copy()
-    return [(ra, u3), (ra, -u3), (rb, u3), (rb, -u3)]
-
-
-def pose_from_essential_reference(E, q0, q1):
-    """(R [3, 3], t [3], num_front, the four counts) in float64: of pose_candidates(E), the one under which the
-    most correspondences (q0, q1 [n, 2], camera coordinates) triangulate (_depths: the midpoint method) to a
-    positive depth in both cameras; the lowest index among equals. X1 = R X0 + t, |t| = 1, det R = +1."""
-    q0, q1 = _np(q0).reshape(-1, 2), _np(q1).reshape(-1, 2)
-    cands = pose_candidates(E)
-    counts = []
-    for r, t in cands:
-        d0, d1 = _depths(r, t, q0, q1)
-        counts.append(int(((d0 > 0) & (d1 > 0)).sum()))
-    i = int(np.argmax(counts))
-    return torch.from_numpy(cands[i][0].copy()), torch.from_numpy(cands[i][1].copy()), counts[i], counts
-
-
-# ---- the pose polish and the triangulation in float64 --------------------------------------------------------------
-def _skew(t: np.ndarray) -> np.ndarray:
-    return np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
-
-
-def _sampson(e: np.ndarray, x0: np.ndarray, x1: np.ndarray, k: np.ndarray) -> np.ndarray:
-    with np.errstate(all="ignore"):
-        q0 = np.concatenate([(x0 - k[0, 2:4]) / k[0, 0:2], np.ones((len(x0), 1))], 1)
-        q1 = np.concatenate([(x1 - k[1, 2:4]) / k[1, 0:2], np.ones((len(x1), 1))], 1)
-        l1, l0 = q0 @ e.T, q1 @ e
-        d = (q1 * l1).sum(1)
-        n2 = (l1[:, 0] / k[1, 0]) ** 2 + (l1[:, 1] / k[1, 1]) ** 2 + (l0[:, 0] / k[0, 0]) ** 2 + (l0[:, 1] / k[0, 1]) ** 2
-        return d / np.sqrt(n2)
-
-
-def sampson_error(E, x0, x1, intrinsics) -> torch.Tensor:
-    """The signed Sampson distance in pixels of each correspondence (x0, x1 [n, 2] in pixels) under E [3, 3] (camera
-    coordinates, any scale; intrinsics [2, 4]), float64 [n]: with q the camera coordinates, (a, b, .) = E q0,
-    (a', b', .) = Eᵀ q1 and d = q1ᵀ E q0, d / sqrt((a / fx1)² + (b / fy1)² + (a' / fx0)² + (b' / fy0)²): the first-order
-    distance to the epipolar constraint in the pixels of both images. The polish's cost is the sum of its squares."""
-    return torch.from_numpy(_sampson(_np(E).reshape(3, 3), _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2),
-                                     _np(intrinsics).reshape(2, 4)))
-
-
-def _axis_order(t: np.ndarray):
-    i = int(np.argmin(np.abs(t)))  # (the lowest index among equals)
-    return i, (i + 1) % 3, (i + 2) % 3
-
-
-def polish_pose_reference(R, t, x0, x1, intrinsics, mask, threshold: float = 3.0) -> PolishResult:
-    """PosePolish.refine's contract for one valid pair in float64, run to convergence: R [3, 3], t [3], the pair's
-    correspondences x0, x1 [n, 2] in pixels, intrinsics [2, 4], mask [n] (its non-zeros: the given inliers) ->
-    PolishResult without the batch dimension (E, R, t, cost float64). The fixed set is the given inliers with a finite
-    sampson_error under the given pose; with fewer than 5 of them, bad intrinsics, a non-finite R or t or a zero t
-    the pair is passed through. Else the sum of squared sampson_error over the fixed set is minimised by
-    scipy.optimize.least_squares(method="lm") at its tolerance floor over a global rotation vector and the two
-    angles of t about the axis of its smallest component, with a numeric Jacobian (not the kernel's route: a local
-    rotation, a tangent step of t, an analytic Jacobian and a fixed number of rounds). The mask is then recomputed
-    over all n correspondences as essential_reference scores a candidate; with at least as many inliers as given the
-    polished pose, its mask and its counts are returned (kept = 1), else the given ones (kept = 0, both costs the
-    entering one, E = canonical([t]x R) of the given pose)."""
-    from scipy.optimize import least_squares
-    from scipy.spatial.transform import Rotation
-
-    r, t = _np(R).reshape(3, 3), _np(t).reshape(3)
-    x0, x1, kk = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2), _np(intrinsics).reshape(2, 4)
-    given = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask).reshape(-1) != 0
-    n_in, thr2 = int(given.sum()), float(threshold) ** 2
-    with np.errstate(all="ignore"):
-        e_given = _unit(_skew(t) @ r) if np.isfinite(r).all() and np.isfinite(t).all() else None
-        length = float(np.linalg.norm(t))
-    good = _intrinsics_ok(kk)
-
-    def front_of(rr, tt, rows):
-        if not good:
-            return 0
-        d0, d1 = _depths(rr, tt, camera_coordinates(x0[rows], kk[0]), camera_coordinates(x1[rows], kk[1]))
-        return int(((d0 > 0) & (d1 > 0)).sum())
-
-    def result(e, rr, tt, rows, costs, kept):
-        return PolishResult(torch.from_numpy(np.zeros((3, 3)) if e is None else e.copy()), torch.from_numpy(rr.copy()),
-                            torch.from_numpy(tt.copy()), torch.from_numpy(rows.astype(np.uint8)),
-                            torch.tensor(int(rows.sum()), dtype=torch.int32), torch.tensor(front_of(rr, tt, rows), dtype=torch.int32),
-                            torch.tensor(costs, dtype=torch.float64), torch.tensor(kept, dtype=torch.int32))
-
-    if not (good and e_given is not None and np.isfinite(length) and length > 0.0):
-        return result(e_given, r, t, given, [0.0, 0.0], 0)
-    t0 = t / length
-    rows = np.nonzero(given)[0]
-    rows = rows[np.isfinite(_sampson(_skew(t0) @ r, x0[rows], x1[rows], kk))]
-    rot0 = Rotation.from_matrix(r)  # (the nearest rotation: a pose rounded to fp32 is 1e-7 off)
-    cost0 = float((_sampson(_skew(t0) @ rot0.as_matrix(), x0[rows], x1[rows], kk) ** 2).sum())
-    if len(rows) < MIN_POLISH_ROWS or not np.isfinite(cost0):
-        return result(e_given, r, t, given, [cost0, cost0], 0)
-    i, j, k = _axis_order(t0)
-
-    def pose(p):
-        tt = np.zeros(3)
-        tt[i], tt[j], tt[k] = np.cos(p[3]), np.sin(p[3]) * np.cos(p[4]), np.sin(p[3]) * np.sin(p[4])
-        return Rotation.from_rotvec(p[:3]).as_matrix(), tt
-
-    def residuals(p):
-        rr, tt = pose(p)
-        return _sampson(_skew(tt) @ rr, x0[rows], x1[rows], kk)
-
-    p0 = np.concatenate([rot0.as_rotvec(), [np.arccos(np.clip(t0[i], -1.0, 1.0)), np.arctan2(t0[k], t0[j])]])
-    sol = least_squares(residuals, p0, method="lm", xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=4000)
-    cost1 = float((sol.fun ** 2).sum())
-    r1, t1 = pose(sol.x) if np.isfinite(cost1) and cost1 < cost0 else pose(p0)
-    cost1 = cost1 if np.isfinite(cost1) and cost1 < cost0 else cost0
-    e1 = _unit(_skew(t1) @ r1)
-    f1 = None if e1 is None else _f_of_e(e1, kk)
-    again = np.zeros(len(x0), dtype=bool) if f1 is None else _epi(f1, x0, x1) <= thr2
-    if f1 is None or int(again.sum()) < n_in:
-        return result(e_given, r, t, given, [cost0, cost0], 0)
-    return result(e1, r1, t1, again, [cost0, cost1], 1)
-
-
-def polish_reference(pose, matches, counts, kpts0, kpts1, intrinsics, threshold: float = 3.0) -> PolishResult:
-    """PosePolish(threshold).refine for a batch in float64, run to convergence: polish_pose_reference on every pair
-    with pose.valid != 0 (over its gathered correspondences and pose.inliers); a pair with valid == 0 returns R, t
-    and the mask as given and zeros elsewhere. E, R, t, cost float64."""
-    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
-    out = PolishResult(torch.zeros((pr, 3, 3), dtype=torch.float64), _as64(pose.R).clone(), _as64(pose.t).clone(),
-                       torch.zeros((pr, kmax), dtype=torch.uint8), torch.zeros((pr,), dtype=torch.int32),
-                       torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr, 2), dtype=torch.float64),
-                       torch.zeros((pr,), dtype=torch.int32))
-    for p in range(pr):
-        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
-        n = len(x0)
-        given = pose.inliers[p, :n].cpu()
-        if not int(pose.valid[p]):
-            out.inliers[p, :n] = (given != 0).to(torch.uint8)
-            continue
-        one = polish_pose_reference(pose.R[p], pose.t[p], x0, x1, intrinsics[p], given, threshold)
-        out.E[p], out.R[p], out.t[p], out.cost[p] = one.E, one.R, one.t, one.cost
-        out.inliers[p, :n] = one.inliers
-        out.num_inliers[p], out.num_front[p], out.kept[p] = one.num_inliers, one.num_front, one.kept
-    return out
-
-
-def _as64(t) -> torch.Tensor:
-    return torch.from_numpy(_np(t))
-
-
-def triangulate_reference(R, t, x0, x1, intrinsics, mask):
-    """triangulate's contract for one pair in float64: (points [n, 3], ok [n] uint8). For a row with mask != 0 the
-    midpoint method of pose_from_essential_reference: the depths (d0, d1) of _depths, and X = (d0 a + Rᵀ (d1 b - t)) / 2
-    in camera 0's frame for the rays a = (q0, 1), b = (q1, 1), at the scale |t| = 1; ok where both depths are
-    positive and X is finite. Every other entry is zeros."""
-    r, t = _np(R).reshape(3, 3), _np(t).reshape(3)
-    x0, x1, kk = _np(x0).reshape(-1, 2), _np(x1).reshape(-1, 2), _np(intrinsics).reshape(2, 4)
-    rows = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask).reshape(-1) != 0
-    pts, ok = np.zeros((len(x0), 3)), np.zeros(len(x0), dtype=bool)
-    if _intrinsics_ok(kk):
-        q0, q1 = camera_coordinates(x0, kk[0]), camera_coordinates(x1, kk[1])
-        d0, d1 = _depths(r, t, q0, q1)
-        with np.errstate(all="ignore"):
-            a = np.concatenate([q0, np.ones((len(q0), 1))], 1)
-            b = np.concatenate([q1, np.ones((len(q1), 1))], 1)
-            x = 0.5 * (d0[:, None] * a + (d1[:, None] * b - t) @ r)
-            ok = rows & (d0 > 0) & (d1 > 0) & np.isfinite(x).all(1)
-        pts[ok] = x[ok]
-    return torch.from_numpy(pts), torch.from_numpy(ok.astype(np.uint8))
-
-
-def rotation_angle_deg(ra, rb) -> float:
-    """The angle of the rotation Raᵀ Rb in degrees: |Ra - Rb| = 2 sqrt 2 sin(angle / 2) in the Frobenius norm (exact
-    for small angles, where the arc cosine of the trace is not)."""
-    d = np.linalg.norm(_np(ra).reshape(3, 3) - _np(rb).reshape(3, 3))
-    return float(np.degrees(2.0 * np.arcsin(min(1.0, d / (2.0 * np.sqrt(2.0))))))
-
-
-def direction_angle_deg(ta, tb) -> float:
-    """The angle between two directions in degrees: |a - b| = 2 sin(angle / 2) at unit length."""
-    a, b = _np(ta).reshape(3), _np(tb).reshape(3)
-    return float(np.degrees(2.0 * np.arcsin(min(1.0, np.linalg.norm(a / np.linalg.norm(a) - b / np.linalg.norm(b)) / 2.0))))
-
-
-def _check_params(threshold, hypotheses, refits) -> None:
-    if not 0.0 < float(threshold) <= 1e6:
-        raise ValueError(f"threshold must be in (0, 1e6] pixels, got {threshold}")
-    if not 1 <= int(hypotheses) <= MAX_HYPOTHESES:
-        raise ValueError(f"hypotheses must be in [1, {MAX_HYPOTHESES}], got {hypotheses}")
-    if not 0 <= int(refits) <= MAX_REFITS:
-        raise ValueError(f"refits must be in [0, {MAX_REFITS}], got {refits}")
-
-
-def gather_correspondences(matches, count: int, kpts0, kpts1) -> Tuple[np.ndarray, np.ndarray]:
-    """One pair's correspondences as the kernels read them: matches [Kmax, 2], kpts0 [K0, 2], kpts1 [K1, 2] ->
-    (x0, x1) float64 [count, 2], the count clamped into [0, Kmax] and the indices into range."""
-    m = np.asarray(matches.cpu() if isinstance(matches, torch.Tensor) else matches).astype(np.int64)
-    k0, k1 = _np(kpts0), _np(kpts1)
-    n = min(max(int(count), 0), len(m))
-    return k0[np.clip(m[:n, 0], 0, len(k0) - 1)], k1[np.clip(m[:n, 1], 0, len(k1) - 1)]
-
-
-def ransac_reference(matches, counts, kpts0, kpts1, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2,
-                     seed: int = 888) -> GeometryResult:
-    """FundamentalRansac(threshold, hypotheses, refits, seed).verify in float64 on the CPU: matches [P, Kmax, 2],
-    counts [P], kpts0 [P, K0, 2], kpts1 [P, K1, 2] -> GeometryResult (F float64). The steps are the header's:
-    gather and normalise, ransac_samples, solve7_reference, every candidate scored in pixels (the winner: the
-    highest count, then the lowest hypothesis, then the lowest root), `refits` rounds of fundamental_refit's
-    arithmetic over the current inliers (a round with fewer than 8 keeps F and mask)."""
-    _check_params(threshold, hypotheses, refits)
-    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
-    out = GeometryResult(torch.zeros((pr, 3, 3), dtype=torch.float64), torch.zeros((pr, kmax), dtype=torch.uint8),
-                         torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr,), dtype=torch.int32),
-                         torch.full((pr,), -1, dtype=torch.int32))
-    thr2 = float(threshold) ** 2
-    for p in range(pr):
-        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
-        n = len(x0)
-        if n < MIN_INLIERS:
-            continue
-        best_n, best_h, best_f = -1, -1, None
-        for h, sample in enumerate(ransac_samples(seed, hypotheses, n).numpy()):
-            for f in solve7_reference(x0, x1, sample).candidates:
-                got = int((_epi(f, x0, x1) <= thr2).sum())
-                if got > best_n:
-                    best_n, best_h, best_f = got, h, f
-        if best_n < MIN_INLIERS:
-            continue
-        f, mask = best_f, _epi(best_f, x0, x1) <= thr2
-        for _ in range(int(refits)):
-            if int(mask.sum()) < MIN_INLIERS:
-                break
-            again = _refit(x0[mask], x1[mask])
-            if again is None:
-                break
-            f, mask = again, _epi(again, x0, x1) <= thr2
-        out.F[p] = torch.from_numpy(f)
-        out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
-        out.num_inliers[p], out.valid[p], out.best[p] = int(mask.sum()), 1, best_h
-    return out
-
-
-def homography_reference(matches, counts, kpts0, kpts1, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2,
-                         seed: int = 888) -> HomographyResult:
-    """HomographyRansac(threshold, hypotheses, refits, seed).verify in float64 on the CPU: matches [P, Kmax, 2],
-    counts [P], kpts0 [P, K0, 2], kpts1 [P, K1, 2] -> HomographyResult (H float64). The steps are the header's:
-    gather and normalise, ransac_samples(size=4), solve4_reference, the candidate scored in pixels (the winner: the
-    highest count, then the lowest hypothesis), `refits` rounds of homography_refit's arithmetic over the current
-    inliers (a round with fewer than 4 keeps H and mask). No Levenberg-Marquardt polish."""
-    _check_params(threshold, hypotheses, refits)
-    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
-    out = HomographyResult(torch.zeros((pr, 3, 3), dtype=torch.float64), torch.zeros((pr, kmax), dtype=torch.uint8),
-                           torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr,), dtype=torch.int32),
-                           torch.full((pr,), -1, dtype=torch.int32))
-    thr2 = float(threshold) ** 2
-    for p in range(pr):
-        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
-        n = len(x0)
-        if n < MIN_INLIERS_H:
-            continue
-        best_n, best_h, best_m = -1, -1, None
-        for h, sample in enumerate(ransac_samples(seed, hypotheses, n, size=4).numpy()):
-            for m in solve4_reference(x0, x1, sample).candidates:
-                got = int((_transfer(m, x0, x1) <= thr2).sum())
-                if got > best_n:
-                    best_n, best_h, best_m = got, h, m
-        if best_n < MIN_INLIERS_H:
-            continue
-        m, mask = best_m, _transfer(best_m, x0, x1) <= thr2
-        for _ in range(int(refits)):
-            if int(mask.sum()) < MIN_INLIERS_H:
-                break
-            again = _refit_h(x0[mask], x1[mask])
-            if again is None:
-                break
-            m, mask = again, _transfer(again, x0, x1) <= thr2
-        out.H[p] = torch.from_numpy(m)
-        out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
-        out.num_inliers[p], out.valid[p], out.best[p] = int(mask.sum()), 1, best_h
-    return out
-
-
-def essential_reference(matches, counts, kpts0, kpts1, intrinsics, threshold: float = 3.0, hypotheses: int = 512,
-                        refits: int = 2, seed: int = 888) -> PoseResult:
-    """EssentialRansac(threshold, hypotheses, refits, seed).verify in float64 on the CPU: matches [P, Kmax, 2],
-    counts [P], kpts0 [P, K0, 2], kpts1 [P, K1, 2], intrinsics [P, 2, 4] -> PoseResult (E, R, t float64). The steps
-    are the header's: gather, camera coordinates, ransac_samples5, solve5_reference, every candidate scored in
-    pixels as essential_to_fundamental's F (the winner: the highest count, then the lowest hypothesis, then the
-    candidate whose canonical E has the smallest entry [0, 0]), `refits` rounds of essential_refit's arithmetic over
-    the current inliers (a round with fewer than 8 stops; a round whose E counts fewer inliers than the current one
-    is dropped and the rounds stop: on a planar scene the 8-point fit is degenerate and the five-point winner
-    stays), the pose by pose_from_essential_reference over the inliers. A pair with fewer than 5 correspondences, or with an intrinsic
-    that is not finite or a focal length <= 0, is invalid."""
-    _check_params(threshold, hypotheses, refits)
-    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
-    out = PoseResult(torch.zeros((pr, 3, 3), dtype=torch.float64), torch.zeros((pr, 3, 3), dtype=torch.float64),
-                     torch.zeros((pr, 3), dtype=torch.float64), torch.zeros((pr, kmax), dtype=torch.uint8),
-                     torch.zeros((pr,), dtype=torch.int32), torch.zeros((pr,), dtype=torch.int32),
-                     torch.zeros((pr,), dtype=torch.int32), torch.full((pr,), -1, dtype=torch.int32))
-    thr2 = float(threshold) ** 2
-    for p in range(pr):
-        x0, x1 = gather_correspondences(matches[p], int(counts[p]), kpts0[p], kpts1[p])
-        kk = _np(intrinsics[p]).reshape(2, 4)
-        n = len(x0)
-        if n < MIN_INLIERS_E or not _intrinsics_ok(kk):
-            continue
-        q0, q1 = camera_coordinates(x0, kk[0]), camera_coordinates(x1, kk[1])
-
-        def mask_of(e):
-            f = _f_of_e(e, kk)
-            return np.zeros(n, dtype=bool) if f is None else _epi(f, x0, x1) <= thr2
-
-        best_n, best_h, best_e = -1, -1, None
-        for h, sample in enumerate(ransac_samples5(seed, hypotheses, n).numpy()):
-            for e in solve5_reference(q0, q1, sample).candidates:
-                got = int(mask_of(e).sum())
-                if got > best_n:
-                    best_n, best_h, best_e = got, h, e
-        if best_n < MIN_INLIERS_E:
-            continue
-        e, mask = best_e, mask_of(best_e)
-        for _ in range(int(refits)):
-            if int(mask.sum()) < MIN_INLIERS:
-                break
-            again = _refit_e(q0[mask], q1[mask])
-            if again is None:
-                break
-            mask_again = mask_of(again)
-            if int(mask_again.sum()) < int(mask.sum()):
-                break
-            e, mask = again, mask_again
-        r, t, front, _ = pose_from_essential_reference(e, q0[mask], q1[mask])
-        out.E[p], out.R[p], out.t[p] = torch.from_numpy(e), r, t
-        out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
-        out.num_inliers[p], out.num_front[p], out.valid[p], out.best[p] = int(mask.sum()), front, 1, best_h
-    return out
-
-
-# ---- synthetic pairs ------------------------------------------------------------------------------------------------
-def _scene_camera(cam: np.ndarray, h: int, w: int):
-    """The scenes' intrinsics (focal length w, the centre of the image) and the second camera's rotation from the
-    first draws of the stream."""
-    kk = np.array([[w, 0.0, w / 2.0], [0.0, w, h / 2.0], [0.0, 0.0, 1.0]])
-    ang = (cam[:3] - 0.5) * np.array([0.12, 0.5, 0.12]) + np.array([0.0, 0.15, 0.0])  # radians about x, y, z
-    cx, cy, cz = np.cos(ang)
-    sx, sy, sz = np.sin(ang)
-    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
-    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
-    return kk, rz @ ry @ rx
-
-
-def _scene_shift(cam: np.ndarray) -> np.ndarray:
-    """The second camera's translation (X1 = R X0 + t): sideways."""
-    return np.array([-1.0 - cam[3], 0.3 * (cam[4] - 0.5), 0.3 * (cam[5] - 0.5)])
-
-
-def two_view_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
-    """Two pinhole views (size = (h, w), focal length w, the second camera turned and moved sideways) of random
-    3D points, from synth.uniform24: (kpts0 [k, 2] fp32, kpts1 [k, 2] fp32, gt_mask [k] bool, F_true [3, 3]
-    float64 at unit norm). round(k outlier_fraction) rows are outliers: both ends uniform in the images, redrawn
-    until their error under F_true exceeds 12 px; the inliers are projections moved by at most noise_px in each
-    image; the rows are shuffled."""
-    h, w = int(size[0]), int(size[1])
-    n_out = int(round(k * outlier_fraction))
-    n_in = k - n_out
-    if k < 1 or n_in < 0 or n_out < 0 or noise_px < 0:
-        raise ValueError(f"two_view_scene: bad k / outlier_fraction / noise_px {k}, {outlier_fraction}, {noise_px}")
-    pool = 16 * k + 64
-    u = synth.uniform24(int(seed), 16 + 9 * pool).astype(np.float64)
-    cam, u = u[:16], u[16:].reshape(9, pool)
-    kk, rot = _scene_camera(cam, h, w)
-    t = _scene_shift(cam)
-    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
-    kinv = np.linalg.inv(kk)
-    f_true = kinv.T @ tx @ rot @ kinv
-    f_true = _unit(f_true)
-    # inliers: a pixel of image 0 at a depth, seen in image 1
-    p0 = np.stack([u[0] * (w - 1), u[1] * (h - 1)], 1)
-    depth = 4.0 + 8.0 * u[2]
-    xyz = (np.concatenate([p0, np.ones((pool, 1))], 1) @ kinv.T) * depth[:, None]
-    q = (xyz @ rot.T + t) @ kk.T
-    p1 = q[:, :2] / q[:, 2:3]
-    ok = (q[:, 2] > 0.5) & (p1[:, 0] >= 0) & (p1[:, 0] <= w - 1) & (p1[:, 1] >= 0) & (p1[:, 1] <= h - 1)
-    keep = np.nonzero(ok)[0][:n_in]
-    # outliers
-    o0 = np.stack([u[3] * (w - 1), u[4] * (h - 1)], 1)
-    o1 = np.stack([u[5] * (w - 1), u[6] * (h - 1)], 1)
-    far = np.nonzero(np.sqrt(_epi(f_true, o0, o1)) > 12.0)[0][:n_out]
-    if len(keep) < n_in or len(far) < n_out:
-        raise ValueError("two_view_scene: the pool ran out (a seed whose second view sees too little)")
-    a = noise_px / np.sqrt(2.0)
-    noise = (u[7:9, :2 * n_in].reshape(2, 2, n_in) * 2.0 - 1.0) * a
-    k0 = np.concatenate([p0[keep] + noise[0].T, o0[far]])
-    k1 = np.concatenate([p1[keep] + noise[1].T, o1[far]])
-    gt = np.concatenate([np.ones(n_in, dtype=bool), np.zeros(n_out, dtype=bool)])
-    order = np.argsort(synth.uniform24(int(seed) + 0x5EED, k), kind="stable")
-    return (torch.from_numpy(k0[order].astype(np.float32)), torch.from_numpy(k1[order].astype(np.float32)),
-            torch.from_numpy(gt[order]), torch.from_numpy(f_true))
-
-
-def planar_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640),
-                 rotation_only: bool = False):
-    """two_view_scene's twin for the homography: two pinhole views (size = (h, w), focal length w) of points on one
-    random plane (a depth of 5 to 9 at the image centre, tilted by up to 0.3 in x and in y), the second camera
-    turned and moved sideways as two_view_scene's is; rotation_only: the second camera only turned, the points at
-    any depth. From synth.uniform24: (kpts0 [k, 2] fp32, kpts1 [k, 2] fp32, gt_mask [k] bool, H_true [3, 3] float64
-    at unit norm, x1 ~ H_true x0). round(k outlier_fraction) rows are outliers: both ends uniform in the images,
-    redrawn until their transfer error under H_true exceeds 12 px; the inliers are projections moved by at most
-    noise_px in each image; the rows are shuffled."""
-    h, w = int(size[0]), int(size[1])
-    n_out = int(round(k * outlier_fraction))
-    n_in = k - n_out
-    if k < 1 or n_in < 0 or n_out < 0 or noise_px < 0:
-        raise ValueError(f"planar_scene: bad k / outlier_fraction / noise_px {k}, {outlier_fraction}, {noise_px}")
-    pool = 16 * k + 64
-    u = synth.uniform24(int(seed) + (0x9A7A if rotation_only else 0x91A9), 16 + 8 * pool).astype(np.float64)
-    cam, u = u[:16], u[16:].reshape(8, pool)
-    kk, rot = _scene_camera(cam, h, w)
-    kinv = np.linalg.inv(kk)
-    if rotation_only:
-        h_true = kk @ rot @ kinv
-    else:  # the plane n · X = d in the first camera's frame, X' = R X + t: H = K (R + t nᵀ / d) K⁻¹
-        t = _scene_shift(cam)
-        n = np.array([-0.6 * (cam[6] - 0.5), -0.6 * (cam[7] - 0.5), 1.0])
-        d = 5.0 + 4.0 * cam[8]
-        h_true = kk @ (rot + np.outer(t, n) / d) @ kinv
-    h_true = _unit(h_true)
-    # inliers: a pixel of image 0 through H_true
-    p0 = np.stack([u[0] * (w - 1), u[1] * (h - 1)], 1)
-    q = np.concatenate([p0, np.ones((pool, 1))], 1) @ h_true.T
-    p1 = q[:, :2] / q[:, 2:3]
-    ok = (q[:, 2] * h_true[2, 2] > 0) & (p1[:, 0] >= 0) & (p1[:, 0] <= w - 1) & (p1[:, 1] >= 0) & (p1[:, 1] <= h - 1)
-    keep = np.nonzero(ok)[0][:n_in]
-    # outliers
-    o0 = np.stack([u[2] * (w - 1), u[3] * (h - 1)], 1)
-    o1 = np.stack([u[4] * (w - 1), u[5] * (h - 1)], 1)
-    with np.errstate(all="ignore"):
-        far = np.nonzero(np.sqrt(_transfer(h_true, o0, o1)) > 12.0)[0][:n_out]
-    if len(keep) < n_in or len(far) < n_out:
-        raise ValueError("planar_scene: the pool ran out (a seed whose second view sees too little)")
-    a = noise_px / np.sqrt(2.0)
-    noise = (u[6:8, :2 * n_in].reshape(2, 2, n_in) * 2.0 - 1.0) * a
-    k0 = np.concatenate([p0[keep] + noise[0].T, o0[far]])
-    k1 = np.concatenate([p1[keep] + noise[1].T, o1[far]])
-    gt = np.concatenate([np.ones(n_in, dtype=bool), np.zeros(n_out, dtype=bool)])
-    order = np.argsort(synth.uniform24(int(seed) + 0x5EED, k), kind="stable")
-    return (torch.from_numpy(k0[order].astype(np.float32)), torch.from_numpy(k1[order].astype(np.float32)),
-            torch.from_numpy(gt[order]), torch.from_numpy(h_true))
-
-
-def _scene_pose(seed: int, k: int, size, stream_seed: int, rows: int):
-    h, w = int(size[0]), int(size[1])
-    cam = synth.uniform24(stream_seed, 16 + rows * (16 * k + 64)).astype(np.float64)[:16]
-    kk, rot = _scene_camera(cam, h, w)
-    t = _scene_shift(cam)
-    return torch.from_numpy(kk), torch.from_numpy(rot), torch.from_numpy(t / np.linalg.norm(t))
-
-
-def calibrated_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
-    """two_view_scene(seed, k, outlier_fraction, noise_px, size) with its cameras: (kpts0, kpts1, gt_mask, F_true,
-    K [3, 3] float64 (both images'), R [3, 3], t [3] at unit length: X1 = R X0 + t). The first four are two_view_scene's
-    own, bit for bit: the same random stream."""
-    return two_view_scene(seed, k, outlier_fraction, noise_px, size) + _scene_pose(seed, k, size, int(seed), 9)
-
-
-def calibrated_planar_scene(seed: int, k: int, outlier_fraction: float, noise_px: float, size=(480, 640)):
-    """planar_scene(seed, k, outlier_fraction, noise_px, size) (the moved camera, not the rotation-only one) with its
-    cameras: (kpts0, kpts1, gt_mask, H_true, K, R, t) as calibrated_scene's."""
-    return planar_scene(seed, k, outlier_fraction, noise_px, size) + _scene_pose(seed, k, size, int(seed) + 0x91A9, 8)
+def _intrinsics(intrinsics: torch.Tensor, pr: int, matches: torch.Tensor) -> torch.Tensor:
+    """The check of intrinsics [P, 2, 4] fp32 next to the matches -> contiguous."""
+    require_gpu("intrinsics", intrinsics, _STAGE, (torch.float32,), 3)
+    _like_matches("intrinsics", intrinsics, (pr, 2, 4), matches)
+    return intrinsics.contiguous()
 
 
 # ---- the kernels --------------------------------------------------------------------------------------------------
 class _Ransac:
-    """What the two estimators share: the parameters, the checks of verify's inputs and the call. _ENTRY: the C
-    entry point; _RESULT: the NamedTuple of its five outputs."""
-    _ENTRY = ""
-    _RESULT = None
+    """What the estimators share: the parameters, the checks of verify's inputs and the call. _ENTRY: the C entry
+    point; _WORKSPACE: the entry point of its workspace size; _RESULT: the NamedTuple of its outputs."""
+    _ENTRY, _WORKSPACE, _RESULT = "", "lg_ransac_workspace", None
 
     def __init__(self, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2, seed: int = 888) -> None:
         _check_params(threshold, hypotheses, refits)
@@ -1080,26 +103,25 @@ class _Ransac:
                 raise ValueError(f"{name}: on {t.device}, the matches on {matches.device}")
         return tuple(t.contiguous() for t in (matches, counts, kpts0, kpts1)), pr, kmax
 
+    def _run(self, inputs, pr: int, kmax: int, *extra: torch.Tensor):
+        """The call on _inputs' outputs; extra: the tensors whose pointers follow kpts1's (the intrinsics)."""
+        matches, _, kpts0, kpts1 = inputs
+        out = _empty(self._RESULT, pr, kmax, matches.device)
+        if pr == 0:
+            return out
+        stream = stream_of(matches)
+        nbytes = int(getattr(_lib.load(), self._WORKSPACE)(pr, kmax, self.hypotheses))
+        ws, = carve(matches.device, stream, [nbytes])
+        call(self._ENTRY, *(t.data_ptr() for t in inputs + extra), pr, kmax, int(kpts0.shape[1]), int(kpts1.shape[1]),
+             self.threshold, self.hypotheses, self.refits, self._seed32(), ws.data_ptr(), nbytes, *(t.data_ptr() for t in out),
+             stream)
+        return out
+
     def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor):
         """result.matches [P, Kmax, 2] / result.counts [P] (int32) index kpts0 [P, K0, 2] and kpts1 [P, K1, 2]
         (fp32, (x, y) in pixels; ImageInput.keypoints' output is the intended one) -> the estimator's result. Two
         launches on the current stream, nothing read back; counts and indices are clamped, never trusted."""
-        (matches, counts, kpts0, kpts1), pr, kmax = self._inputs(result, kpts0, kpts1)
-        dev = matches.device
-        out = self._RESULT(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
-                           torch.empty((pr, kmax), dtype=torch.uint8, device=dev),
-                           torch.empty((pr,), dtype=torch.int32, device=dev),
-                           torch.empty((pr,), dtype=torch.int32, device=dev),
-                           torch.empty((pr,), dtype=torch.int32, device=dev))
-        if pr == 0:
-            return out
-        stream = stream_of(matches)
-        nbytes = int(_lib.load().lg_ransac_workspace(pr, kmax, self.hypotheses))
-        ws, = carve(dev, stream, [nbytes])
-        call(self._ENTRY, matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), pr, kmax,
-             int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses, self.refits, self._seed32(), ws.data_ptr(),
-             nbytes, *(t.data_ptr() for t in out), stream)
-        return out
+        return self._run(*self._inputs(result, kpts0, kpts1))
 
     def _seed32(self) -> int:
         return self.seed - (1 << 32) if self.seed >= 1 << 31 else self.seed  # the same 32 bits as int32
@@ -1111,10 +133,15 @@ class FundamentalRansac(_Ransac):
     on the data); refits: least-squares rounds over the inliers; seed: of the samples. verify -> GeometryResult."""
     _ENTRY, _RESULT = "lg_ransac_fundamental", GeometryResult
 
-    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor) -> GeometryResult:
-        return super().verify(result, kpts0, kpts1)
 
-    verify.__doc__ = _Ransac.verify.__doc__
+class HomographyRansac(_Ransac):
+    """RANSAC for the homography x1 ~ H x0 of every pair of a MatchResult (planar scenes, a rotating camera; what
+    cv::findHomography(pts0, pts1, cv::RANSAC, 3) does on the host, without its final Levenberg-Marquardt polish: on
+    the planar scenes a float64 prototype of it lowered the transfer cost by 3e-6 to 8e-5 relative, DESIGN §7).
+    The parameters are FundamentalRansac's; verify -> HomographyResult. A pair is valid from 4 inliers on, and a
+    4-inlier winner is only its own sample: threshold num_inliers before trusting H."""
+    _ENTRY, _RESULT = "lg_ransac_homography", HomographyResult
+
 
 class EssentialRansac(_Ransac):
     """Five-point RANSAC for the essential matrix, and the relative pose from it, of every pair of a MatchResult
@@ -1124,6 +151,7 @@ class EssentialRansac(_Ransac):
     appended as a third launch. verify -> PoseResult. A pair is valid from 5 inliers on, and a 5-inlier winner is
     only its own sample: threshold num_inliers before trusting the pose. On a planar scene two poses fit; which of
     them comes out is not specified."""
+    _ENTRY, _WORKSPACE, _RESULT = "lg_ransac_essential", "lg_ransac_essential_workspace", PoseResult
 
     def __init__(self, threshold: float = 3.0, hypotheses: int = 512, refits: int = 2, seed: int = 888, polish: int = 0) -> None:
         super().__init__(threshold, hypotheses, refits, seed)
@@ -1136,64 +164,31 @@ class EssentialRansac(_Ransac):
         keypoints' pixel frame) -> PoseResult. Two launches on the current stream (three with polish > 0: the result
         is then the polished one, valid and best the RANSAC's), nothing read back; a pair with a non-finite intrinsic
         or a focal length <= 0 is invalid."""
-        (matches, counts, kpts0, kpts1), pr, kmax = self._inputs(result, kpts0, kpts1)
-        require_gpu("intrinsics", intrinsics, _STAGE, (torch.float32,), 3)
-        if tuple(intrinsics.shape) != (pr, 2, 4):
-            raise ValueError(f"intrinsics: expected [{pr}, 2, 4], got {tuple(intrinsics.shape)}")
-        if intrinsics.device != matches.device:
-            raise ValueError(f"intrinsics: on {intrinsics.device}, the matches on {matches.device}")
-        dev = matches.device
-
-        def i32():
-            return torch.empty((pr,), dtype=torch.int32, device=dev)
-
-        out = PoseResult(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
-                         torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
-                         torch.empty((pr, 3), dtype=torch.float32, device=dev),
-                         torch.empty((pr, kmax), dtype=torch.uint8, device=dev), i32(), i32(), i32(), i32())
-        if pr == 0:
+        inputs, pr, kmax = self._inputs(result, kpts0, kpts1)
+        intrinsics = _intrinsics(intrinsics, pr, inputs[0])
+        out = self._run(inputs, pr, kmax, intrinsics)
+        if not self.polish or pr == 0:
             return out
-        intrinsics = intrinsics.contiguous()
-        stream = stream_of(matches)
-        nbytes = int(_lib.load().lg_ransac_essential_workspace(pr, kmax, self.hypotheses))
-        ws, = carve(dev, stream, [nbytes])
-        call("lg_ransac_essential", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(),
-             intrinsics.data_ptr(), pr, kmax, int(kpts0.shape[1]), int(kpts1.shape[1]), self.threshold, self.hypotheses,
-             self.refits, self._seed32(), ws.data_ptr(), nbytes, *(t.data_ptr() for t in out), stream)
-        if not self.polish:
-            return out
-        fine = _polish_call(matches, counts, kpts0, kpts1, intrinsics, out, self.threshold, self.polish, stream)
+        fine = _polish_call(*inputs, intrinsics, out, self.threshold, self.polish, stream_of(inputs[0]))
         return PoseResult(fine.E, fine.R, fine.t, fine.inliers, fine.num_inliers, fine.num_front, out.valid, out.best)
 
 
 def _calibrated_inputs(result: MatchResult, kpts0, kpts1, intrinsics, pose):
     """The checks PosePolish.refine and triangulate share -> (matches, counts, kpts0, kpts1, intrinsics, R, t, inliers)
     contiguous, P, Kmax."""
-    (matches, counts, kpts0, kpts1), pr, kmax = _Ransac._inputs(result, kpts0, kpts1)
-    require_gpu("intrinsics", intrinsics, _STAGE, (torch.float32,), 3)
+    inputs, pr, kmax = _Ransac._inputs(result, kpts0, kpts1)
+    intrinsics = _intrinsics(intrinsics, pr, inputs[0])
     require_gpu("R", pose.R, _STAGE, (torch.float32,), 3)
     require_gpu("t", pose.t, _STAGE, (torch.float32,), 2)
     require_gpu("inliers", pose.inliers, _STAGE, (torch.uint8,), 2)
-    for name, t, shape in (("intrinsics", intrinsics, (pr, 2, 4)), ("R", pose.R, (pr, 3, 3)), ("t", pose.t, (pr, 3)),
-                           ("inliers", pose.inliers, (pr, kmax))):
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name}: expected {list(shape)}, got {tuple(t.shape)}")
-        if t.device != matches.device:
-            raise ValueError(f"{name}: on {t.device}, the matches on {matches.device}")
-    return (matches, counts, kpts0, kpts1) + tuple(t.contiguous() for t in (intrinsics, pose.R, pose.t, pose.inliers)), pr, kmax
+    for name, t, shape in (("R", pose.R, (pr, 3, 3)), ("t", pose.t, (pr, 3)), ("inliers", pose.inliers, (pr, kmax))):
+        _like_matches(name, t, shape, inputs[0])
+    return inputs + (intrinsics,) + tuple(t.contiguous() for t in (pose.R, pose.t, pose.inliers)), pr, kmax
 
 
 def _polish_call(matches, counts, kpts0, kpts1, intrinsics, pose, threshold: float, iterations: int, stream) -> PolishResult:
-    pr, kmax, dev = int(matches.shape[0]), int(matches.shape[1]), matches.device
-
-    def i32():
-        return torch.empty((pr,), dtype=torch.int32, device=dev)
-
-    out = PolishResult(torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
-                       torch.empty((pr, 3, 3), dtype=torch.float32, device=dev),
-                       torch.empty((pr, 3), dtype=torch.float32, device=dev),
-                       torch.empty((pr, kmax), dtype=torch.uint8, device=dev), i32(), i32(),
-                       torch.empty((pr, 2), dtype=torch.float32, device=dev), i32())
+    pr, kmax = int(matches.shape[0]), int(matches.shape[1])
+    out = _empty(PolishResult, pr, kmax, matches.device)
     if pr:
         call("lg_pose_polish", matches.data_ptr(), counts.data_ptr(), kpts0.data_ptr(), kpts1.data_ptr(), intrinsics.data_ptr(),
              pr, kmax, int(kpts0.shape[1]), int(kpts1.shape[1]), pose.R.data_ptr(), pose.t.data_ptr(), pose.inliers.data_ptr(),
@@ -1241,20 +236,6 @@ def triangulate(result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor, i
              ok.data_ptr(), stream_of(matches))
     return points, ok
 
-
-
-class HomographyRansac(_Ransac):
-    """RANSAC for the homography x1 ~ H x0 of every pair of a MatchResult (planar scenes, a rotating camera; what
-    cv::findHomography(pts0, pts1, cv::RANSAC, 3) does on the host, without its final Levenberg-Marquardt polish: on
-    the planar scenes a float64 prototype of it lowered the transfer cost by 3e-6 to 8e-5 relative, DESIGN §7).
-    The parameters are FundamentalRansac's; verify -> HomographyResult. A pair is valid from 4 inliers on, and a
-    4-inlier winner is only its own sample: threshold num_inliers before trusting H."""
-    _ENTRY, _RESULT = "lg_ransac_homography", HomographyResult
-
-    def verify(self, result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor) -> HomographyResult:
-        return super().verify(result, kpts0, kpts1)
-
-    verify.__doc__ = _Ransac.verify.__doc__
 
 def verify_source_images(image_input: ImageInput, encoder, frontend, matcher,
                          ransac: "FundamentalRansac | HomographyRansac | EssentialRansac", images0, images1, *, intrinsics=None):

@@ -9,6 +9,7 @@ import torch
 
 from geometry_scenes import (ALT_SEEDS, FORMAT_LIMIT, HYPOTHESES, NOISE, OUTLIERS, REFITS, SCENE_SEEDS, SEED,  # noqa: F401
                              THRESHOLD, batch, pair)
+from scene_common import plant_dirty_rows
 
 # The seeds are geometry_scenes.py's: on each the float64 five-point reference returns exactly gt_mask with every
 # inlier below 1.5 px and every outlier above 6 px (test_essential.py asserts it), so none had to be replaced.
@@ -169,11 +170,7 @@ def ragged():
     m, counts, kp0, kp1 = batch(RAGGED_SPECS, RAGGED_KMAX)
     pad = torch.zeros((len(RAGGED_SPECS), 8, 2))
     kp0, kp1 = torch.cat([kp0, pad], 1), torch.cat([kp1, pad], 1)
-    p, k = RAGGED_DIRTY, 200
-    m[p, 5], m[p, 6] = torch.tensor([-7, k + 500]).int(), torch.tensor([k + 8, -1]).int()
-    kp0[p, int(m[p, 10, 0])] = float("nan")
-    kp1[p, int(m[p, 11, 1]), 0] = float("inf")
-    kp0[p, int(m[p, 12, 0]), 1] = float("-inf")
+    plant_dirty_rows(m[RAGGED_DIRTY], kp0[RAGGED_DIRTY], kp1[RAGGED_DIRTY], 200)
     intr = batch_intrinsics(len(RAGGED_SPECS)).clone()
     intr[RAGGED_BAD, 1, 0] = 0.0
     return m, counts, kp0, kp1, intr

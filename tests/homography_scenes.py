@@ -7,6 +7,7 @@ import functools
 import numpy as np
 import torch
 
+import scene_common
 from geometry_scenes import (FORMAT_LIMIT, HYPOTHESES, NOISE, OUTLIERS, PIVOT_MARGIN, REFITS, SCORE_MARGIN, SEED,  # noqa: F401
                              THRESHOLD)
 
@@ -30,23 +31,13 @@ def pair(k, alt=False, rotation=False):
     """The scene through the matcher's layout: (matches [k, 2] int32, kpts0 [k, 2], kpts1 [k, 2]) with the
     keypoints of each image in a shuffled order of their own; correspondence j is the scene's row j."""
     k0, k1, _, _ = scene(k, alt, rotation)
-    gen = torch.Generator().manual_seed(2000 + k)
-    p0, p1 = torch.randperm(k, generator=gen), torch.randperm(k, generator=gen)
-    kp0, kp1 = torch.empty_like(k0), torch.empty_like(k1)
-    kp0[p0], kp1[p1] = k0, k1
-    return torch.stack([p0, p1], 1).int(), kp0, kp1
+    return scene_common.shuffled_pair(k0, k1, 2000 + k)
 
 
 def batch(specs, kmax, alt=False, rotation=False):
     """specs: (scene k, count) per pair -> (matches [P, kmax, 2] with -1 past the count, counts [P], kpts0, kpts1
     [P, max k, 2] zero-padded)."""
-    kk = max(k for k, _ in specs)
-    m = torch.full((len(specs), kmax, 2), -1, dtype=torch.int32)
-    kp0, kp1 = torch.zeros((len(specs), kk, 2)), torch.zeros((len(specs), kk, 2))
-    for p, (k, count) in enumerate(specs):
-        mm, a, b = pair(k, alt, rotation)
-        m[p, :count], kp0[p, :k], kp1[p, :k] = mm[:count], a, b
-    return m, torch.tensor([c for _, c in specs], dtype=torch.int32), kp0, kp1
+    return scene_common.batch_of(lambda k: pair(k, alt, rotation), specs, kmax)
 
 
 @functools.lru_cache(maxsize=None)
@@ -117,10 +108,8 @@ def score_inputs():
     is moved to. Rows whose float64 error under a candidate lies within SCORE_MARGIN of the threshold are moved
     until none does."""
     from lightglue_amd import homography_refit, solve4_reference, transfer_error
-    from lightglue_amd.geometry import gather_correspondences
 
-    k = 2048
-    k0, k1, gt, h_true = scene(k)
+    k0, k1, gt, h_true = scene(2048)
     cands = [h_true.numpy(), homography_refit(k0[gt], k1[gt]).numpy()]
     inl = torch.nonzero(gt)[:, 0]
     for i in range(16):
@@ -129,30 +118,8 @@ def score_inputs():
     assert len(cands) == 6, "score_inputs: the all-inlier samples gave too few candidates"
     w0 = np.array([[0.5, 0.0, 0.0], [0.0, 0.5, 0.0], [2.0 ** -10, 0.0, -W0_POINT[0] * 2.0 ** -10]])
     cands = np.stack(cands + [np.zeros((3, 3)), np.full((3, 3), np.nan), w0]).astype(np.float32)
-    pr = len(SCORE_COUNTS)
-    m = torch.full((pr, k, 2), -1, dtype=torch.int32)
-    kp0, kp1 = torch.zeros((pr, k + 8, 2)), torch.zeros((pr, k + 8, 2))
-    want = torch.zeros((pr, len(cands)), dtype=torch.int32)
-    for p, count in enumerate(SCORE_COUNTS):
-        idx = (torch.arange(k) + 97 * p) % k
-        kp0[p, :k], kp1[p, :k] = k0, k1
-        kp0[p, k:], kp1[p, k:] = k0[:8], k1[-8:]          # rows that only a clamped index reaches
-        m[p, :count] = torch.stack([idx, idx], 1)[:count].int()
-        if count >= 63:
-            m[p, 5], m[p, 6] = torch.tensor([-7, k + 500]).int(), torch.tensor([k + 8, -1]).int()  # out of range
-            kp0[p, int(m[p, 10, 0])] = float("nan")
-            kp1[p, int(m[p, 11, 1]), 0] = float("inf")
-            kp0[p, int(m[p, 12, 0]), 1] = float("-inf")
-            kp0[p, int(m[p, 20, 0])] = torch.tensor(W0_POINT)
-        for _ in range(50):
-            x0, x1 = gather_correspondences(m[p], count, kp0[p], kp1[p])
-            err = torch.stack([transfer_error(c, x0, x1).sqrt() for c in cands])
-            near = ((err - THRESHOLD).abs() <= SCORE_MARGIN).any(0)
-            if not bool(near.any()):
-                break
-            for j in torch.nonzero(near)[:, 0].tolist():
-                kp1[p, int(m[p, j, 1].clamp(0, k + 7))] += torch.tensor([7.3, -5.1])
-        assert not bool(near.any()), "score_inputs: rows within the margin of the threshold remain"
-        want[p] = (err <= THRESHOLD).sum(1).int()  # (NaN and Inf compare false)
-    counts = torch.tensor(SCORE_COUNTS, dtype=torch.int32)
-    return m, counts, kp0, kp1, torch.from_numpy(cands).reshape(1, -1, 9).repeat(pr, 1, 1), want
+
+    def to_w0(p, m, kp0):
+        kp0[p, int(m[p, 20, 0])] = torch.tensor(W0_POINT)
+
+    return scene_common.score_inputs(k0, k1, cands, SCORE_COUNTS, transfer_error, THRESHOLD, SCORE_MARGIN, plant=to_w0)

@@ -8,6 +8,8 @@ import numpy as np
 import torch
 
 from geometry_scenes import ALT_SEEDS, HYPOTHESES, OUTLIERS, REFITS, SCENE_SEEDS, SEED, THRESHOLD  # noqa: F401
+from essential_scenes import batch_intrinsics, intrinsics, pose_errors_deg  # noqa: F401  (the cameras are the same)
+from scene_common import batch_of, shuffled_pair
 
 NOISE = 1.0
 POLISH = 10
@@ -29,37 +31,17 @@ def scene(k, alt=False):
 
 
 @functools.lru_cache(maxsize=None)
-def intrinsics():
-    kk = scene(24)[4]
-    return torch.tensor([[kk[0, 0], kk[1, 1], kk[0, 2], kk[1, 2]]] * 2, dtype=torch.float32)
-
-
-def batch_intrinsics(pairs):
-    return intrinsics()[None].repeat(pairs, 1, 1).contiguous()
-
-
-@functools.lru_cache(maxsize=None)
 def pair(k, alt=False):
     """The scene through the matcher's layout: (matches [k, 2] int32, kpts0 [k, 2], kpts1 [k, 2]) with the keypoints of
     each image in a shuffled order of their own; correspondence j is the scene's row j."""
     k0, k1 = scene(k, alt)[:2]
-    gen = torch.Generator().manual_seed(2000 + k)
-    p0, p1 = torch.randperm(k, generator=gen), torch.randperm(k, generator=gen)
-    kp0, kp1 = torch.empty_like(k0), torch.empty_like(k1)
-    kp0[p0], kp1[p1] = k0, k1
-    return torch.stack([p0, p1], 1).int(), kp0, kp1
+    return shuffled_pair(k0, k1, 2000 + k)
 
 
 def batch(specs, kmax):
     """specs: (k, alt) per pair, each whole -> (matches [P, kmax, 2] with -1 past the count, counts [P], kpts0, kpts1
     [P, max k, 2] zero-padded, intrinsics [P, 2, 4])."""
-    kk = max(k for k, _ in specs)
-    m = torch.full((len(specs), kmax, 2), -1, dtype=torch.int32)
-    kp0, kp1 = torch.zeros((len(specs), kk, 2)), torch.zeros((len(specs), kk, 2))
-    for p, (k, alt) in enumerate(specs):
-        mm, a, b = pair(k, alt)
-        m[p, :k], kp0[p, :k], kp1[p, :k] = mm, a, b
-    return m, torch.tensor([k for k, _ in specs], dtype=torch.int32), kp0, kp1, batch_intrinsics(len(specs))
+    return batch_of(lambda s: pair(*s), [((k, alt), k) for k, alt in specs], kmax) + (batch_intrinsics(len(specs)),)
 
 
 @functools.lru_cache(maxsize=None)
@@ -131,12 +113,6 @@ def keep_rule():
     b = batch(((64, False),), 64)
     ref = six_ransac()
     return b, given_pose(ref.R[1], ref.t[1], torch.ones(64, dtype=torch.uint8))
-
-
-def pose_errors_deg(r, t, r_want, t_want):
-    from lightglue_amd.geometry import direction_angle_deg, rotation_angle_deg
-
-    return rotation_angle_deg(r, r_want), direction_angle_deg(t, t_want)
 
 
 def rounded(pose):

@@ -132,7 +132,8 @@ def test_samples5_are_the_first_five_of_the_seven():
 # ---- the float64 pieces -----------------------------------------------------------------------------------------
 def test_reference_candidates_satisfy_the_constraints_and_their_samples():
     from lightglue_amd import camera_coordinates
-    from lightglue_amd.geometry import _rows, essential_residuals
+    from lightglue_amd.geometry import essential_residuals
+    from lightglue_amd.geometry_contract import _rows
 
     _, cases = es.solve_cases()
     intr = es.intrinsics()

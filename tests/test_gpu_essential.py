@@ -1,5 +1,5 @@
 """The calibrated five-point RANSAC on the MI355X (csrc/lightglue_essential.hip) against the float64 contract in
-lightglue_amd/geometry.py: the 5-samples bitwise, the five-point solve per hypothesis, the whole call on a ragged
+lightglue_amd/geometry_contract.py: the 5-samples bitwise, the five-point solve per hypothesis, the whole call on a ragged
 batch with untrusted inputs, the pose hook, the full width, independence of the batch, capture and replay, the planar
 scenes, and verify_source_images with intrinsics captured as one piece. The scenes and their preconditions are in
 essential_scenes.py and test_essential.py. Nothing here reads the reference tree.

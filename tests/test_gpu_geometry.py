@@ -1,5 +1,5 @@
 """Geometric verification on the MI355X (csrc/lightglue_geometry.hip) against the float64 contract in
-lightglue_amd/geometry.py: the samples bitwise, the 7-point solve per hypothesis, the scoring counts exactly, the
+lightglue_amd/geometry_contract.py: the samples bitwise, the 7-point solve per hypothesis, the scoring counts exactly, the
 whole call on ragged batches and at full width, independence of the batch, determinism, capture and replay, and
 verify_source_images against its parts. The scenes and their preconditions are in geometry_scenes.py and
 test_geometry.py. Nothing here reads the reference tree.

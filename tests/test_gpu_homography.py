@@ -1,5 +1,5 @@
 """The homography's RANSAC on the MI355X (csrc/lightglue_geometry.hip, the HomographyModel instantiations) against
-the float64 contract in lightglue_amd/geometry.py: the 4-samples bitwise, the 4-point solve per hypothesis, the
+the float64 contract in lightglue_amd/geometry_contract.py: the 4-samples bitwise, the 4-point solve per hypothesis, the
 scoring counts exactly, the whole call on ragged batches, small scenes, a rotation-only scene and at full width,
 guarded outputs, independence of the batch, determinism, capture and replay, and verify_source_images with a
 HomographyRansac against its parts. The scenes and their preconditions are in homography_scenes.py and

@@ -1,5 +1,5 @@
 """The pose polish and the triangulation on the MI355X (csrc/lightglue_polish.hip) against the float64 contract in
-lightglue_amd/geometry.py (polish_reference: scipy's least squares run to convergence in another parameterisation):
+lightglue_amd/geometry_contract.py (polish_reference: scipy's least squares run to convergence in another parameterisation):
 polish = 0 bitwise today's call, verify(polish = 10) on the six scenes in one call, the hook on a ragged batch with
 untrusted inputs through raw pointers, the full width, the keep rule, the planar pairs, independence of the batch,
 repeatability, capture and replay, and lg_triangulate. The scenes and their preconditions are in polish_scenes.py and

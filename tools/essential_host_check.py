@@ -1,7 +1,7 @@
 """The five-point RANSAC's statements on the CPU, before any GPU run: csrc/lightglue_essential_math.h is
 __host__ __device__, tools/essential_host.cpp wraps its 5-sample, five-point solve (the four lanes of a hypothesis
 run in turn), one refit round as the finalize kernel orders it and the pose, and this script compares them with the
-float64 contract in lightglue_amd/geometry.py on the calibrated scenes of tests/essential_scenes.py (k = 24, 64, 200
+float64 contract in lightglue_amd/geometry_contract.py on the calibrated scenes of tests/essential_scenes.py (k = 24, 64, 200
 and the alternates, rows as they are and reversed, 64 hypotheses each). It prints the worsts the bounds of
 tests/test_gpu_essential.py are pinned from (four times each): the sample-point epipolar error of a kept candidate
 (SOLVE_BOUND_PX), the refit against essential_refit per point on the ground-truth mask (REFIT_BOUND_PX), R and t

@@ -1,6 +1,6 @@
 """The homography's per-lane statements on the CPU, before any GPU run: csrc/lightglue_geometry_math.h is
 __host__ __device__, tools/homography_host.cpp wraps its 4-sample, 4-point solve (in double and in float) and
-transfer-error test, and this script compares them with the float64 contract in lightglue_amd/geometry.py on the
+transfer-error test, and this script compares them with the float64 contract in lightglue_amd/geometry_contract.py on the
 planar scenes of tests/homography_scenes.py (k = 8, 24, 64, 200, the alternates and the rotation scene, rows as
 they are and reversed, 64 hypotheses each). Per real type: the hypotheses the reference keeps (a pivot >= 1e-3,
 orientation determinants >= 1e-3, its own candidate rounded to fp32 within 5e-3 px of its sample), disagreements

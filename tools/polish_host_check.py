@@ -1,7 +1,7 @@
 """The pose polish's and the triangulation's statements on the CPU, before any GPU run: csrc/lightglue_polish_math.h
 is __host__ __device__, tools/polish_host.cpp wraps pose_polish_kernel for one pair with the workgroup's rows run
 serially (and tools/essential_host.cpp the RANSAC before it), and this script compares them with the float64 contract
-in lightglue_amd/geometry.py (polish_reference: scipy's least squares run to convergence in another
+in lightglue_amd/geometry_contract.py (polish_reference: scipy's least squares run to convergence in another
 parameterisation) on every pair tests/test_gpu_pose_polish.py runs: the six scenes of tests/polish_scenes.py through
 RANSAC and POLISH rounds, the hook on essential_scenes.ragged(), the full width, the keep rule's pair and the planar
 pairs. Masks, counts and kept must equal the reference's; it prints the worsts the GPU bounds are pinned from (four
