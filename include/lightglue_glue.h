@@ -676,6 +676,84 @@ int32_t lg_triangulate(const int32_t* matches, const int32_t* counts, const floa
                        const float* intrinsics, int32_t pairs, int32_t kmax, int32_t k0, int32_t k1, const float* r, const float* t,
                        const uint8_t* inliers, float* points, uint8_t* ok, hipStream_t stream);
 
+/* The absolute pose (csrc/lightglue_absolute.hip): the pose of a camera against 3D points that earlier frames produced,
+ * what cv::solvePnPRansac does on the host. lg_ransac_essential gives every pair a frame and a scale (|t| = 1) of its
+ * own; localising the next image against the points lg_triangulate wrote gives it a pose in the first pair's frame at
+ * the first pair's scale, so a sequence's poses compose (the reference's demo walks a sequence, each frame matched
+ * against the previous one: demo/demo_mono.cpp:400-405). New symbols only: LG_GLUE_ABI_VERSION stays 4. The general
+ * statements of lg_ransac_fundamental hold for every call below (arguments checked before any device call, a no-op for
+ * pairs == 0, counts and indices clamped, never trusted, no allocation, no host synchronisation, every output entry
+ * written), with one change to "no atomics": there are no floating-point atomics, and lg_link_landmarks uses an integer
+ * atomicMin in LDS, whose result does not depend on the order. lightglue_amd/geometry_contract.py restates the contract
+ * in float64 by another route (link_landmarks_reference, absolute_pose_reference).
+ *
+ * lg_link_landmarks: the 3D points of pair A onto the match rows of pair B, where both pairs share an image. Inputs:
+ * matches_a [pairs, kmax_a, 2] and counts_a, points_a [pairs, kmax_a, 3] fp32 and ok_a [pairs, kmax_a] uint8
+ * (lg_triangulate's outputs); side_a in {0, 1}: the column of matches_a that indexes the shared image; matches_b
+ * [pairs, kmax_b, 2] and counts_b, whose column 0 indexes the shared image and column 1 the new one; kpts_b1
+ * [pairs, k_b1, 2] fp32: the new image's keypoints in pixels. 1 <= kmax_a, kmax_b, k_shared <= 2048 (k_shared: the
+ * shared image's keypoints), k_b1 >= 1; every pointer but ok_a 4-B aligned. A row r of A below its count with
+ * ok_a != 0 owns the shared keypoint matches_a[r, side_a] (clamped into [0, k_shared)); where several rows name one
+ * keypoint the lowest row owns it. A row k of B below its count is linked iff its shared keypoint (clamped) has an
+ * owner. The linked rows, compacted in ascending k: points [pairs, kmax_b, 3] fp32 (the owner's point, the same bits),
+ * image [pairs, kmax_b, 2] fp32 (the new image's keypoint, its index clamped), rows [pairs, kmax_b] int32 (the row of
+ * matches_b), n [pairs] int32 (their number); past n points and image are zeros and rows -1. One launch, one workgroup
+ * per pair: the owners in LDS, the compaction by a workgroup prefix sum. The outputs may not alias the inputs. */
+int32_t lg_link_landmarks(const int32_t* matches_a, const int32_t* counts_a, const float* points_a, const uint8_t* ok_a,
+                          int32_t side_a, const int32_t* matches_b, const int32_t* counts_b, const float* kpts_b1, int32_t pairs,
+                          int32_t kmax_a, int32_t kmax_b, int32_t k_shared, int32_t k_b1, float* points, float* image,
+                          int32_t* rows, int32_t* n, hipStream_t stream);
+/* lg_ransac_absolute: the pose from 2D-3D correspondences (a caller with a map of their own needs no
+ * lg_link_landmarks). Inputs: points [pairs, kmax, 3] fp32, image [pairs, kmax, 2] fp32 (pixels), counts [pairs] int32
+ * (clamped into [0, kmax]), intrinsics [pairs, 4] fp32, (fx, fy, cx, cy) of the one camera. 1 <= kmax <= 2048,
+ * pairs <= 65,535, pairs * kmax <= 2^28; every pointer 4-B aligned, the workspace 16-B. Model: X_c = R X + t,
+ * det R = +1; t is not normalised: the scale is the map's. The error of a row: with (X_c, Y_c, Z_c) = R X + t,
+ * (fx X_c / Z_c + cx - x)² + (fy Y_c / Z_c + cy - y)²; an inlier iff Z_c > 0 and the error <= threshold² (NaN is none).
+ * The kernels test dx² + dy² <= threshold² Z_c² with dx = fx X_c + (cx - x) Z_c, dy alike, in fp32. Per pair:
+ *   1. Fewer than 4 rows, an intrinsic that is not finite or a focal length <= 0: the pair is invalid, every output
+ *      zeros and best = -1.
+ *   2. Hypothesis h samples 3 distinct rows: the first three draws of lg_ransac_fundamental's step 2 (ransac_samples3).
+ *   3. The P3P solve, fp64 (the route is written out in csrc/lightglue_absolute_math.h). Bearings: the unit vectors
+ *      of ((x - cx) / fx, (y - cy) / fy, 1). The quartic in u = s2 / s1 (the ratio of two camera distances; Grunert's),
+ *      its real roots in (0, Cauchy bound] by cutting the interval at the real roots of the derivative (a closed-form
+ *      cubic), 40 bisections of every piece whose ends differ in sign and 4 bracketed Newton steps; per root the three
+ *      camera points and the pose from the two triangles' orthonormal frames. No candidate: anything non-finite, a
+ *      sample triangle whose area over its longest side squared is below 1e-6, a distance ratio <= 0, or a candidate
+ *      under which one of its own three points has depth <= 0. 0 to 4 candidates, rounded to fp32, in ascending
+ *      |R X_s0 + t| (the first sample point's distance from the camera).
+ *   4. Each candidate is scored in fp32 over all rows. The winner: the highest count, then the lowest hypothesis, then
+ *      the candidates' order.
+ *   5. `refits` rounds, each with at least 4 current inliers: Levenberg-Marquardt on the 6 parameters (R <- exp([ω]x) R
+ *      by the exact Rodrigues formula, t <- t + δ) over Σ squared reprojection error in px² of the round's fixed set (the
+ *      current inliers with a finite residual at a positive depth under the entering pose: the current fp32 pose, R one
+ *      Newton step of the polar iteration nearer the rotations; fewer than 3 rows end the rounds), analytic Jacobian,
+ *      (JᵀJ + λ diag(JᵀJ)) δ = -Jᵀr by a 6 x 6 Cholesky in fp64, λ and the accept rule lg_pose_polish's, 4 rounds
+ *      (kAbsoluteLmRounds), one pass over the rows a round. Then the mask again as in step 4 at the pose rounded to
+ *      fp32. A round whose pose counts fewer inliers, or is not finite, is dropped and the rounds stop.
+ *   6. valid = 1 from 4 inliers on. A 4-inlier winner is little more than its own sample: threshold num_inliers.
+ * Two launches, the shapes of lg_ransac_essential's (the four lanes of a hypothesis take a piece of the quartic's
+ * interval each). threshold, hypotheses, refits, seed as there. Outputs: r [pairs, 3, 3], t [pairs, 3] fp32, inliers
+ * [pairs, kmax] uint8 (0 past the count), num_inliers, valid, best [pairs] int32. */
+size_t lg_ransac_absolute_workspace(int32_t pairs, int32_t kmax, int32_t hypotheses);
+int32_t lg_ransac_absolute(const float* points, const float* image, const int32_t* counts, const float* intrinsics,
+                           int32_t pairs, int32_t kmax, float threshold, int32_t hypotheses, int32_t refits, int32_t seed,
+                           void* workspace, size_t workspace_bytes, float* r, float* t, uint8_t* inliers, int32_t* num_inliers,
+                           int32_t* valid, int32_t* best, hipStream_t stream);
+/* Stage hooks over the same device code (tests). lg_ransac_samples3: step 2 for one count in [3, 2048] -> samples
+ * [hypotheses, 3] int32 in draw order. */
+int32_t lg_ransac_samples3(int32_t count, int32_t hypotheses, int32_t seed, int32_t* samples, hipStream_t stream);
+/* lg_ransac_solve3: step 3 on given samples [hypotheses, 3] int32 (device; clamped into [0, count), shared by the
+ * pairs) -> candidates [pairs, hypotheses, 4, 12] fp32 (R row-major then t; those that exist first, in step 3's order,
+ * the rest zeros) and num [pairs, hypotheses] int32. An invalid pair: zeros. */
+int32_t lg_ransac_solve3(const float* points, const float* image, const int32_t* counts, const float* intrinsics, int32_t pairs,
+                         int32_t kmax, const int32_t* samples, int32_t hypotheses, float* candidates, int32_t* num,
+                         hipStream_t stream);
+/* lg_ransac_score_absolute: step 4's count for given poses [pairs, num_poses, 12] fp32 (1 <= num_poses <= 4096) ->
+ * inlier_counts [pairs, num_poses] int32 (zeros where an intrinsic is bad). */
+int32_t lg_ransac_score_absolute(const float* points, const float* image, const int32_t* counts, const float* intrinsics,
+                                 int32_t pairs, int32_t kmax, const float* poses, int32_t num_poses, float threshold,
+                                 int32_t* inlier_counts, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

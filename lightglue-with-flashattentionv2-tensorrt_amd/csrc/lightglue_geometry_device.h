@@ -1,6 +1,6 @@
 // lightglue_geometry_device.h — what the RANSAC kernel files share on the device and in their entry points
 // (csrc/lightglue_geometry.hip: the fundamental matrix and the homography; csrc/lightglue_essential.hip: the
-// calibrated five-point): the launch shapes, a pair's arguments and its correspondences into LDS, the ordered block
+// calibrated five-point; csrc/lightglue_absolute.hip: the absolute pose's P3P): the launch shapes, a pair's arguments and its correspondences into LDS, the ordered block
 // sum, the refit's steps (the Hartley normalisation, the normal matrix's eigenvectors: the wave tree of its 45 sums
 // and the round-robin Jacobi on the 9 x 9 in LDS), the samples' entry point and the argument checks. The per-lane arithmetic is in lightglue_geometry_math.h.
 #pragma once
@@ -184,7 +184,7 @@ bool score_args_ok(float threshold, int32_t num_candidates, const float* candida
            aligned4(candidates) && aligned4(inlier_counts);
 }
 
-// lg_ransac_samples, lg_ransac_samples4, lg_ransac_samples5: a lane is a hypothesis.
+// lg_ransac_samples, lg_ransac_samples4, lg_ransac_samples5, lg_ransac_samples3: a lane is a hypothesis.
 template <int N>
 __global__ __launch_bounds__(kHypLanes) void ransac_samples_kernel(int count, int hypotheses, uint32_t seed,
                                                                     int32_t* __restrict__ out) {

@@ -210,6 +210,13 @@ SIGNATURES.update({
     "lg_pose_polish": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                         _P], _I),
     "lg_triangulate": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    # the absolute pose (csrc/lightglue_absolute.hip)
+    "lg_link_landmarks": ([_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "lg_ransac_absolute_workspace": ([_I, _I, _I], _S),
+    "lg_ransac_absolute": ([_P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _I, _I, _P, _S, _P, _P, _P, _P, _P, _P, _P], _I),
+    "lg_ransac_samples3": ([_I, _I, _I, _P, _P], _I),
+    "lg_ransac_solve3": ([_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P], _I),
+    "lg_ransac_score_absolute": ([_P, _P, _P, _P, _I, _I, _P, _I, ctypes.c_float, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -18,6 +18,12 @@ matrix and the relative pose (R, t) from it, given each image's (fx, fy, cx, cy)
 Sampson distance in pixels over the pose's inliers by N rounds of Levenberg-Marquardt on the 5 parameters of (R, t),
 recomputes the mask and keeps the result where it loses no inlier; ``triangulate`` writes every inlier's 3D point.
 
+``AbsolutePoseRansac.localize`` (csrc/lightglue_absolute.hip) is the absolute pose: P3P RANSAC for the pose of a camera
+against 3D points, what cv::solvePnPRansac does on the host; ``link_landmarks`` carries the points ``triangulate`` wrote
+for one pair onto the match rows of the next pair that shares an image with it, and ``inliers_on_matches`` brings the
+result's mask back onto those rows: EssentialRansac(polish=N).verify -> triangulate -> link_landmarks ->
+localize_landmarks gives the next frame a pose in the first pair's frame at the first pair's scale.
+
 This module is the kernel side only. What each call computes is pinned in float64 in geometry_contract.py, and the
 synthetic pairs of the tests are in geometry_scenes.py; both are re-exported here.
 """
@@ -28,14 +34,15 @@ import torch
 from . import _lib
 from ._host import call, carve, require_gpu, stream_of
 from .geometry_contract import (  # noqa: F401  (the public names this module had before the contract was split off)
-    _M32, MAX_HYPOTHESES, MAX_REFITS, MIN_INLIERS, MIN_INLIERS_E, MIN_INLIERS_H, MIN_POLISH_ROWS, PIVOT_EPS, GeometryResult,
+    _M32, AbsolutePoseResult, Landmarks, MAX_HYPOTHESES, MAX_REFITS, MIN_INLIERS, MIN_INLIERS_E, MIN_INLIERS_H, MIN_POLISH_ROWS, PIVOT_EPS, GeometryResult,
     HomographyResult, PolishResult, PoseResult, Solve4, Solve5, Solve7, _check_params, _rows, camera_coordinates, direction_angle_deg,
     elimination_pivots, epipolar_error, essential_constraints, essential_reference, essential_refit, essential_residuals,
     essential_to_fundamental, fundamental_refit, gather_correspondences, homography_reference, homography_refit,
     polish_pose_reference, polish_reference, pose_candidates, pose_from_essential_reference, ransac_reference, ransac_samples,
-    ransac_samples5, rotation_angle_deg, sampson_error, solve4_reference, solve5_reference, solve7_reference, transfer_error,
-    triangulate_reference)
-from .geometry_scenes import calibrated_planar_scene, calibrated_scene, planar_scene, two_view_scene  # noqa: F401
+    ransac_samples3, ransac_samples5, reprojection_error, rotation_angle_deg, sampson_error, solve4_reference, solve5_reference, solve7_reference, transfer_error,
+    triangulate_reference, absolute_pose_reference, absolute_refit_reference, link_landmarks_reference, solve3_reference, Solve3)
+from .geometry_scenes import (ThreeViews, absolute_scene, calibrated_planar_scene, calibrated_scene, planar_scene,  # noqa: F401
+                              three_view_scene, two_view_scene)
 from .image import ImageInput, match_source_images
 from .matches import MatchResult
 
@@ -46,7 +53,8 @@ MAX_POLISH = 16         # rounds of the pose polish
 # A result field's shape after [P] (None: Kmax) and dtype on the device; every field not named here is [P] int32.
 _FIELDS = {"F": ((3, 3), torch.float32), "H": ((3, 3), torch.float32), "E": ((3, 3), torch.float32),
            "R": ((3, 3), torch.float32), "t": ((3,), torch.float32), "cost": ((2,), torch.float32),
-           "inliers": ((None,), torch.uint8)}
+           "inliers": ((None,), torch.uint8), "points": ((None, 3), torch.float32), "image": ((None, 2), torch.float32),
+           "rows": ((None,), torch.int32)}
 
 
 def _empty(result, pr: int, kmax: int, dev):
@@ -235,6 +243,100 @@ def triangulate(result: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor, i
              kmax, int(kpts0.shape[1]), int(kpts1.shape[1]), r.data_ptr(), t.data_ptr(), inliers.data_ptr(), points.data_ptr(),
              ok.data_ptr(), stream_of(matches))
     return points, ok
+
+
+# ---- the absolute pose ------------------------------------------------------------------------------------------------
+def link_landmarks(result_a: MatchResult, points_a: torch.Tensor, ok_a: torch.Tensor, result_b: MatchResult,
+                   kpts_b1: torch.Tensor, *, side_a: int = 1, num_shared: int) -> Landmarks:
+    """The 3D points of pair A onto the match rows of pair B, where both pairs share an image: result_a (matches
+    [P, Ka, 2], counts [P]) with triangulate's points_a [P, Ka, 3] fp32 and ok_a [P, Ka] uint8; side_a: the column of
+    pair A's matches that indexes the shared image (1: the sequence's case, A = (i - 1, i) and B = (i, i + 1));
+    result_b, whose column 0 indexes the shared image; kpts_b1 [P, K1, 2] fp32: the new image's keypoints in pixels;
+    num_shared in [1, 2048]: the shared image's keypoints -> Landmarks. A row of B is linked iff a row of A with
+    ok_a != 0 names its shared keypoint (the lowest such row owns it); the linked rows are compacted in ascending order.
+    One launch on the current stream, nothing read back."""
+    ma, ca, mb, cb = result_a.matches, result_a.counts, result_b.matches, result_b.counts
+    for name, t, dt, nd in (("matches_a", ma, torch.int32, 3), ("counts_a", ca, torch.int32, 1), ("points_a", points_a, torch.float32, 3),
+                            ("ok_a", ok_a, torch.uint8, 2), ("matches_b", mb, torch.int32, 3), ("counts_b", cb, torch.int32, 1),
+                            ("kpts_b1", kpts_b1, torch.float32, 3)):
+        require_gpu(name, t, _STAGE, (dt,), nd)
+    if side_a not in (0, 1):
+        raise ValueError(f"side_a is 0 or 1, got {side_a}")
+    if not 1 <= int(num_shared) <= MAX_POINTS:
+        raise ValueError(f"num_shared must be in [1, {MAX_POINTS}], got {num_shared}")
+    pr, ka, kb = int(ma.shape[0]), int(ma.shape[1]), int(mb.shape[1])
+    if ma.shape[2] != 2 or not 1 <= ka <= MAX_POINTS:
+        raise ValueError(f"matches_a: expected [P, Ka, 2] with 1 <= Ka <= {MAX_POINTS}, got {tuple(ma.shape)}")
+    if mb.shape[0] != pr or mb.shape[2] != 2 or not 1 <= kb <= MAX_POINTS:
+        raise ValueError(f"matches_b: expected [{pr}, Kb, 2] with 1 <= Kb <= {MAX_POINTS}, got {tuple(mb.shape)}")
+    if kpts_b1.shape[0] != pr or kpts_b1.shape[1] < 1 or kpts_b1.shape[2] != 2:
+        raise ValueError(f"kpts_b1: expected [{pr}, K, 2] with K >= 1, got {tuple(kpts_b1.shape)}")
+    for name, t, shape in (("counts_a", ca, (pr,)), ("points_a", points_a, (pr, ka, 3)), ("ok_a", ok_a, (pr, ka)),
+                           ("matches_b", mb, (pr, kb, 2)), ("counts_b", cb, (pr,)), ("kpts_b1", kpts_b1, tuple(kpts_b1.shape))):
+        _like_matches(name, t, shape, ma)
+    ma, ca, points_a, ok_a, mb, cb, kpts_b1 = (t.contiguous() for t in (ma, ca, points_a, ok_a, mb, cb, kpts_b1))
+    out = _empty(Landmarks, pr, kb, ma.device)
+    if pr:
+        call("lg_link_landmarks", ma.data_ptr(), ca.data_ptr(), points_a.data_ptr(), ok_a.data_ptr(), int(side_a), mb.data_ptr(),
+             cb.data_ptr(), kpts_b1.data_ptr(), pr, ka, kb, int(num_shared), int(kpts_b1.shape[1]), *(t.data_ptr() for t in out),
+             stream_of(ma))
+    return out
+
+
+class AbsolutePoseRansac(_Ransac):
+    """P3P RANSAC for the pose of a camera from 2D-3D correspondences (what cv::solvePnPRansac does on the host), with
+    Levenberg-Marquardt refits of the reprojection error over the inliers. The parameters are FundamentalRansac's; the
+    threshold is the reprojection error in pixels. localize -> AbsolutePoseResult: X_c = R X + t at the scale of the
+    points. A pair is valid from 4 inliers on, and a 4-inlier winner is little more than its own sample: threshold
+    num_inliers before trusting the pose. Unlike the 8-point refit, P3P is not degenerate on planar points."""
+    _ENTRY, _WORKSPACE, _RESULT = "lg_ransac_absolute", "lg_ransac_absolute_workspace", AbsolutePoseResult
+
+    def localize(self, points: torch.Tensor, image: torch.Tensor, counts: torch.Tensor, intrinsics: torch.Tensor) -> AbsolutePoseResult:
+        """points [P, Kmax, 3], image [P, Kmax, 2] (pixels) fp32, counts [P] int32 (row k < counts[p] pairs points[p, k]
+        with image[p, k]), intrinsics [P, 4] fp32 (fx, fy, cx, cy) -> AbsolutePoseResult. Two launches on the current
+        stream, nothing read back; counts are clamped, never trusted; a pair with a non-finite intrinsic or a focal
+        length <= 0 is invalid."""
+        require_gpu("points", points, _STAGE, (torch.float32,), 3)
+        require_gpu("image", image, _STAGE, (torch.float32,), 3)
+        require_gpu("counts", counts, _STAGE, (torch.int32,), 1)
+        require_gpu("intrinsics", intrinsics, _STAGE, (torch.float32,), 2)
+        pr, kmax = int(points.shape[0]), int(points.shape[1])
+        if points.shape[2] != 3 or not 1 <= kmax <= MAX_POINTS:
+            raise ValueError(f"points: expected [P, Kmax, 3] with 1 <= Kmax <= {MAX_POINTS}, got {tuple(points.shape)}")
+        for name, t, shape in (("image", image, (pr, kmax, 2)), ("counts", counts, (pr,)), ("intrinsics", intrinsics, (pr, 4))):
+            _like_matches(name, t, shape, points)
+        points, image, counts, intrinsics = (t.contiguous() for t in (points, image, counts, intrinsics))
+        out = _empty(AbsolutePoseResult, pr, kmax, points.device)
+        if pr == 0:
+            return out
+        stream = stream_of(points)
+        nbytes = int(_lib.load().lg_ransac_absolute_workspace(pr, kmax, self.hypotheses))
+        ws, = carve(points.device, stream, [nbytes])
+        call(self._ENTRY, points.data_ptr(), image.data_ptr(), counts.data_ptr(), intrinsics.data_ptr(), pr, kmax, self.threshold,
+             self.hypotheses, self.refits, self._seed32(), ws.data_ptr(), nbytes, *(t.data_ptr() for t in out), stream)
+        return out
+
+    def localize_landmarks(self, landmarks: Landmarks, intrinsics: torch.Tensor) -> AbsolutePoseResult:
+        """localize on link_landmarks' output; the mask is aligned with the landmarks' rows (inliers_on_matches brings
+        it back onto pair B's match rows)."""
+        return self.localize(landmarks.points, landmarks.image, landmarks.counts, intrinsics)
+
+    def verify(self, *args, **kwargs):
+        raise TypeError("AbsolutePoseRansac has no verify: its inputs are 2D-3D correspondences (localize, localize_landmarks)")
+
+
+def inliers_on_matches(landmarks: Landmarks, result: AbsolutePoseResult, kmax_b: int) -> torch.Tensor:
+    """The absolute pose's mask on the rows of pair B's matches: [P, kmax_b] uint8, 1 where the row was linked and its
+    landmark is an inlier of `result`. Framework ops (a masked scatter), nothing read back."""
+    pr, kb = landmarks.rows.shape
+    if tuple(result.inliers.shape) != (pr, kb) or int(kmax_b) < kb:
+        raise ValueError(f"inliers_on_matches: a mask of {[pr, kb]} and kmax_b >= {kb}, got {tuple(result.inliers.shape)} and {kmax_b}")
+    live = landmarks.rows >= 0
+    # the rows past the count go to a column of their own (every write there is a 0), which is then cut off
+    out = torch.zeros((pr, int(kmax_b) + 1), dtype=torch.uint8, device=landmarks.rows.device)
+    index = torch.where(live, landmarks.rows, torch.full_like(landmarks.rows, int(kmax_b))).long()
+    out.scatter_(1, index, (result.inliers != 0).to(torch.uint8) * live.to(torch.uint8))
+    return out[:, :int(kmax_b)].contiguous()
 
 
 def verify_source_images(image_input: ImageInput, encoder, frontend, matcher,

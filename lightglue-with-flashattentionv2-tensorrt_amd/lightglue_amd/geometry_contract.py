@@ -22,6 +22,12 @@ The pose polish and the triangulation: ``sampson_error``, ``polish_pose_referenc
 (``scipy.optimize.least_squares(method="lm")`` on a global rotation vector and two angles of t with a numeric
 Jacobian, deliberately not the kernel's route: the converged minimiser is what is compared), ``polish_reference`` (a
 batch of it) and ``triangulate_reference``.
+
+The absolute pose (a camera against 3D points): ``ransac_samples3``, ``reprojection_error``, ``solve3_reference``
+(Grunert's quartic by ``numpy.roots``, the third distance from a quadratic, the pose by an SVD absolute orientation:
+not the kernel's bracketed roots, rational third distance and triangle frames), ``absolute_refit_reference`` (scipy's
+least squares to its tolerance floor on a global rotation vector and t), ``absolute_pose_reference`` (the whole, a
+fourth model of ``_ransac_pair``) and ``link_landmarks_reference`` (the 3D points of one pair onto the rows of the next).
 """
 from __future__ import annotations
 
@@ -36,6 +42,10 @@ MIN_POLISH_ROWS = 5     # the polish's fixed set needs as many rows as there are
 MIN_INLIERS = 8         # a fundamental matrix, and its refit, needs 8 correspondences
 MIN_INLIERS_H = 4       # a homography, and its refit, needs 4
 MIN_INLIERS_E = 5       # an essential matrix needs 5 (its refit 8, as the fundamental matrix's)
+MIN_INLIERS_A = 4       # an absolute pose, and its refit, needs 4 correspondences
+MIN_ABSOLUTE_ROWS = 3   # the refit's fixed set needs as many residuals as there are parameters
+AREA_EPS = 1e-6         # a P3P sample triangle's area over its longest side squared below this: no candidate
+MAX_POINTS = 2048       # kmax, and the keypoints of a shared image
 PIVOT_EPS = 1e-6        # a pivot of the 7 x 9 (8 x 9) elimination below this: no candidate
 _M32 = 0xFFFFFFFF
 
@@ -97,6 +107,31 @@ class PolishResult(NamedTuple):
     kept: torch.Tensor
 
 
+class AbsolutePoseResult(NamedTuple):
+    """R [P, 3, 3] and t [P, 3] (X_c = R X + t, det R = +1; t is not normalised: the scale is the map's), inliers
+    [P, Kmax] uint8 aligned with the rows of the correspondences (0 past the count), num_inliers, valid, best [P] int32
+    (best: the winning hypothesis, -1 where valid == 0; every other output is zeros there). A pair is valid from 4
+    inliers on, and a 4-inlier winner is little more than its own sample: threshold num_inliers before trusting the
+    pose."""
+    R: torch.Tensor
+    t: torch.Tensor
+    inliers: torch.Tensor
+    num_inliers: torch.Tensor
+    valid: torch.Tensor
+    best: torch.Tensor
+
+
+class Landmarks(NamedTuple):
+    """The 2D-3D correspondences link_landmarks makes of two pairs that share an image: points [P, Kmax_b, 3] (pair A's
+    3D points), image [P, Kmax_b, 2] (the new image's keypoints, pixels), rows [P, Kmax_b] int32 (the row of pair B's
+    matches each came from, ascending; -1 past the count), counts [P] int32. Points and image are zeros past the
+    count."""
+    points: torch.Tensor
+    image: torch.Tensor
+    rows: torch.Tensor
+    counts: torch.Tensor
+
+
 # ---- the minimal samples --------------------------------------------------------------------------------------
 def _hash32(seed: int, h: np.ndarray, j: int) -> np.ndarray:
     """The counter-based hash of (seed, hypothesis, draw), uint32 arithmetic: the key folded by odd multipliers,
@@ -143,6 +178,15 @@ def ransac_samples5(seed: int, hypotheses: int, count: int) -> torch.Tensor:
     if count < 5 or hypotheses < 1:
         raise ValueError(f"ransac_samples5: count >= 5 and hypotheses >= 1, got {count} and {hypotheses}")
     return _samples(seed, hypotheses, count, 5)
+
+
+def ransac_samples3(seed: int, hypotheses: int, count: int) -> torch.Tensor:
+    """[H, 3] int32: hypothesis h's three distinct indices in [0, count) for the absolute pose, by ransac_samples'
+    rule (count >= 3): for count >= 7 the first three columns of its 7-sample."""
+    seed, hypotheses, count = int(seed), int(hypotheses), int(count)
+    if count < 3 or hypotheses < 1:
+        raise ValueError(f"ransac_samples3: count >= 3 and hypotheses >= 1, got {count} and {hypotheses}")
+    return _samples(seed, hypotheses, count, 3)
 
 
 # ---- the contract's pieces in float64 ---------------------------------------------------------------------------
@@ -762,12 +806,14 @@ def gather_correspondences(matches, count: int, kpts0, kpts1) -> Tuple[np.ndarra
 
 
 # ---- the scheme -------------------------------------------------------------------------------------------------------
-def _ransac_pair(samples, solve, mask_of, refit, min_valid: int, min_refit: int, refits: int, drop_worse: bool):
+def _ransac_pair(samples, solve, mask_of, refit, min_valid: int, min_refit: int, refits: int, drop_worse: bool,
+                 refit_from_model: bool = False):
     """One pair's RANSAC -> (model, mask, the winning hypothesis), or None where the winner has fewer than min_valid
     inliers. samples: the table, a row a hypothesis; solve(sample): its candidates in scoring order; mask_of(model): the
     inliers [n] bool; refit(mask): a model or None. The winner is the highest count, strictly: the first hypothesis,
     then the first candidate, among equals. Then `refits` rounds over the current inliers: a round with fewer than
-    min_refit of them, or without a model, ends them; with drop_worse so does one whose model counts fewer."""
+    min_refit of them, or without a model, ends them; with drop_worse so does one whose model counts fewer. With
+    refit_from_model the refit is iterative and starts at the current model: refit(mask, model)."""
     best_n, best_h, best_m = -1, -1, None
     for h, sample in enumerate(samples):
         for m in solve(sample):
@@ -780,7 +826,7 @@ def _ransac_pair(samples, solve, mask_of, refit, min_valid: int, min_refit: int,
     for _ in range(int(refits)):
         if int(mask.sum()) < min_refit:
             break
-        again = refit(mask)
+        again = refit(mask, m) if refit_from_model else refit(mask)
         if again is None:
             break
         mask_again = mask_of(again)
@@ -890,3 +936,216 @@ def essential_reference(matches, counts, kpts0, kpts1, intrinsics, threshold: fl
         out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
         out.num_inliers[p], out.num_front[p], out.valid[p], out.best[p] = int(mask.sum()), front, 1, best_h
     return out
+
+
+# ---- the absolute pose in float64 ----------------------------------------------------------------------------------------
+def _camera_ok(k: np.ndarray) -> bool:
+    return bool(np.isfinite(k).all() and (k[:2] > 0).all())
+
+
+def _reproject(r: np.ndarray, t: np.ndarray, pts: np.ndarray, img: np.ndarray, k: np.ndarray) -> np.ndarray:
+    with np.errstate(all="ignore"):
+        c = pts @ r.T + t
+        err = (k[0] * c[:, 0] / c[:, 2] + k[2] - img[:, 0]) ** 2 + (k[1] * c[:, 1] / c[:, 2] + k[3] - img[:, 1]) ** 2
+        return np.where(c[:, 2] > 0, err, np.inf)
+
+
+def reprojection_error(R, t, X, x, intrinsics) -> torch.Tensor:
+    """The error of each 2D-3D correspondence (X [n, 3], x [n, 2] in pixels) under the pose (R [3, 3], t [3]:
+    X_c = R X + t) and the camera intrinsics [4] = (fx, fy, cx, cy), in squared pixels, float64 [n]:
+    (fx X_c / Z_c + cx - x)² + (fy Y_c / Z_c + cy - y)², +inf at a depth Z_c <= 0. An inlier has error <= threshold²; a NaN
+    (a non-finite coordinate) is none."""
+    return torch.from_numpy(_reproject(_np(R).reshape(3, 3), _np(t).reshape(3), _np(X).reshape(-1, 3), _np(x).reshape(-1, 2),
+                                       _np(intrinsics).reshape(4)))
+
+
+class Solve3(NamedTuple):
+    """R [n, 3, 3], t [n, 3] float64: the candidates in ascending |R X_s0 + t|; roots: the quartic's four complex roots
+    (fewer where its leading coefficients vanish); area: the sample triangle's area over its longest side squared."""
+    R: np.ndarray
+    t: np.ndarray
+    roots: np.ndarray
+    area: float
+
+
+def _absolute_orientation(a: np.ndarray, b: np.ndarray):
+    """(R, t) with b ~ R a + t for point sets [n, 3], det R = +1 (Kabsch / Umeyama without scale, by SVD)."""
+    ca, cb = a.mean(0), b.mean(0)
+    u, _, vt = np.linalg.svd((b - cb).T @ (a - ca))
+    d = np.diag([1.0, 1.0, np.sign(np.linalg.det(u @ vt))])
+    r = u @ d @ vt
+    return r, cb - r @ ca
+
+
+def solve3_reference(points, image, intrinsics, sample) -> Solve3:
+    """The P3P solve of the contract in float64: points [n, 3], image [n, 2] (pixels) all correspondences of the pair,
+    intrinsics [4], sample 3 indices. Bearings f_i: the unit vectors of ((x - cx) / fx, (y - cy) / fy, 1). With the
+    camera distances s1, s2 = u s1, s3 = v s1 and the law of cosines on the three sides, Grunert's quartic in u by
+    generic polynomial products, its roots by numpy.roots; for each real root u > 0 the two v of the quadratic
+    v² - 2 c13 v + 1 - E q(u) = 0, the one that fits the third side better, (u, v) then polished by three Newton steps on the
+    two conics; s1 = |X1 - X2| / sqrt(q(u)); the pose by an SVD
+    absolute orientation of the three camera points s_i f_i onto the map points. Deliberately not the kernel's
+    bracketed root finding, rational v and triangle frames. No candidate: anything non-finite, a sample triangle whose
+    area over its longest side squared is below AREA_EPS, u or v <= 0, or a sample point at depth <= 0 under the
+    candidate. The candidates are in ascending |R X_s0 + t|."""
+    pts, img, k = _np(points).reshape(-1, 3), _np(image).reshape(-1, 2), _np(intrinsics).reshape(4)
+    idx = np.asarray(sample, dtype=np.int64).reshape(3)
+    x, px = pts[idx], img[idx]
+    none = Solve3(np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros((0,), dtype=complex), float("nan"))
+    with np.errstate(all="ignore"):
+        f = np.concatenate([(px - k[2:4]) / k[0:2], np.ones((3, 1))], 1)
+        f = f / np.linalg.norm(f, axis=1, keepdims=True)
+        sides = np.array([((x[1] - x[0]) ** 2).sum(), ((x[2] - x[0]) ** 2).sum(), ((x[2] - x[1]) ** 2).sum()])
+        area = 0.5 * np.linalg.norm(np.cross(x[1] - x[0], x[2] - x[0])) / sides.max()
+    if not (np.isfinite(f).all() and np.isfinite(x).all() and np.isfinite(area)):
+        return none
+    if not area >= AREA_EPS:
+        return Solve3(none.R, none.t, none.roots, float(area))
+    c12, c13, c23 = float(f[0] @ f[1]), float(f[0] @ f[2]), float(f[1] @ f[2])
+    ee, ff = sides[1] / sides[0], sides[2] / sides[0]
+    q = np.array([1.0, -2.0 * c12, 1.0])                      # q(u), highest power first
+    n = np.polyadd(np.array([1.0, 0.0, -1.0]), (ee - ff) * q)  # N(u)
+    d = np.array([2.0 * c23, -2.0 * c13])                     # D(u)
+    quartic = np.polyadd(np.polysub(np.polymul(n, n), 2.0 * c13 * np.polymul(n, d)),
+                         np.polymul(np.polysub([1.0], ee * q), np.polymul(d, d)))
+    if not np.isfinite(quartic).all():
+        return Solve3(none.R, none.t, none.roots, float(area))
+    roots = np.roots(quartic).astype(complex)
+    cands = []
+    for z in roots:
+        if abs(z.imag) > 1e-9 * max(1.0, abs(z)) or not z.real > 0.0:
+            continue
+        u = float(z.real)
+        qu = 1.0 - 2.0 * c12 * u + u * u
+        disc = c13 * c13 - (1.0 - ee * qu)
+        both = [c13 + sg * np.sqrt(max(disc, 0.0)) for sg in (1.0, -1.0)]
+        v = min(both, key=lambda w: abs(w * w - 2.0 * c23 * u * w + u * u - ff * qu))
+        for _ in range(3):  # Newton on the two conics in (u, v): the square root loses digits where the two v are close
+            qu, dq = 1.0 - 2.0 * c12 * u + u * u, 2.0 * u - 2.0 * c12
+            fa, fb = v * v - 2.0 * c13 * v + 1.0 - ee * qu, v * v - 2.0 * c23 * u * v + u * u - ff * qu
+            jac = np.array([[-ee * dq, 2.0 * v - 2.0 * c13], [-2.0 * c23 * v + 2.0 * u - ff * dq, 2.0 * v - 2.0 * c23 * u]])
+            with np.errstate(all="ignore"):
+                try:
+                    step = np.linalg.solve(jac, [fa, fb])
+                except np.linalg.LinAlgError:
+                    break
+            if not np.isfinite(step).all():
+                break
+            u, v = u - step[0], v - step[1]
+        qu = 1.0 - 2.0 * c12 * u + u * u
+        with np.errstate(all="ignore"):
+            s1 = np.sqrt(sides[0] / qu)
+            y = np.array([s1, u * s1, v * s1])[:, None] * f
+        if not (v > 0.0 and np.isfinite(y).all()):
+            continue
+        r, t = _absolute_orientation(x, y)
+        if not (np.isfinite(r).all() and np.isfinite(t).all() and ((x @ r.T + t)[:, 2] > 0).all()):
+            continue
+        cands.append((float(np.linalg.norm(r @ x[0] + t)), r, t))
+    cands.sort(key=lambda c: c[0])
+    return Solve3(np.array([c[1] for c in cands]).reshape(-1, 3, 3), np.array([c[2] for c in cands]).reshape(-1, 3), roots,
+                  float(area))
+
+
+def absolute_refit_reference(R, t, X, x, intrinsics):
+    """One refit round of the absolute pose's contract in float64, run to convergence: from the pose (R, t) over the
+    given correspondences (X [n, 3], x [n, 2]: the round's current inliers) -> (R, t), or None. The fixed set is the rows
+    with a finite residual at a positive depth under the given pose; with fewer than 3 of them, or a pose that is not
+    finite, there is no refit. Else Σ squared reprojection error in px² over the fixed set is minimised by
+    scipy.optimize.least_squares(method="lm") at its tolerance floor over a global rotation vector and t with a numeric
+    Jacobian (not the kernel's route: a local rotation, an analytic Jacobian and a fixed number of rounds); the given
+    pose comes back where the minimiser's cost is not below it."""
+    from scipy.optimize import least_squares
+    from scipy.spatial.transform import Rotation
+
+    r, t = _np(R).reshape(3, 3), _np(t).reshape(3)
+    pts, img, k = _np(X).reshape(-1, 3), _np(x).reshape(-1, 2), _np(intrinsics).reshape(4)
+    if not (np.isfinite(r).all() and np.isfinite(t).all()):
+        return None
+    rows = np.isfinite(_reproject(r, t, pts, img, k))
+    if int(rows.sum()) < MIN_ABSOLUTE_ROWS:
+        return None
+    pts, img = pts[rows], img[rows]
+
+    def residuals(p):
+        c = pts @ Rotation.from_rotvec(p[:3]).as_matrix().T + p[3:]
+        with np.errstate(all="ignore"):
+            return np.concatenate([k[0] * c[:, 0] / c[:, 2] + k[2] - img[:, 0], k[1] * c[:, 1] / c[:, 2] + k[3] - img[:, 1]])
+
+    rot0 = Rotation.from_matrix(r)  # (the nearest rotation)
+    p0 = np.concatenate([rot0.as_rotvec(), t])
+    cost0 = float((residuals(p0) ** 2).sum())
+    if not np.isfinite(cost0):
+        return None
+    sol = least_squares(residuals, p0, method="lm", xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=4000)
+    cost1 = float((sol.fun ** 2).sum())
+    p1 = sol.x if np.isfinite(cost1) and cost1 < cost0 else p0
+    return Rotation.from_rotvec(p1[:3]).as_matrix(), p1[3:].copy()
+
+
+def absolute_pose_reference(points, image, counts, intrinsics, threshold: float = 3.0, hypotheses: int = 512,
+                            refits: int = 2, seed: int = 888) -> AbsolutePoseResult:
+    """AbsolutePoseRansac(threshold, hypotheses, refits, seed).localize in float64 on the CPU: points [P, Kmax, 3],
+    image [P, Kmax, 2], counts [P], intrinsics [P, 4] -> AbsolutePoseResult (R, t float64). The steps are the header's:
+    ransac_samples3, solve3_reference, every candidate scored by reprojection_error with a positive depth (the winner:
+    the highest count, then the lowest hypothesis, then the candidates' order), `refits` rounds of
+    absolute_refit_reference from the current pose over the current inliers (a round with fewer than 4 stops; a round
+    whose pose counts fewer inliers than the current one is dropped and the rounds stop). A pair with fewer than 4
+    correspondences, or with an intrinsic that is not finite or a focal length <= 0, is invalid."""
+    _check_params(threshold, hypotheses, refits)
+    pr, kmax = int(points.shape[0]), int(points.shape[1])
+    out = _blank(AbsolutePoseResult, pr, kmax, (3, 3), (3,))
+    thr2 = float(threshold) ** 2
+    for p in range(pr):
+        n = min(max(int(counts[p]), 0), kmax)
+        pts, img, kk = _np(points[p])[:n].reshape(-1, 3), _np(image[p])[:n].reshape(-1, 2), _np(intrinsics[p]).reshape(4)
+        if n < MIN_INLIERS_A or not _camera_ok(kk):
+            continue
+
+        def solve(s):
+            got = solve3_reference(pts, img, kk, s)
+            return list(zip(got.R, got.t))
+
+        def mask_of(m):
+            with np.errstate(all="ignore"):
+                return _reproject(m[0], m[1], pts, img, kk) <= thr2
+
+        won = _ransac_pair(ransac_samples3(seed, hypotheses, n).numpy(), solve, mask_of,
+                           lambda mask, m: absolute_refit_reference(m[0], m[1], pts[mask], img[mask], kk),
+                           MIN_INLIERS_A, MIN_INLIERS_A, refits, True, refit_from_model=True)
+        if won is None:
+            continue
+        (r, t), mask, best_h = won
+        out.R[p], out.t[p] = torch.from_numpy(np.array(r)), torch.from_numpy(np.array(t))
+        out.inliers[p, :n] = torch.from_numpy(mask.astype(np.uint8))
+        out.num_inliers[p], out.valid[p], out.best[p] = int(mask.sum()), 1, best_h
+    return out
+
+
+def link_landmarks_reference(matches_a, counts_a, points_a, ok_a, matches_b, counts_b, kpts_b1, side_a: int = 1,
+                             num_shared: int = MAX_POINTS) -> Landmarks:
+    """link_landmarks' contract on the CPU: matches_a [P, Ka, 2], counts_a [P], points_a [P, Ka, 3], ok_a [P, Ka]
+    (triangulate's outputs for pair A), matches_b [P, Kb, 2], counts_b [P], kpts_b1 [P, K1, 2] -> Landmarks. A row r of
+    A below its count with ok_a != 0 owns the shared keypoint matches_a[r, side_a] (clamped into [0, num_shared)), the
+    lowest row where several name one; a row k of B below its count is linked iff its shared keypoint matches_b[k, 0]
+    (clamped) has an owner. The linked rows in ascending k: the owner's point (the same bits), the new image's keypoint
+    kpts_b1[matches_b[k, 1]] (clamped), and k; zeros and -1 past their number."""
+    ma, mb = np.asarray(matches_a).astype(np.int64), np.asarray(matches_b).astype(np.int64)
+    pa, oka, kb1 = np.asarray(points_a), np.asarray(ok_a), np.asarray(kpts_b1)
+    pr, ka, kb = ma.shape[0], ma.shape[1], mb.shape[1]
+    points, image = np.zeros((pr, kb, 3), dtype=pa.dtype), np.zeros((pr, kb, 2), dtype=kb1.dtype)
+    rows, n = np.full((pr, kb), -1, dtype=np.int32), np.zeros((pr,), dtype=np.int32)
+    for p in range(pr):
+        owner = {}
+        for r in range(min(max(int(counts_a[p]), 0), ka)):
+            if oka[p, r]:
+                owner.setdefault(int(np.clip(ma[p, r, int(side_a)], 0, int(num_shared) - 1)), r)
+        pos = 0
+        for k in range(min(max(int(counts_b[p]), 0), kb)):
+            r = owner.get(int(np.clip(mb[p, k, 0], 0, int(num_shared) - 1)))
+            if r is None:
+                continue
+            points[p, pos], image[p, pos], rows[p, pos] = pa[p, r], kb1[p, int(np.clip(mb[p, k, 1], 0, kb1.shape[1] - 1))], k
+            pos += 1
+        n[p] = pos
+    return Landmarks(torch.from_numpy(points), torch.from_numpy(image), torch.from_numpy(rows), torch.from_numpy(n))

@@ -30,7 +30,10 @@ the call's own pose at N rounds and at 1 round (added_us: the medians' differenc
 per_round_us: the hook's (N rounds - 1 round) / (N - 1); hook_one_round_us holds the launch, the staging, the first
 pass, the mask and the outputs). Written to profiles/geometry/ab_polish.jsonl unless --out is given.
 
-    python tools/geometry_ab.py [--model fundamental|homography|essential] [--repeats 5] [--part all|verify|pipeline]
+--model absolute: AbsolutePoseRansac.localize on absolute_scene's 2D-3D correspondences: the whole call, the call
+without refits, lg_ransac_solve3 alone and lg_link_landmarks, all by graph replay (-> ab_absolute.jsonl).
+
+    python tools/geometry_ab.py [--model fundamental|homography|essential|absolute] [--repeats 5] [--part all|verify|pipeline]
                                 [--polish N] [--out profiles/geometry/ab.jsonl]
 """
 import argparse
@@ -229,12 +232,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--polish", type=int, default=0, help="with --model essential: the A/B of verify at polish 0 and N")
     ap.add_argument("--part", choices=("all", "verify", "pipeline"), default="all")
-    ap.add_argument("--model", choices=("fundamental", "homography", "essential"), default="fundamental")
+    ap.add_argument("--model", choices=("fundamental", "homography", "essential", "absolute"), default="fundamental")
     args = ap.parse_args()
     if args.polish and args.model != "essential":
         sys.exit("geometry_ab.py: --polish goes with --model essential")
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "geometry", "ab_polish.jsonl" if args.polish else "ab.jsonl")
+        name = "ab_polish.jsonl" if args.polish else ("ab_absolute.jsonl" if args.model == "absolute" else "ab.jsonl")
+        args.out = os.path.join(REPO, "profiles", "geometry", name)
     if not torch.cuda.is_available():
         sys.exit("geometry_ab.py: needs a GPU (timings from anywhere else mean nothing)")
     dev = torch.device("cuda:0")
@@ -251,6 +255,9 @@ def main():
     fr = FundamentalRansac(THR, H, R, SEED)
     if args.model == "homography":
         homography_part(args, dev, stream, base, emit, fr)
+        return
+    if args.model == "absolute":
+        absolute_part(args, dev, stream, base, emit)
         return
     if args.model == "essential":
         if args.polish:
@@ -416,6 +423,50 @@ def polish_part(args, dev, stream, base, emit):
                 rec.update(verify_us=spread(times[0]), verify_polish_us=spread(times[1]), hook_us=spread(times[2]),
                            hook_one_round_us=spread(times[3]), added_us=round(med[1] - med[0], 2),
                            per_round_us=round((med[2] - med[3]) / max(n - 1, 1), 2))
+            emit(rec)
+            del graphs
+
+
+def absolute_part(args, dev, stream, base, emit):
+    """AbsolutePoseRansac.localize on absolute_scene's correspondences: the whole call, the call without refits, the
+    P3P solve alone (lg_ransac_solve3 on the call's own samples) and lg_link_landmarks on a full pair."""
+    from lightglue_amd import AbsolutePoseRansac, absolute_scene, link_landmarks, ransac_samples3
+
+    full, bare = AbsolutePoseRansac(THR, H, R, SEED), AbsolutePoseRansac(THR, H, 0, SEED)
+    for k in (256, 1024, 2048):
+        pts, kp, gt, kk, _, _ = absolute_scene(k, k, 0.25, 0.25)
+        samples = ransac_samples3(SEED, H, k).to(dev)
+        for pr in (1, 16):
+            x, px = pts.to(dev)[None].repeat(pr, 1, 1).contiguous(), kp.to(dev)[None].repeat(pr, 1, 1).contiguous()
+            counts = torch.full((pr,), k, dtype=torch.int32, device=dev)
+            intr = torch.tensor([kk[0, 0], kk[1, 1], kk[0, 2], kk[1, 2]], dtype=torch.float32, device=dev)[None].repeat(pr, 1).contiguous()
+            cand = torch.empty((pr, H, 4, 12), dtype=torch.float32, device=dev)
+            num = torch.empty((pr, H), dtype=torch.int32, device=dev)
+            m = torch.arange(k, dtype=torch.int32, device=dev)[None, :, None].repeat(pr, 1, 2).contiguous()
+            res = MatchResult(None, None, None, None, m, None, counts)
+            ok = torch.ones((pr, k), dtype=torch.uint8, device=dev)
+
+            def solve():
+                call("lg_ransac_solve3", x.data_ptr(), px.data_ptr(), counts.data_ptr(), intr.data_ptr(), pr, k, samples.data_ptr(), H,
+                     cand.data_ptr(), num.data_ptr(), torch.cuda.current_stream().cuda_stream)
+
+            with torch.no_grad():
+                ours = lambda: full.localize(x, px, counts, intr)                       # noqa: E731
+                norefit = lambda: bare.localize(x, px, counts, intr)                    # noqa: E731
+                link = lambda: link_landmarks(res, x, ok, res, px, side_a=1, num_shared=k)  # noqa: E731
+                mine, marks = ours(), link()
+                torch.cuda.synchronize()
+                rec = dict(base, part="localize", model="absolute", K=k, P=pr,
+                           ours_mask_is_gt=bool((mine.inliers.bool().cpu() == gt[None]).all()), linked=int(marks.counts[0]))
+                graphs = [graph_of(f, stream, CALLS) for f in (ours, norefit, solve, link)]
+                times = [[], [], [], []]
+                for _ in range(args.repeats):
+                    for g, t in zip(graphs, times):
+                        t.append(time_graph(g, stream, CALLS))
+                med = [statistics.median(t) for t in times]
+                rec.update(localize_us=spread(times[0]), localize_no_refits_us=spread(times[1]), solve3_us=spread(times[2]),
+                           link_us=spread(times[3]), refits_add_us=round(med[0] - med[1], 2),
+                           localize_eager_us=round(time_eager(ours, 50), 2), candidates_per_hypothesis=round(float(num.float().mean()), 2))
             emit(rec)
             del graphs
 
