@@ -754,6 +754,56 @@ int32_t lg_ransac_score_absolute(const float* points, const float* image, const 
                                  int32_t pairs, int32_t kmax, const float* poses, int32_t num_poses, float threshold,
                                  int32_t* inlier_counts, hipStream_t stream);
 
+/* The bundle adjustment (csrc/lightglue_bundle.hip): every call above fits one pair, or one camera against points held
+ * fixed; lg_bundle_adjust refines the poses of the views of a window and its landmarks together, so the error of the
+ * first pair's map no longer passes down a sequence. New symbols only: LG_GLUE_ABI_VERSION stays 4. The general
+ * statements of lg_ransac_fundamental hold (arguments checked before any device call, a no-op for windows == 0, counts
+ * clamped, no floating-point atomic, no allocation, no host synchronisation, every output entry written).
+ * lightglue_amd/geometry_contract.py restates the contract in float64 by another route (bundle_adjust_reference: scipy's
+ * sparse least squares to convergence over global rotation vectors; the converged minimiser is what is compared).
+ *
+ * A window is `views` views (2 .. 8) of up to lmax landmarks (1 .. 2048); view 0 is the frame, R0 = I and t0 = 0, and
+ * X_c = R_v X + t_v. Inputs: obs [windows, views, lmax, 2] fp32 (pixels); seen [windows, views, lmax] uint8 (non-zero:
+ * landmark l is observed in view v); counts [windows] int32 (clamped into [0, lmax]); intrinsics [windows, views, 4] fp32
+ * (fx, fy, cx, cy); r [windows, views, 3, 3], t [windows, views, 3] fp32, whose entry 0 is not read; points
+ * [windows, lmax, 3] fp32 in view 0's frame; iterations in [1, 32]; windows <= 65,535. Every pointer 4-B aligned, the
+ * workspace 16-B. Per window:
+ *   1. The fixed set: the observations (v, l) with seen != 0 and l below the count whose residual (step 2) under the
+ *      entering state is finite at a positive depth; a landmark is live with at least 2 of them, and one that is not
+ *      drops its observations from the set and keeps its point (the same bits). The entering rotations take the polar
+ *      Newton step of lg_pose_polish. The window is passed through (step 5) where an intrinsic is not finite or a focal
+ *      length <= 0, a view from 1 on has fewer than 4 observations in the set, a pose is not finite, or t1 = 0.
+ *   2. The residual of an observation, fp64, in pixels: (fx X_c / Z_c + cx - x, fy Y_c / Z_c + cy - y). The cost is Σ r²
+ *      over the fixed set, which does not change during the rounds.
+ *   3. Parameters: view 0 none; view 1 five, (ω, τ1, τ2): R <- exp([ω]x) R and t1's direction takes lg_pose_polish's
+ *      tangent-plane step while its length stays the entering |t1| (the scale gauge: the map keeps its scale); a view
+ *      from 2 on six, (ω, δt), as lg_ransac_absolute's refit; a live landmark three. 6 views - 7 camera parameters, at
+ *      most 41. The Jacobians are analytic.
+ *   4. `iterations` rounds of Levenberg-Marquardt by the Schur complement. Per landmark V_l = Σ J_xᵀ J_x and g_l, per
+ *      (view, landmark) W_vl = J_cᵀ J_x, per view U_v and g_c; damped as elsewhere, (. + λ diag .), λ = 1e-3 at first;
+ *      S = U* - Σ_l W_l V_l*⁻¹ W_lᵀ, the right side -(g_c - Σ_l W_l V_l*⁻¹ g_l), S δc = the right side by an fp64
+ *      Cholesky, δx_l = -V_l*⁻¹ (g_l + W_lᵀ δc). A pivot that is not positive or not finite, of a V_l* or of S, rejects
+ *      the round. The trial is accepted iff its cost is finite and below the current cost; then λ <- max(λ / 10, 1e-12),
+ *      else λ <- min(10 λ, 1e12). The set is fixed: a trial that moves a point behind a camera is accepted like any
+ *      other if its cost is finite and lower. The whole workgroup takes each decision from the same bits, read from
+ *      ordered reductions; the result does not depend on the schedule. No loop's length depends on the data: the
+ *      passes run over lmax landmarks, the solve over the 6 views - 7 columns, the rounds over `iterations`.
+ *   5. Where a round was accepted and the refined poses and live points are finite in fp32, kept = 1: the poses rounded to fp32, entry 0 the identity and zeros, the live points
+ *      refined and the others as given. Else the pass-through, kept = 0: poses and points as given (the same bits),
+ *      entry 0 still the identity and zeros.
+ * Outputs: r_out, t_out, points_out as the inputs' shapes; cost [windows, 2] fp32: the entering and the final Σ r² in
+ * px² (equal on pass-through; zeros where the cost was never taken: bad intrinsics, a pose that is not finite, t1 = 0);
+ * num_obs [windows] int32: the size of the fixed set (0 where it was never formed); kept [windows] int32. One launch,
+ * one workgroup of 256 threads per window; the Schur product runs on v_mfma_f64_16x16x4_f64. The workspace holds the
+ * points and the trial points in fp64: lg_bundle_adjust_workspace bytes (0 for arguments out of range). The outputs may
+ * not alias the inputs. Not built: a robust loss (the fixed set is the robustness, as in the polish), recomputed inlier
+ * masks, refined intrinsics, more than 8 views, a map across calls. */
+size_t lg_bundle_adjust_workspace(int32_t windows, int32_t views, int32_t lmax);
+int32_t lg_bundle_adjust(const float* obs, const uint8_t* seen, const int32_t* counts, const float* intrinsics, const float* r,
+                         const float* t, const float* points, int32_t windows, int32_t views, int32_t lmax, int32_t iterations,
+                         void* workspace, size_t workspace_bytes, float* r_out, float* t_out, float* points_out, float* cost,
+                         int32_t* num_obs, int32_t* kept, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

@@ -217,6 +217,9 @@ SIGNATURES.update({
     "lg_ransac_samples3": ([_I, _I, _I, _P, _P], _I),
     "lg_ransac_solve3": ([_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P], _I),
     "lg_ransac_score_absolute": ([_P, _P, _P, _P, _I, _I, _P, _I, ctypes.c_float, _P, _P], _I),
+    # the bundle adjustment (csrc/lightglue_bundle.hip)
+    "lg_bundle_adjust_workspace": ([_I, _I, _I], _S),
+    "lg_bundle_adjust": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _S, _P, _P, _P, _P, _P, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -24,6 +24,9 @@ for one pair onto the match rows of the next pair that shares an image with it, 
 result's mask back onto those rows: EssentialRansac(polish=N).verify -> triangulate -> link_landmarks ->
 localize_landmarks gives the next frame a pose in the first pair's frame at the first pair's scale.
 
+``BundleAdjust.refine`` (csrc/lightglue_bundle.hip) refines the poses of the views of a window and its landmarks together:
+Levenberg-Marquardt over Σ squared reprojection error by the Schur complement, whose product runs on the fp64 MFMA.
+
 This module is the kernel side only. What each call computes is pinned in float64 in geometry_contract.py, and the
 synthetic pairs of the tests are in geometry_scenes.py; both are re-exported here.
 """
@@ -40,8 +43,8 @@ from .geometry_contract import (  # noqa: F401  (the public names this module ha
     essential_to_fundamental, fundamental_refit, gather_correspondences, homography_reference, homography_refit,
     polish_pose_reference, polish_reference, pose_candidates, pose_from_essential_reference, ransac_reference, ransac_samples,
     ransac_samples3, ransac_samples5, reprojection_error, rotation_angle_deg, sampson_error, solve4_reference, solve5_reference, solve7_reference, transfer_error,
-    triangulate_reference, absolute_pose_reference, absolute_refit_reference, link_landmarks_reference, solve3_reference, Solve3)
-from .geometry_scenes import (ThreeViews, absolute_scene, calibrated_planar_scene, calibrated_scene, planar_scene,  # noqa: F401
+    triangulate_reference, BundleResult, MAX_BUNDLE, MAX_VIEWS, bundle_adjust_reference, bundle_fixed_set, absolute_pose_reference, absolute_refit_reference, link_landmarks_reference, solve3_reference, Solve3)
+from .geometry_scenes import (MultiViews, ThreeViews, absolute_scene, multi_view_scene, calibrated_planar_scene, calibrated_scene, planar_scene,  # noqa: F401
                               three_view_scene, two_view_scene)
 from .image import ImageInput, match_source_images
 from .matches import MatchResult
@@ -323,6 +326,94 @@ class AbsolutePoseRansac(_Ransac):
 
     def verify(self, *args, **kwargs):
         raise TypeError("AbsolutePoseRansac has no verify: its inputs are 2D-3D correspondences (localize, localize_landmarks)")
+
+
+# ---- the bundle adjustment ----------------------------------------------------------------------------------------------
+class BundleAdjust:
+    """Bundle adjustment over a window of V views (2 .. 8) of up to Lmax landmarks (1 .. 2048), view 0 the frame
+    (csrc/lightglue_bundle.hip): `iterations` rounds in [1, 32] of Levenberg-Marquardt over Σ squared reprojection error in
+    px² on the poses of the views from 1 on (|t1| keeps its entering length: the scale gauge) and the landmarks seen at
+    least twice, by the Schur complement on the cameras. refine -> BundleResult."""
+
+    def __init__(self, iterations: int = 10) -> None:
+        if not 1 <= int(iterations) <= MAX_BUNDLE:
+            raise ValueError(f"iterations must be in [1, {MAX_BUNDLE}], got {iterations}")
+        self.iterations = int(iterations)
+
+    def refine(self, obs: torch.Tensor, seen: torch.Tensor, counts: torch.Tensor, intrinsics: torch.Tensor, R: torch.Tensor,
+               t: torch.Tensor, points: torch.Tensor) -> BundleResult:
+        """obs [B, V, Lmax, 2] fp32 (pixels), seen [B, V, Lmax] uint8 (non-zero: landmark l is observed in view v), counts
+        [B] int32 (clamped, never trusted), intrinsics [B, V, 4] fp32 (fx, fy, cx, cy), R [B, V, 3, 3] and t [B, V, 3] fp32
+        (X_c = R_v X + t_v; entry 0 is not read: view 0 is the frame), points [B, Lmax, 3] fp32 -> BundleResult. One launch
+        on the current stream, one workgroup per window, nothing read back."""
+        for name, x, dt, nd in (("obs", obs, torch.float32, 4), ("seen", seen, torch.uint8, 3), ("counts", counts, torch.int32, 1),
+                                ("intrinsics", intrinsics, torch.float32, 3), ("R", R, torch.float32, 4), ("t", t, torch.float32, 3),
+                                ("points", points, torch.float32, 3)):
+            require_gpu(name, x, _STAGE, (dt,), nd)
+        bw, views, lmax = int(obs.shape[0]), int(obs.shape[1]), int(obs.shape[2])
+        if obs.shape[3] != 2 or not 2 <= views <= MAX_VIEWS or not 1 <= lmax <= MAX_POINTS:
+            raise ValueError(f"obs: expected [B, V, Lmax, 2] with 2 <= V <= {MAX_VIEWS} and 1 <= Lmax <= {MAX_POINTS}, got {tuple(obs.shape)}")
+        for name, x, shape in (("seen", seen, (bw, views, lmax)), ("counts", counts, (bw,)), ("intrinsics", intrinsics, (bw, views, 4)),
+                               ("R", R, (bw, views, 3, 3)), ("t", t, (bw, views, 3)), ("points", points, (bw, lmax, 3))):
+            _like_matches(name, x, shape, obs)
+        obs, seen, counts, intrinsics, R, t, points = (x.contiguous() for x in (obs, seen, counts, intrinsics, R, t, points))
+        dev = obs.device
+        out = BundleResult(torch.empty((bw, views, 3, 3), dtype=torch.float32, device=dev),
+                           torch.empty((bw, views, 3), dtype=torch.float32, device=dev),
+                           torch.empty((bw, lmax, 3), dtype=torch.float32, device=dev),
+                           torch.empty((bw, 2), dtype=torch.float32, device=dev), torch.empty((bw,), dtype=torch.int32, device=dev),
+                           torch.empty((bw,), dtype=torch.int32, device=dev))
+        if bw == 0:
+            return out
+        stream = stream_of(obs)
+        nbytes = int(_lib.load().lg_bundle_adjust_workspace(bw, views, lmax))
+        ws, = carve(dev, stream, [nbytes])
+        call("lg_bundle_adjust", obs.data_ptr(), seen.data_ptr(), counts.data_ptr(), intrinsics.data_ptr(), R.data_ptr(), t.data_ptr(),
+             points.data_ptr(), bw, views, lmax, self.iterations, ws.data_ptr(), nbytes, *(x.data_ptr() for x in out), stream)
+        return out
+
+
+def window_from_chain(result_a: MatchResult, result_b: MatchResult, kpts0: torch.Tensor, kpts1: torch.Tensor, kpts2: torch.Tensor,
+                      pose, points: torch.Tensor, ok: torch.Tensor, landmarks: Landmarks, absolute: AbsolutePoseResult,
+                      on_b: torch.Tensor):
+    """The three-view window of the chain EssentialRansac(polish).verify -> triangulate -> link_landmarks ->
+    localize_landmarks -> inliers_on_matches, as BundleAdjust.refine's arguments without the intrinsics: (obs [P, 3, Ka, 2],
+    seen [P, 3, Ka] uint8, counts [P] int32, R [P, 3, 3, 3], t [P, 3, 3], points [P, Ka, 3]). A landmark is a row of pair A
+    (result_a over kpts0, kpts1; `pose`, `points`, `ok` its pose and triangulate's outputs); it is seen in views 0 and 1 where
+    the row is below the count, an inlier of `pose` and ok, and in view 2 where it also owns its keypoint of the shared image
+    (the lowest such row, link_landmarks' rule) and a row of pair B (result_b over kpts1, kpts2; the lowest) with on_b != 0
+    names that keypoint. View 2's pose is `absolute`'s; `landmarks` gives pair B's width. Framework ops on the inputs' device:
+    two owner tables over the shared image by scatter_reduce(amin), then gathers; nothing is read back."""
+    ma, mb = result_a.matches.long(), result_b.matches.long()
+    pr, ka, kb, k1 = ma.shape[0], ma.shape[1], mb.shape[1], kpts1.shape[1]
+    if tuple(on_b.shape) != (pr, kb) or tuple(landmarks.rows.shape) != (pr, kb) or tuple(points.shape) != (pr, ka, 3):
+        raise ValueError(f"window_from_chain: on_b and the landmarks [{pr}, {kb}], points [{pr}, {ka}, 3]; got {tuple(on_b.shape)}, "
+                         f"{tuple(landmarks.rows.shape)}, {tuple(points.shape)}")
+    dev = ma.device
+    none = max(ka, kb)
+    rows_a, rows_b = torch.arange(ka, device=dev).expand(pr, ka), torch.arange(kb, device=dev).expand(pr, kb)
+    ca, cb = result_a.counts.clamp(0, ka).long()[:, None], result_b.counts.clamp(0, kb).long()[:, None]
+    in_a = (rows_a < ca) & (pose.inliers != 0) & (ok != 0)
+    shared_a = ma[..., 1].clamp(0, k1 - 1)
+    shared_b = mb[..., 0].clamp(0, k1 - 1)
+    owner_a = torch.full((pr, k1), none, dtype=torch.long, device=dev).scatter_reduce(
+        1, shared_a, torch.where((rows_a < ca) & (ok != 0), rows_a, none), "amin")
+    owner_b = torch.full((pr, k1), none, dtype=torch.long, device=dev).scatter_reduce(
+        1, shared_b, torch.where((rows_b < cb) & (on_b != 0), rows_b, none), "amin")
+    row_b = owner_b.gather(1, shared_a)
+    in_2 = in_a & (owner_a.gather(1, shared_a) == rows_a) & (row_b < none)
+    new_kp = mb[..., 1].gather(1, row_b.clamp(max=kb - 1)).clamp(0, kpts2.shape[1] - 1)
+
+    def pixels(kpts, index):
+        return kpts.gather(1, index[..., None].expand(pr, ka, 2))
+
+    obs = torch.stack([pixels(kpts0, ma[..., 0].clamp(0, kpts0.shape[1] - 1)), pixels(kpts1, shared_a), pixels(kpts2, new_kp)], 1)
+    obs = torch.where(torch.stack([in_a, in_a, in_2], 1)[..., None], obs, torch.zeros_like(obs))
+    seen = torch.stack([in_a, in_a, in_2], 1).to(torch.uint8)
+    eye = torch.eye(3, dtype=pose.R.dtype, device=dev).expand(pr, 3, 3)
+    r = torch.stack([eye, pose.R, absolute.R.to(pose.R.dtype)], 1)
+    t = torch.stack([torch.zeros_like(pose.t), pose.t, absolute.t.to(pose.t.dtype)], 1)
+    return obs.contiguous(), seen.contiguous(), result_a.counts.clamp(0, ka).to(torch.int32), r.contiguous(), t.contiguous(), points.contiguous()
 
 
 def inliers_on_matches(landmarks: Landmarks, result: AbsolutePoseResult, kmax_b: int) -> torch.Tensor:

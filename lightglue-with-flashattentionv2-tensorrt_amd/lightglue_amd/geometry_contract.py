@@ -121,6 +121,18 @@ class AbsolutePoseResult(NamedTuple):
     best: torch.Tensor
 
 
+class BundleResult(NamedTuple):
+    """R [B, V, 3, 3] and t [B, V, 3] (X_c = R_v X + t_v; entry 0 the identity and zeros), points [B, Lmax, 3] in view 0's
+    frame, cost [B, 2] (the entering and the final Σ r² in px² over the fixed set), num_obs [B] int32 (the size of the
+    fixed set), kept [B] int32 (1: refined; 0: poses and points as given)."""
+    R: torch.Tensor
+    t: torch.Tensor
+    points: torch.Tensor
+    cost: torch.Tensor
+    num_obs: torch.Tensor
+    kept: torch.Tensor
+
+
 class Landmarks(NamedTuple):
     """The 2D-3D correspondences link_landmarks makes of two pairs that share an image: points [P, Kmax_b, 3] (pair A's
     3D points), image [P, Kmax_b, 2] (the new image's keypoints, pixels), rows [P, Kmax_b] int32 (the row of pair B's
@@ -1149,3 +1161,109 @@ def link_landmarks_reference(matches_a, counts_a, points_a, ok_a, matches_b, cou
             pos += 1
         n[p] = pos
     return Landmarks(torch.from_numpy(points), torch.from_numpy(image), torch.from_numpy(rows), torch.from_numpy(n))
+
+
+# ---- the bundle adjustment ------------------------------------------------------------------------------------------
+MAX_VIEWS = 8           # views a window
+MAX_BUNDLE = 32         # rounds of the bundle adjustment
+MIN_VIEW_OBS = 4        # a view from 1 on needs as many observations of live landmarks
+
+
+def _bundle_residuals(r, t, pts, obs, k):
+    """[V, L, 2] residuals in px and [V, L] depths of every (view, landmark) under poses r [V, 3, 3], t [V, 3]."""
+    with np.errstate(all="ignore"):
+        c = np.einsum("vij,lj->vli", r, pts) + t[:, None, :]
+        res = np.stack([k[:, None, 0] * c[..., 0] / c[..., 2] + k[:, None, 2] - obs[..., 0],
+                        k[:, None, 1] * c[..., 1] / c[..., 2] + k[:, None, 3] - obs[..., 1]], -1)
+    return res, c[..., 2]
+
+
+def bundle_fixed_set(obs, seen, count, intrinsics, R, t, points):
+    """Step 1 of the bundle adjustment's contract for one window in float64: obs [V, L, 2], seen [V, L], count,
+    intrinsics [V, 4], R [V, 3, 3], t [V, 3] (entry 0 not read), points [L, 3] -> (mask [V, L] bool: the fixed set,
+    usable: False where the window is passed through, residuals [V, L, 2] at the entering state)."""
+    obs, k, r, t, pts = _np(obs), _np(intrinsics), _np(R).copy(), _np(t).copy(), _np(points)
+    views, lmax = obs.shape[0], obs.shape[1]
+    r[0], t[0] = np.eye(3), 0.0
+    usable = bool(np.isfinite(k).all() and (k[:, :2] > 0).all() and np.isfinite(r).all() and np.isfinite(t).all() and t[1].any())
+    if not usable:
+        return np.zeros((views, lmax), dtype=bool), False, np.zeros((views, lmax, 2))
+    r = np.stack([0.5 * m @ (3.0 * np.eye(3) - m.T @ m) for m in r])  # the polar Newton step
+    res, depth = _bundle_residuals(r, t, pts, obs, k)
+    n = min(max(int(count), 0), lmax)
+    mask = (np.asarray(seen.cpu() if isinstance(seen, torch.Tensor) else seen) != 0) & (np.arange(lmax) < n)[None, :]
+    mask &= np.isfinite(res).all(-1) & (depth > 0)
+    mask &= (mask.sum(0) >= 2)[None, :]
+    usable = bool((mask[1:].sum(1) >= MIN_VIEW_OBS).all())
+    return mask, usable, res
+
+
+def bundle_adjust_reference(obs, seen, count, intrinsics, R, t, points) -> BundleResult:
+    """The bundle adjustment's contract for one window in float64, run to convergence by another route:
+    scipy.optimize.least_squares (trf, a sparse 3-point numeric Jacobian by jac_sparsity, tolerances at the floor) over global
+    rotation vectors, t1 as two angles at the entering length, the other t and the live points -> BundleResult without
+    the batch dimension (R, t, points float64). The kernel's route is a local rotation, analytic Jacobians, the Schur
+    complement and a fixed number of rounds; the converged minimiser is what is compared. The given state comes back
+    (kept = 0) where the window is passed through or the minimiser's cost is not below the entering cost."""
+    from scipy.optimize import least_squares
+    from scipy.sparse import lil_matrix
+    from scipy.spatial.transform import Rotation
+
+    mask, usable, res0 = bundle_fixed_set(obs, seen, count, intrinsics, R, t, points)
+    obs_n, k, pts0 = _np(obs), _np(intrinsics), _np(points)
+    r0, t0 = _np(R).copy(), _np(t).copy()
+    views = obs_n.shape[0]
+    r0[0], t0[0] = np.eye(3), 0.0
+    cost0 = float((res0[mask] ** 2).sum()) if mask.any() else 0.0
+    given = BundleResult(torch.from_numpy(r0), torch.from_numpy(t0), torch.from_numpy(pts0.copy()),
+                         torch.tensor([cost0, cost0], dtype=torch.float64), torch.tensor(int(mask.sum()), dtype=torch.int32),
+                         torch.tensor(0, dtype=torch.int32))
+    if not usable or not np.isfinite(cost0):
+        return given
+    live = np.nonzero(mask.any(0))[0]
+    vs, ls = np.nonzero(mask)
+    slot = np.full(obs_n.shape[1], -1)
+    slot[live] = np.arange(len(live))
+    # t1 = s q (sin a cos b, sin a sin b, cos a) with q taking the x axis to the entering direction: (a, b) = (π / 2, 0)
+    scale = float(np.linalg.norm(t0[1]))
+    u = t0[1] / scale
+    axis = np.eye(3)[int(np.argmin(np.abs(u)))]
+    b1 = np.cross(u, axis) / np.linalg.norm(np.cross(u, axis))
+    frame = np.stack([u, b1, np.cross(u, b1)], 1)
+    ncam = 5 + 6 * (views - 2)
+
+    def unpack(p):
+        r, tt = np.empty((views, 3, 3)), np.zeros((views, 3))
+        r[0] = np.eye(3)
+        r[1] = Rotation.from_rotvec(p[:3]).as_matrix()
+        a, b = p[3], p[4]
+        tt[1] = scale * frame @ np.array([np.sin(a) * np.cos(b), np.sin(a) * np.sin(b), np.cos(a)])
+        for v in range(2, views):
+            q = p[5 + 6 * (v - 2):11 + 6 * (v - 2)]
+            r[v], tt[v] = Rotation.from_rotvec(q[:3]).as_matrix(), q[3:]
+        x = pts0.copy()
+        x[live] = p[ncam:].reshape(-1, 3)
+        return r, tt, x
+
+    def residuals(p):
+        r, tt, x = unpack(p)
+        res, _ = _bundle_residuals(r, tt, x, obs_n, k)
+        return res[vs, ls].reshape(-1)
+
+    p0 = np.concatenate([Rotation.from_matrix(r0[1]).as_rotvec(), [np.pi / 2.0, 0.0]] +
+                        [np.concatenate([Rotation.from_matrix(r0[v]).as_rotvec(), t0[v]]) for v in range(2, views)] +
+                        [pts0[live].reshape(-1)])
+    sparsity = lil_matrix((2 * len(vs), len(p0)), dtype=int)
+    for i, (v, l) in enumerate(zip(vs, ls)):
+        if v >= 1:
+            c0 = 0 if v == 1 else 5 + 6 * (v - 2)
+            sparsity[2 * i:2 * i + 2, c0:c0 + (5 if v == 1 else 6)] = 1
+        sparsity[2 * i:2 * i + 2, ncam + 3 * slot[l]:ncam + 3 * slot[l] + 3] = 1
+    sol = least_squares(residuals, p0, method="trf", jac="3-point", jac_sparsity=sparsity, x_scale="jac", xtol=1e-15, ftol=1e-15, gtol=1e-15,
+                        max_nfev=1000)
+    cost1 = float((sol.fun ** 2).sum())
+    if not (np.isfinite(cost1) and cost1 < cost0):
+        return given
+    r, tt, x = unpack(sol.x)
+    return BundleResult(torch.from_numpy(r), torch.from_numpy(tt), torch.from_numpy(x), torch.tensor([cost0, cost1], dtype=torch.float64),
+                        torch.tensor(int(mask.sum()), dtype=torch.int32), torch.tensor(1, dtype=torch.int32))

@@ -4,7 +4,8 @@ that only turns, for the homography), and ``calibrated_scene`` / ``calibrated_pl
 bit with their cameras (K, R, t) for the essential matrix and the pose polish. The errors that place the outliers are
 the float64 contract's (geometry_contract.py). ``absolute_scene`` is a map of 3D points and one camera that sees it (the
 absolute pose), ``three_view_scene`` three cameras in a row and the match rows of the two pairs that share the middle
-one (the chain from a relative pose to the next camera's pose in the first pair's frame)."""
+one (the chain from a relative pose to the next camera's pose in the first pair's frame), ``multi_view_scene`` a window of
+up to 8 cameras in a row with a perturbed start (the bundle adjustment)."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -267,3 +268,72 @@ def three_view_scene(seed: int, k: int, outlier_fraction: float, noise_px: float
     return ThreeViews(as32(k0), as32(k1), as32(k2), rows(order_a), rows(order_b), torch.from_numpy(order_a < n_in),
                       torch.from_numpy(order_b < n_in - n_out), torch.from_numpy(kk), torch.from_numpy(r1), torch.from_numpy(t1),
                       torch.from_numpy(r2), torch.from_numpy(t2))
+
+
+def _rodrigues(w: np.ndarray) -> np.ndarray:
+    """exp([w]x)."""
+    th = np.linalg.norm(w)
+    kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    a, b = (1.0, 0.5) if th == 0 else (np.sin(th) / th, (1.0 - np.cos(th)) / th ** 2)
+    return np.eye(3) + a * kx + b * kx @ kx
+
+
+class MultiViews(NamedTuple):
+    """multi_view_scene's result. obs [V, k, 2] fp32 and seen [V, k] uint8: the observations; K [3, 3]; R [V, 3, 3], t [V, 3]
+    and points [k, 3] float64: the true poses (X_v = R_v X + t_v, view 0 the frame, |t1| = 1) and landmarks; R0, t0, points0
+    fp32: the perturbed start."""
+    obs: torch.Tensor
+    seen: torch.Tensor
+    K: torch.Tensor
+    R: torch.Tensor
+    t: torch.Tensor
+    points: torch.Tensor
+    R0: torch.Tensor
+    t0: torch.Tensor
+    points0: torch.Tensor
+
+
+def multi_view_scene(seed: int, views: int, k: int, noise_px: float, miss_fraction: float, size=(480, 640)) -> MultiViews:
+    """`views` pinhole cameras in a row (size = (h, w), focal length w), each turned and moved sideways from the one before
+    as three_view_scene's are (in smaller steps, so that the last still sees the first's points), the world scaled so that
+    |t1| = 1; k random 3D points seen in view 0, from synth.uniform24. Each projection is moved by at most noise_px; seen is
+    cleared where the point is out of the image or not in front of the camera, and on a hashed miss_fraction of the rest
+    (never in view 0). The start: every pose from 1 on turned by up to 0.01 rad about a seeded axis and shifted by up to
+    0.02 (t1 then back at unit length, so the start's gauge is the truth's), every point moved by up to 0.05."""
+    h, w = int(size[0]), int(size[1])
+    if not 2 <= views <= 8 or k < 1 or noise_px < 0 or not 0.0 <= miss_fraction < 1.0:
+        raise ValueError(f"multi_view_scene: bad views / k / noise_px / miss_fraction {views}, {k}, {noise_px}, {miss_fraction}")
+    u = synth.uniform24(int(seed) + 0xBA5E, 64 * views + (8 + 3 * views) * k).astype(np.float64)
+    cam, u = u[:64 * views].reshape(views, 64), u[64 * views:].reshape(8 + 3 * views, k)
+    kk = np.array([[w, 0.0, w / 2.0], [0.0, w, h / 2.0], [0.0, 0.0, 1.0]])
+    kinv = np.linalg.inv(kk)
+    rs, ts = [np.eye(3)], [np.zeros(3)]
+    for v in range(1, views):
+        ang = (cam[v, :3] - 0.5) * np.array([0.04, 0.04, 0.04]) + np.array([0.0, 0.05, 0.0])
+        step = np.array([-0.5 - 0.2 * cam[v, 3], 0.1 * (cam[v, 4] - 0.5), 0.1 * (cam[v, 5] - 0.5)])
+        cx, cy, cz = np.cos(ang)
+        sx, sy, sz = np.sin(ang)
+        turn = (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @
+                np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]))
+        rs.append(turn @ rs[-1])
+        ts.append(turn @ ts[-1] + step)
+    scale = 1.0 / np.linalg.norm(ts[1])
+    r, t = np.stack(rs), np.stack(ts) * scale
+    p0 = np.stack([u[0] * (w - 1), u[1] * (h - 1)], 1)
+    xyz = (np.concatenate([p0, np.ones((k, 1))], 1) @ kinv.T) * ((4.0 + 8.0 * u[2]) * scale)[:, None]
+    a = noise_px / np.sqrt(2.0)
+    obs, seen = np.zeros((views, k, 2)), np.zeros((views, k), dtype=np.uint8)
+    for v in range(views):
+        p, ok = _inside((xyz @ r[v].T + t[v]) @ kk.T, h, w)
+        miss = (u[3 + v] < miss_fraction) & (v > 0)
+        obs[v] = np.where(ok[:, None], p, 0.0) + (u[3 + views + 2 * v:5 + views + 2 * v].T * 2.0 - 1.0) * a
+        seen[v] = ok & ~miss
+    r0, t0 = r.copy(), t.copy()
+    for v in range(1, views):
+        r0[v] = _rodrigues((cam[v, 8:11] - 0.5) * 0.02 / np.sqrt(3.0) * 2.0) @ r[v]
+        t0[v] = t[v] + (cam[v, 11:14] - 0.5) * 0.04 / np.sqrt(3.0)
+    t0[1] /= np.linalg.norm(t0[1])
+    x0 = xyz + (u[3 + 3 * views:6 + 3 * views].T - 0.5) * 0.1 / np.sqrt(3.0)
+    f32 = lambda m: torch.from_numpy(m.astype(np.float32))  # noqa: E731
+    return MultiViews(f32(obs), torch.from_numpy(seen), torch.from_numpy(kk), torch.from_numpy(r), torch.from_numpy(t),
+                      torch.from_numpy(xyz), f32(r0), f32(t0), f32(x0))

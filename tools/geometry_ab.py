@@ -232,12 +232,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--polish", type=int, default=0, help="with --model essential: the A/B of verify at polish 0 and N")
     ap.add_argument("--part", choices=("all", "verify", "pipeline"), default="all")
-    ap.add_argument("--model", choices=("fundamental", "homography", "essential", "absolute"), default="fundamental")
+    ap.add_argument("--form", choices=("mfma", "fma"), default="mfma", help="with --model bundle: the loaded library's Schur product")
+    ap.add_argument("--model", choices=("fundamental", "homography", "essential", "absolute", "bundle"), default="fundamental")
     args = ap.parse_args()
     if args.polish and args.model != "essential":
         sys.exit("geometry_ab.py: --polish goes with --model essential")
     if args.out is None:
-        name = "ab_polish.jsonl" if args.polish else ("ab_absolute.jsonl" if args.model == "absolute" else "ab.jsonl")
+        name = "ab_polish.jsonl" if args.polish else {"absolute": "ab_absolute.jsonl", "bundle": "ab_bundle.jsonl"}.get(args.model, "ab.jsonl")
         args.out = os.path.join(REPO, "profiles", "geometry", name)
     if not torch.cuda.is_available():
         sys.exit("geometry_ab.py: needs a GPU (timings from anywhere else mean nothing)")
@@ -258,6 +259,9 @@ def main():
         return
     if args.model == "absolute":
         absolute_part(args, dev, stream, base, emit)
+        return
+    if args.model == "bundle":
+        bundle_part(args, dev, stream, emit)
         return
     if args.model == "essential":
         if args.polish:
@@ -425,6 +429,35 @@ def polish_part(args, dev, stream, base, emit):
                            per_round_us=round((med[2] - med[3]) / max(n - 1, 1), 2))
             emit(rec)
             del graphs
+
+
+def bundle_part(args, dev, stream, emit):
+    """BundleAdjust(10).refine on multi_view_scene windows (noise 0.5 px, a fifth of the observations missing) from the
+    perturbed start, by graph replay: V in {3, 8} x L in {256, 1024, 2048} at B = 1 and B = 64. The form of the Schur
+    product is the library's (MHA_HD64_LIB names a `make variant SRC=lightglue_bundle DEFS=-DLG_BA_FMA` build for the other
+    arm, with --form fma, which only labels the record)."""
+    from lightglue_amd import BundleAdjust, multi_view_scene
+
+    form = args.form
+    ba = BundleAdjust(10)
+    for views in (3, 8):
+        for lmax in (256, 1024, 2048):
+            s = multi_view_scene(11, views, lmax, 0.5, 0.2)
+            kk = s.K
+            intr = torch.tensor([kk[0, 0], kk[1, 1], kk[0, 2], kk[1, 2]], dtype=torch.float32).repeat(views, 1)
+            for bw in (1, 64):
+                one = (s.obs, s.seen, torch.tensor(lmax, dtype=torch.int32), intr, s.R0, s.t0, s.points0)
+                a = tuple(x.unsqueeze(0).repeat(bw, *([1] * x.dim())).contiguous().to(dev) for x in one)
+                calls = 4
+                with torch.cuda.stream(stream):
+                    out = ba.refine(*a)
+                torch.cuda.synchronize()
+                g = graph_of(lambda: ba.refine(*a), stream, calls)
+                for _ in range(3):
+                    time_graph(g, stream, calls)
+                t = [time_graph(g, stream, calls) for _ in range(max(args.repeats, 9))]
+                emit(dict(part="refine", model="bundle", form=form, V=views, L=lmax, B=bw, iterations=10, kept=int(out.kept.sum()),
+                          num_obs=int(out.num_obs[0]), refine_us=spread(t), device=torch.cuda.get_device_name(0)))
 
 
 def absolute_part(args, dev, stream, base, emit):
