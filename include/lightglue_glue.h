@@ -804,6 +804,82 @@ int32_t lg_bundle_adjust(const float* obs, const uint8_t* seen, const int32_t* c
                          void* workspace, size_t workspace_bytes, float* r_out, float* t_out, float* points_out, float* cost,
                          int32_t* num_obs, int32_t* kept, hipStream_t stream);
 
+/* The sequence window (csrc/lightglue_window.hip): what turns the matcher's V - 1 consecutive pair results into
+ * lg_bundle_adjust's window, and gives the next frame its 2D-3D rows. lg_link_landmarks only carries the first pair's
+ * points one pair further, so a sequence's map never grows and a point seen in five views is still the midpoint of its
+ * first two rays; here tracks are chained through every shared image and each track's point comes from all of its posed
+ * views. New symbols only: LG_GLUE_ABI_VERSION stays 4. The general statements of lg_link_landmarks' block hold for every
+ * call below: arguments checked before any device call, a no-op for windows == 0, counts and indices never trusted, no
+ * floating-point atomics (lg_window_tracks uses the integer atomicMin in LDS, whose result does not depend on the
+ * order), no allocation, no scratch, no host synchronisation, every output entry written, every loop bounded at compile
+ * time. windows <= 65,535, 2 <= views <= 8, 1 <= lmax <= 2048; every int32 and fp32 pointer 4-B aligned, kpts 8-B. The
+ * outputs may not alias the inputs. lightglue_amd/geometry_contract.py restates the contract (window_tracks_reference:
+ * plain loops over integers; window_points_reference: the fixed-round scheme in float64; window_points_converged:
+ * scipy's least squares per track, another route).
+ *
+ * lg_window_tracks: the matches of V - 1 consecutive pairs to a track table. Pair v is (view v, view v + 1). Inputs:
+ * matches [windows, views - 1, kmax, 2] int32 (column 0 indexes view v's keypoints, column 1 view v + 1's), counts
+ * [windows, views - 1] int32 (clamped into [0, kmax]), mask [windows, views - 1, kmax] uint8 (non-zero: the row counts;
+ * a pose's inliers, or lightglue_amd's inliers_on_matches), kp_counts [windows, views] int32 (the keypoints of each
+ * view, clamped into [0, 2048]); 1 <= kmax <= 2048. Per window:
+ *   1. A row is live iff it is below its count, its mask is non-zero and both its indices are inside their views'
+ *      keypoint counts.
+ *   2. In pair v, keypoint i of view v is owned by the lowest live row naming it in column 0, keypoint j of view v + 1
+ *      by the lowest live row naming it in column 1 (lg_link_landmarks' rule, on both sides).
+ *   3. A link i -> j exists iff one row owns both i and j. A keypoint thus has at most one link out and one in: the
+ *      tracks are simple paths, without merges or forks, whatever the input holds.
+ *   4. A track starts at (v, i) where i has a link in pair v and no link into it from pair v - 1, and follows the links
+ *      to the end: at least two views, and consecutive ones.
+ *   5. The tracks are numbered in ascending (start view, start keypoint) order; the first lmax are kept.
+ * Outputs: track_kp [windows, views, lmax] int32 (the track's keypoint in the view, or -1; -1 past the kept tracks),
+ * kept [windows] and found [windows] int32 (the number kept, and the number that exist). One launch, one workgroup of
+ * 256 threads per window: the next / prev tables as 16-bit indices in LDS (56 KiB), a pair's owner tables (16 KiB, reused
+ * by every pair), the start flags through lg_link_landmarks' workgroup prefix sum, one thread per kept track for the
+ * walk. The result does not depend on the order of anything: it is bitwise reproducible. */
+int32_t lg_window_tracks(const int32_t* matches, const int32_t* counts, const uint8_t* mask, const int32_t* kp_counts,
+                         int32_t windows, int32_t views, int32_t kmax, int32_t lmax, int32_t* track_kp, int32_t* kept,
+                         int32_t* found, hipStream_t stream);
+/* lg_window_points: each track's point from all of its posed views. Inputs: track_kp and kept (lg_window_tracks'; kept
+ * is clamped into [0, lmax], and a keypoint index outside [0, kp) is no keypoint); kpts [windows, views, kp, 2] fp32
+ * (pixels), kp >= 1 and windows * views * kp <= 2^28; intrinsics [windows, views, 4] fp32 (fx, fy, cx, cy); r
+ * [windows, views, 3, 3], t [windows, views, 3] fp32 with X_c = R_v X + t_v, whose entry 0 is not read (view 0 is the
+ * frame, as in lg_bundle_adjust; the rotations take its polar Newton step); posed [windows, views] uint8; threshold in
+ * (0, 1e6] pixels. A view counts iff posed != 0, its intrinsics are finite with focal lengths > 0 and its pose is
+ * finite. Per track below kept, fp64, over S = its views that count and hold a keypoint:
+ *   1. The linear start: the point closest to the rays of S, Σ (I - d dᵀ) X = Σ (I - d dᵀ) c by a 3 x 3 Cholesky, d the
+ *      unit ray Rᵀ ((x - cx) / fx, (y - cy) / fy, 1) / |.| and c = -Rᵀ t. Where a pivot is not positive or not finite the
+ *      system is not solved: X starts at zeros, and the track cannot be ok on this pass.
+ *   2. 3 rounds (kWindowGnRounds) of Gauss-Newton on Σ squared reprojection error in px² over S:
+ *      X <- X - (JᵀJ)⁻¹ Jᵀr by a 3 x 3 Cholesky; a row whose depth is not positive or whose residual is not finite at
+ *      the round's X adds nothing to it; a round whose JᵀJ has a pivot that is not positive, or whose step is not
+ *      finite, leaves X.
+ *   3. An observation of S is kept iff its depth is positive and its error is <= threshold (r² <= threshold², NaN
+ *      fails).
+ *   4. Steps 1 and 2 once more over the kept set (the same bits where nothing was dropped), then step 3's check of
+ *      every kept view.
+ *   5. ok iff at least 2 views are kept, every kept view passes, the point is finite in fp32, and the smallest pivot of
+ *      step 1's Cholesky over the kept set is >= 1e-5 (kParallaxEps; PARALLAX_EPS in the Python contract) x the
+ *      number of views kept: rays that are all but parallel give no point.
+ * The sums over a track's views are taken pairwise, views (0 + 1) + (2 + 3) then + ((4 + 5) + (6 + 7)), absent views
+ * zeros. Outputs, lg_bundle_adjust's inputs: obs [windows, views, lmax, 2] fp32 (the track's keypoint in the view,
+ * posed or not; zeros where it has none), seen [windows, views, lmax] uint8 (the view is kept and the track ok), counts
+ * [windows] int32 (kept, clamped), points [windows, lmax, 3] fp32 (zeros where not ok); and ok [windows, lmax] uint8,
+ * seen_all [windows, views, lmax] uint8 (the track has a keypoint in the view, posed or not: the next frame's 2D-3D rows
+ * are read off the same table). One launch, grid (tiles of 32 tracks, windows), 256 threads: the 8 adjacent lanes are the
+ * 8 views of a track (lg_bundle_adjust's layout), the sums go round an xor butterfly and every lane solves alike. */
+int32_t lg_window_points(const int32_t* track_kp, const int32_t* kept, const float* kpts, const float* intrinsics, const float* r,
+                         const float* t, const uint8_t* posed, int32_t windows, int32_t views, int32_t lmax, int32_t kp,
+                         float threshold, float* obs, uint8_t* seen, int32_t* counts, float* points, uint8_t* ok, uint8_t* seen_all,
+                         hipStream_t stream);
+/* lg_window_landmarks: the 2D-3D rows of one view, 0 <= view < views, as lg_ransac_absolute takes them. Inputs: track_kp,
+ * kept, ok and points as above; kpts_view [windows, kp, 2] fp32: that view's keypoints. The tracks below kept with
+ * ok != 0 and track_kp[view] in [0, kp), compacted in ascending track order: out_points [windows, lmax, 3] fp32 (the
+ * same bits), image [windows, lmax, 2] fp32, rows [windows, lmax] int32 (the track), n [windows] int32; past n zeros and
+ * rows -1. One launch, one workgroup per window: a stable compaction by the same prefix sum. */
+int32_t lg_window_landmarks(const int32_t* track_kp, const int32_t* kept, const uint8_t* ok, const float* points,
+                            const float* kpts_view, int32_t windows, int32_t views, int32_t lmax, int32_t kp, int32_t view,
+                            float* out_points, float* image, int32_t* rows, int32_t* n, hipStream_t stream);
+
 /* The fp16 forward's inputs (lightglue.py:329-337 and FourierPositionalEncoding :32-52), round 5:
  * x [pairs * (n0 + n1), dim] pair-major from desc0 [pairs, n0, dim] and desc1 [pairs, n1, dim]
  * (dim = 256, 16-B aligned), and the rotary tables cos, sin [pairs * (n0 + n1), 64] from kpts0

@@ -360,17 +360,8 @@ __global__ __launch_bounds__(kFinThreads) void link_kernel(LinkArgs a, float* __
         const int s = min(max(a.matches_b[((size_t)p * a.kmax_b + k) * 2], 0), a.k_shared - 1);
         mine += owner[s] != kNoOwner ? 1 : 0;
     }
-    scan[tid] = mine;
-    __syncthreads();
-#pragma unroll
-    for (int d = 1; d < kFinThreads; d <<= 1) {
-        const int v = tid >= d ? scan[tid - d] : 0;
-        __syncthreads();
-        scan[tid] += v;
-        __syncthreads();
-    }
-    const int total = scan[kFinThreads - 1];
-    int pos = scan[tid] - mine;
+    int total;
+    int pos = block_prefix<kFinThreads>(mine, scan, tid, total);
     for (int k = lo; k < hi; ++k) {
         const size_t row = (size_t)p * a.kmax_b + k;
         const int s = min(max(a.matches_b[2 * row], 0), a.k_shared - 1);

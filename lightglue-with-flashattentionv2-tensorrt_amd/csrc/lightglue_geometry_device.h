@@ -53,6 +53,24 @@ __device__ __forceinline__ double block_sum(double v, double* buf, int tid) {
     return buf[0];
 }
 
+// The exclusive prefix sum over the workgroup of one int per thread, in thread order (lg_link_landmarks' compaction,
+// the window kernels' track numbers); total: the sum, the same in every thread. scan: NT ints in LDS that no thread
+// still reads at entry.
+template <int NT>
+__device__ __forceinline__ int block_prefix(int mine, int* scan, int tid, int& total) {
+    scan[tid] = mine;
+    __syncthreads();
+#pragma unroll
+    for (int d = 1; d < NT; d <<= 1) {
+        const int v = tid >= d ? scan[tid - d] : 0;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    total = scan[NT - 1];
+    return scan[tid] - mine;
+}
+
 // A correspondence as the fundamental matrix and the homography take it: in pixels.
 struct PixelCoord {
     __device__ __forceinline__ void operator()(const float4 q, double c[4]) const {

@@ -220,6 +220,10 @@ SIGNATURES.update({
     # the bundle adjustment (csrc/lightglue_bundle.hip)
     "lg_bundle_adjust_workspace": ([_I, _I, _I], _S),
     "lg_bundle_adjust": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _S, _P, _P, _P, _P, _P, _P, _P], _I),
+    # the sequence window (csrc/lightglue_window.hip)
+    "lg_window_tracks": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    "lg_window_points": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], _I),
+    "lg_window_landmarks": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     "lg_ffn_pack": ([_P, _P, _P, _I, _I, _P, _P], _I),
     "lg_linear_cat_ffn_proj": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _I, _P, _P, _P, _I,
                                 ctypes.POINTER(_P), _P, _P], _I),

@@ -27,6 +27,10 @@ localize_landmarks gives the next frame a pose in the first pair's frame at the 
 ``BundleAdjust.refine`` (csrc/lightglue_bundle.hip) refines the poses of the views of a window and its landmarks together:
 Levenberg-Marquardt over Σ squared reprojection error by the Schur complement, whose product runs on the fp64 MFMA.
 
+``SequenceWindow.build`` (csrc/lightglue_window.hip) makes that window of the matcher's V - 1 consecutive pair results:
+tracks chained through the shared images, each track's point from all of its posed views; ``window_landmarks`` reads the
+next frame's 2D-3D rows off the same table.
+
 This module is the kernel side only. What each call computes is pinned in float64 in geometry_contract.py, and the
 synthetic pairs of the tests are in geometry_scenes.py; both are re-exported here.
 """
@@ -43,8 +47,9 @@ from .geometry_contract import (  # noqa: F401  (the public names this module ha
     essential_to_fundamental, fundamental_refit, gather_correspondences, homography_reference, homography_refit,
     polish_pose_reference, polish_reference, pose_candidates, pose_from_essential_reference, ransac_reference, ransac_samples,
     ransac_samples3, ransac_samples5, reprojection_error, rotation_angle_deg, sampson_error, solve4_reference, solve5_reference, solve7_reference, transfer_error,
-    triangulate_reference, BundleResult, MAX_BUNDLE, MAX_VIEWS, bundle_adjust_reference, bundle_fixed_set, absolute_pose_reference, absolute_refit_reference, link_landmarks_reference, solve3_reference, Solve3)
-from .geometry_scenes import (MultiViews, ThreeViews, absolute_scene, multi_view_scene, calibrated_planar_scene, calibrated_scene, planar_scene,  # noqa: F401
+    triangulate_reference, BundleResult, MAX_BUNDLE, MAX_VIEWS, bundle_adjust_reference, bundle_fixed_set, absolute_pose_reference, absolute_refit_reference, link_landmarks_reference, solve3_reference, Solve3, PARALLAX_EPS, WINDOW_GN_ROUNDS, Window, window_points_converged,
+    window_points_reference, window_tracks_reference)
+from .geometry_scenes import (MultiViews, SequenceViews, ThreeViews, absolute_scene, sequence_scene, multi_view_scene, calibrated_planar_scene, calibrated_scene, planar_scene,  # noqa: F401
                               three_view_scene, two_view_scene)
 from .image import ImageInput, match_source_images
 from .matches import MatchResult
@@ -414,6 +419,102 @@ def window_from_chain(result_a: MatchResult, result_b: MatchResult, kpts0: torch
     r = torch.stack([eye, pose.R, absolute.R.to(pose.R.dtype)], 1)
     t = torch.stack([torch.zeros_like(pose.t), pose.t, absolute.t.to(pose.t.dtype)], 1)
     return obs.contiguous(), seen.contiguous(), result_a.counts.clamp(0, ka).to(torch.int32), r.contiguous(), t.contiguous(), points.contiguous()
+
+
+# ---- the sequence window ----------------------------------------------------------------------------------------------
+class SequenceWindow:
+    """The window of V views (2 .. 8) of a sequence from its V - 1 consecutive pair results (csrc/lightglue_window.hip):
+    tracks chained through the shared images (a keypoint belongs to the lowest live row naming it, on both sides of a
+    pair; a link needs one row owning both ends, so tracks are simple paths), and each track's point from all of its posed
+    views (the point closest to the rays, then Gauss-Newton on the reprojection error in fp64; an observation further than
+    `threshold` pixels is dropped). build -> Window."""
+
+    def __init__(self, threshold: float = 3.0) -> None:
+        if not 0.0 < float(threshold) <= 1e6:
+            raise ValueError(f"threshold must be in (0, 1e6] pixels, got {threshold}")
+        self.threshold = float(threshold)
+
+    def build(self, results, masks, kpts, intrinsics: torch.Tensor, R: torch.Tensor, t: torch.Tensor, posed=None, *, lmax: int,
+              kp_counts=None) -> Window:
+        """results: V - 1 MatchResult (matches [B, Kmax, 2], counts [B] int32; pair v is (view v, view v + 1)); masks: V - 1
+        [B, Kmax] uint8 (non-zero: the row counts; a pose's inliers or inliers_on_matches); kpts: V tensors [B, K, 2] fp32
+        (pixels), of one Kmax and one K; intrinsics [B, V, 4], R [B, V, 3, 3], t [B, V, 3] fp32 (X_c = R_v X + t_v, entry 0
+        not read); posed [B, V] uint8 (None: every view; a view that is not posed adds nothing to the points but keeps its
+        observations); lmax in [1, 2048]: the tracks kept; kp_counts [B, V] int32 (None: K in every view) -> Window. The
+        lists are stacked by framework copies, then two launches on the current stream; nothing is read back."""
+        views = len(kpts)
+        if not 2 <= views <= MAX_VIEWS or len(results) != views - 1 or len(masks) != views - 1:
+            raise ValueError(f"build: V keypoint tensors with 2 <= V <= {MAX_VIEWS}, V - 1 results and V - 1 masks; got {views}, "
+                             f"{len(results)}, {len(masks)}")
+        if not 1 <= int(lmax) <= MAX_POINTS:
+            raise ValueError(f"lmax must be in [1, {MAX_POINTS}], got {lmax}")
+        for i, res in enumerate(results):
+            require_gpu(f"matches[{i}]", res.matches, _STAGE, (torch.int32,), 3)
+            require_gpu(f"counts[{i}]", res.counts, _STAGE, (torch.int32,), 1)
+            require_gpu(f"masks[{i}]", masks[i], _STAGE, (torch.uint8,), 2)
+        for i, x in enumerate(kpts):
+            require_gpu(f"kpts[{i}]", x, _STAGE, (torch.float32,), 3)
+        first = results[0].matches
+        bw, kmax, kp, dev = int(first.shape[0]), int(first.shape[1]), int(kpts[0].shape[1]), first.device
+        if first.shape[2] != 2 or not 1 <= kmax <= MAX_POINTS or kp < 1:
+            raise ValueError(f"matches: expected [B, Kmax, 2] with 1 <= Kmax <= {MAX_POINTS} and K >= 1, got {tuple(first.shape)}, K {kp}")
+        for i, res in enumerate(results):
+            _like_matches(f"matches[{i}]", res.matches, (bw, kmax, 2), first)
+            _like_matches(f"counts[{i}]", res.counts, (bw,), first)
+            _like_matches(f"masks[{i}]", masks[i], (bw, kmax), first)
+        for i, x in enumerate(kpts):
+            _like_matches(f"kpts[{i}]", x, (bw, kp, 2), first)
+        if posed is None:
+            posed = torch.ones((bw, views), dtype=torch.uint8, device=dev)
+        if kp_counts is None:
+            kp_counts = torch.full((bw, views), min(kp, MAX_POINTS), dtype=torch.int32, device=dev)
+        for name, x, dt, shape in (("intrinsics", intrinsics, torch.float32, (bw, views, 4)), ("R", R, torch.float32, (bw, views, 3, 3)),
+                                   ("t", t, torch.float32, (bw, views, 3)), ("posed", posed, torch.uint8, (bw, views)),
+                                   ("kp_counts", kp_counts, torch.int32, (bw, views))):
+            require_gpu(name, x, _STAGE, (dt,), len(shape))
+            _like_matches(name, x, shape, first)
+        matches = torch.stack([res.matches for res in results], 1).contiguous()
+        counts = torch.stack([res.counts for res in results], 1).contiguous()
+        mask = torch.stack(list(masks), 1).contiguous()
+        pixels = torch.stack(list(kpts), 1).contiguous()
+        intrinsics, R, t, posed, kp_counts = (x.contiguous() for x in (intrinsics, R, t, posed, kp_counts))
+        lmax = int(lmax)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+        out = Window(torch.empty((bw, views, lmax, 2), dtype=torch.float32, device=dev), u8(bw, views, lmax), i32(bw), R, t,
+                     torch.empty((bw, lmax, 3), dtype=torch.float32, device=dev), u8(bw, lmax), u8(bw, views, lmax), i32(bw, views, lmax),
+                     i32(bw))
+        if bw == 0:
+            return out
+        stream, kept = stream_of(first), i32(bw)
+        call("lg_window_tracks", matches.data_ptr(), counts.data_ptr(), mask.data_ptr(), kp_counts.data_ptr(), bw, views, kmax, lmax,
+             out.track_kp.data_ptr(), kept.data_ptr(), out.found.data_ptr(), stream)
+        call("lg_window_points", out.track_kp.data_ptr(), kept.data_ptr(), pixels.data_ptr(), intrinsics.data_ptr(), R.data_ptr(),
+             t.data_ptr(), posed.data_ptr(), bw, views, lmax, kp, self.threshold, out.obs.data_ptr(), out.seen.data_ptr(),
+             out.counts.data_ptr(), out.points.data_ptr(), out.ok.data_ptr(), out.seen_all.data_ptr(), stream)
+        return out
+
+
+def window_landmarks(window: Window, kpts_view: torch.Tensor, view: int) -> Landmarks:
+    """The 2D-3D rows of one view of a Window, as AbsolutePoseRansac.localize_landmarks takes them: the tracks that are ok
+    and hold a keypoint of `view` (posed or not), in ascending track order, with kpts_view [B, K, 2] fp32 that view's
+    keypoints -> Landmarks (rows: the track). One launch on the current stream, nothing read back."""
+    require_gpu("track_kp", window.track_kp, _STAGE, (torch.int32,), 3)
+    require_gpu("kpts_view", kpts_view, _STAGE, (torch.float32,), 3)
+    bw, views, lmax = (int(s) for s in window.track_kp.shape)
+    if not 0 <= int(view) < views:
+        raise ValueError(f"view must be in [0, {views}), got {view}")
+    if kpts_view.shape[0] != bw or kpts_view.shape[1] < 1 or kpts_view.shape[2] != 2:
+        raise ValueError(f"kpts_view: expected [{bw}, K, 2] with K >= 1, got {tuple(kpts_view.shape)}")
+    for name, x, shape in (("counts", window.counts, (bw,)), ("ok", window.ok, (bw, lmax)), ("points", window.points, (bw, lmax, 3)),
+                           ("kpts_view", kpts_view, tuple(kpts_view.shape))):
+        _like_matches(name, x, shape, window.track_kp)
+    track_kp, counts, ok, points, kpts_view = (x.contiguous() for x in (window.track_kp, window.counts, window.ok, window.points, kpts_view))
+    out = _empty(Landmarks, bw, lmax, track_kp.device)
+    if bw:
+        call("lg_window_landmarks", track_kp.data_ptr(), counts.data_ptr(), ok.data_ptr(), points.data_ptr(), kpts_view.data_ptr(), bw,
+             views, lmax, int(kpts_view.shape[1]), int(view), *(x.data_ptr() for x in out), stream_of(track_kp))
+    return out
 
 
 def inliers_on_matches(landmarks: Landmarks, result: AbsolutePoseResult, kmax_b: int) -> torch.Tensor:

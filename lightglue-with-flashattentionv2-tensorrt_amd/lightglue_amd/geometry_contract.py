@@ -28,6 +28,9 @@ The absolute pose (a camera against 3D points): ``ransac_samples3``, ``reproject
 not the kernel's bracketed roots, rational third distance and triangle frames), ``absolute_refit_reference`` (scipy's
 least squares to its tolerance floor on a global rotation vector and t), ``absolute_pose_reference`` (the whole, a
 fourth model of ``_ransac_pair``) and ``link_landmarks_reference`` (the 3D points of one pair onto the rows of the next).
+
+The sequence window: ``window_tracks_reference`` (plain loops over integers), ``window_points_reference`` (the fixed-round
+scheme) and ``window_points_converged`` (scipy's least squares per track from another start: the converged minimiser).
 """
 from __future__ import annotations
 
@@ -1267,3 +1270,204 @@ def bundle_adjust_reference(obs, seen, count, intrinsics, R, t, points) -> Bundl
     r, tt, x = unpack(sol.x)
     return BundleResult(torch.from_numpy(r), torch.from_numpy(tt), torch.from_numpy(x), torch.tensor([cost0, cost1], dtype=torch.float64),
                         torch.tensor(int(mask.sum()), dtype=torch.int32), torch.tensor(1, dtype=torch.int32))
+
+
+# ---- the sequence window ----------------------------------------------------------------------------------------------
+PARALLAX_EPS = 1e-5     # the smallest pivot of Σ (I - d dᵀ) over the views kept below this x their number: no point
+WINDOW_GN_ROUNDS = 3    # Gauss-Newton rounds a pass (kWindowGnRounds; profiles/geometry/INDEX.md has the table)
+
+
+class Window(NamedTuple):
+    """SequenceWindow.build's result. The first six fields, with the intrinsics, are BundleAdjust.refine's arguments: obs
+    [B, V, Lmax, 2] fp32 (a track's keypoint in each view, zeros where it has none), seen [B, V, Lmax] uint8 (the view is
+    posed, kept by the track's point and the track ok), counts [B] int32 (the tracks kept), R [B, V, 3, 3], t [B, V, 3] (as
+    given), points [B, Lmax, 3] (zeros where not ok). Then ok [B, Lmax] uint8, seen_all [B, V, Lmax] uint8 (the track has a
+    keypoint in the view, posed or not), track_kp [B, V, Lmax] int32 (that keypoint, or -1) and found [B] int32 (the
+    tracks that exist; counts = min(found, Lmax))."""
+    obs: torch.Tensor
+    seen: torch.Tensor
+    counts: torch.Tensor
+    R: torch.Tensor
+    t: torch.Tensor
+    points: torch.Tensor
+    ok: torch.Tensor
+    seen_all: torch.Tensor
+    track_kp: torch.Tensor
+    found: torch.Tensor
+
+
+def window_tracks_reference(matches, counts, mask, kp_counts, lmax: int):
+    """lg_window_tracks' contract for one window in plain loops over integers: matches [V-1, Kmax, 2], counts [V-1], mask
+    [V-1, Kmax], kp_counts [V] -> (track_kp [V, lmax] int32, kept, found). A row is live below its count with a non-zero
+    mask and both indices inside their views' keypoint counts; a keypoint is owned by the lowest live row naming it, on
+    either side; a link needs one row owning both ends; a track starts where a keypoint has a link out and none in, and
+    follows the links; ascending (start view, start keypoint), the first lmax kept."""
+    m, cnt, msk, kpc = (np.asarray(x) for x in (matches, counts, mask, kp_counts))
+    pairs, kmax = m.shape[0], m.shape[1]
+    nxt, prv = [dict() for _ in range(pairs)], [dict() for _ in range(pairs)]
+    for v in range(pairs):
+        k0, k1 = (min(max(int(kpc[v + s]), 0), MAX_POINTS) for s in (0, 1))
+        own0, own1, live = {}, {}, []
+        for r in range(min(max(int(cnt[v]), 0), kmax)):
+            i, j = int(m[v, r, 0]), int(m[v, r, 1])
+            if msk[v, r] and 0 <= i < k0 and 0 <= j < k1:
+                live.append((r, i, j))
+                own0.setdefault(i, r)
+                own1.setdefault(j, r)
+        for r, i, j in live:
+            if own0[i] == r and own1[j] == r:
+                nxt[v][i], prv[v][j] = j, i
+    track_kp = np.full((pairs + 1, int(lmax)), -1, dtype=np.int32)
+    found = 0
+    for v in range(pairs):
+        for i in sorted(nxt[v]):
+            if v > 0 and i in prv[v - 1]:
+                continue
+            if found < int(lmax):
+                cur, w = i, v
+                while cur is not None:
+                    track_kp[w, found] = cur
+                    cur, w = (nxt[w].get(cur) if w < pairs else None), w + 1
+            found += 1
+    return track_kp, min(found, int(lmax)), found
+
+
+def _window_views(kpts, intrinsics, R, t, posed):
+    """(kpts, k, r, t, usable [V]) in float64: view 0 the frame, the rotations after the polar Newton step, a view usable
+    iff posed with finite intrinsics, focal lengths > 0 and a finite pose."""
+    kp, k, r, tt = _np(kpts), _np(intrinsics), _np(R).copy(), _np(t).copy()
+    r[0], tt[0] = np.eye(3), 0.0
+    usable = (np.asarray(posed) != 0) & np.isfinite(k).all(1) & (k[:, :2] > 0).all(1) & np.isfinite(r).all((1, 2)) & np.isfinite(tt).all(1)
+    with np.errstate(all="ignore"):
+        r = np.stack([0.5 * m @ (3.0 * np.eye(3) - m.T @ m) for m in r])
+    return kp, k, r, tt, usable
+
+
+def _tree8(terms):
+    """The sum of per-view terms [8, ...] in the kernel's order: (0 + 1) + (2 + 3), then + ((4 + 5) + (6 + 7))."""
+    return ((terms[0] + terms[1]) + (terms[2] + terms[3])) + ((terms[4] + terms[5]) + (terms[6] + terms[7]))
+
+
+def _track_residuals(x, views, px, k, r, tt):
+    """(residuals [n, 2] in px, depths [n]) of the point x in `views` against the pixels px [n, 2]."""
+    with np.errstate(all="ignore"):
+        c = np.einsum("vij,j->vi", r[views], x) + tt[views]
+        res = np.stack([k[views, 0] * c[:, 0] / c[:, 2] + k[views, 2] - px[:, 0], k[views, 1] * c[:, 1] / c[:, 2] + k[views, 3] - px[:, 1]], 1)
+    return res, c[:, 2]
+
+
+def _linear_start(views, px, k, r, tt, sum_terms):
+    """Step 1: (x, the smallest Cholesky pivot, solved) of Σ (I - d dᵀ) X = Σ (I - d dᵀ) c over `views`."""
+    a, b = np.zeros((MAX_VIEWS, 3, 3)), np.zeros((MAX_VIEWS, 3))
+    with np.errstate(all="ignore"):
+        for v, p in zip(views, px):
+            n = np.array([(p[0] - k[v, 2]) / k[v, 0], (p[1] - k[v, 3]) / k[v, 1], 1.0])
+            d = r[v].T @ n / np.linalg.norm(n)
+            m = np.eye(3) - np.outer(d, d)
+            a[v], b[v] = m, m @ (-r[v].T @ tt[v])
+        aa, bb = sum_terms(a), sum_terms(b)
+        low = np.zeros((3, 3))
+        piv = []
+        for c in range(3):  # (the pivots by hand: numpy's Cholesky raises where the kernel decides)
+            p = aa[c, c] - low[c, :c] @ low[c, :c]
+            piv.append(p)
+            low[c, c] = np.sqrt(p)
+            for i in range(c + 1, 3):
+                low[i, c] = (aa[i, c] - low[i, :c] @ low[c, :c]) / low[c, c]
+        solved = all(np.isfinite(p) and p > 0 for p in piv)
+        x = np.linalg.solve(low.T, np.linalg.solve(low, bb)) if solved else np.zeros(3)
+    return x, (min(piv) if solved else 0.0), solved
+
+
+def _track_point(views, px, k, r, tt, thr2, rounds, sum_terms):
+    """Steps 1 to 5 of lg_window_points for one track over its usable views -> (x, kept views, ok, the smallest
+    |error - threshold| in px over both checks, the smallest pivot)."""
+    views, px = np.asarray(views, dtype=int), np.asarray(px, dtype=np.float64).reshape(-1, 2)
+    x, piv, solved, passes = np.zeros(3), 0.0, False, np.zeros(0, dtype=bool)
+    err, near = np.zeros(0), np.inf
+    for attempt in range(2):
+        x, piv, solved = _linear_start(views, px, k, r, tt, sum_terms)
+        for _ in range(rounds):
+            res, depth = _track_residuals(x, views, px, k, r, tt)
+            rows = np.isfinite(res).all(1) & (depth > 0)
+            jtj, jtr = np.zeros((MAX_VIEWS, 3, 3)), np.zeros((MAX_VIEWS, 3))
+            with np.errstate(all="ignore"):
+                for v, p, e, row in zip(views, px, res, rows):
+                    if not row:
+                        continue
+                    c = r[v] @ x + tt[v]
+                    jac = np.array([[k[v, 0] / c[2], 0.0, -k[v, 0] * c[0] / c[2] ** 2], [0.0, k[v, 1] / c[2], -k[v, 1] * c[1] / c[2] ** 2]]) @ r[v]
+                    jtj[v], jtr[v] = jac.T @ jac, jac.T @ e
+                h, g = sum_terms(jtj), sum_terms(jtr)
+                try:
+                    np.linalg.cholesky(h)
+                    step = np.linalg.solve(h, g)
+                except np.linalg.LinAlgError:
+                    continue
+                if np.isfinite(step).all():
+                    x = x - step
+        res, depth = _track_residuals(x, views, px, k, r, tt)
+        with np.errstate(all="ignore"):
+            e2 = (res ** 2).sum(1)
+            passes = np.isfinite(res).all(1) & (depth > 0) & (e2 <= thr2)
+        err = np.sqrt(e2)
+        if len(err) and np.isfinite(err).any():
+            near = min(near, float(np.nanmin(np.abs(err - np.sqrt(thr2)))))
+        if attempt == 0:
+            views, px = views[passes], px[passes]
+    with np.errstate(all="ignore"):
+        ok = bool(solved and len(views) >= 2 and passes.all() and np.isfinite(x.astype(np.float32)).all() and piv >= PARALLAX_EPS * len(views))
+    return x, views, ok, near, piv
+
+
+def window_points_reference(track_kp, kept, kpts, intrinsics, R, t, posed, threshold: float = 3.0, rounds: int = WINDOW_GN_ROUNDS,
+                            order=_tree8):
+    """lg_window_points' contract for one window in float64, the fixed-round scheme: track_kp [V, Lmax], kept, kpts
+    [V, Kp, 2], intrinsics [V, 4], R [V, 3, 3], t [V, 3], posed [V] -> (obs [V, Lmax, 2] fp32, seen [V, Lmax] uint8, count,
+    points [Lmax, 3] float64, ok [Lmax] uint8, seen_all [V, Lmax] uint8, margins): per track the linear start over its
+    posed views, `rounds` Gauss-Newton rounds, the check at `threshold`, the same once more over the kept set, and the ok
+    rule. order: how a track's per-view terms [8, ...] are added (the kernel's pairwise tree; a test passes another to
+    measure the sensitivity). margins: (the smallest |error - threshold| in px over every checked observation, the
+    smallest max(pivot / (PARALLAX_EPS n), its inverse) over the tracks with 2 or more kept views)."""
+    tk = np.asarray(track_kp)
+    kp, k, r, tt, usable = _window_views(kpts, intrinsics, R, t, posed)
+    views, lmax = tk.shape
+    n = min(max(int(kept), 0), lmax)
+    obs, seen = np.zeros((views, lmax, 2), dtype=np.float32), np.zeros((views, lmax), dtype=np.uint8)
+    points, ok, seen_all = np.zeros((lmax, 3)), np.zeros(lmax, dtype=np.uint8), np.zeros((views, lmax), dtype=np.uint8)
+    near_thr, near_piv = np.inf, np.inf
+    for l in range(n):
+        has = [v for v in range(views) if 0 <= tk[v, l] < kp.shape[1]]
+        for v in has:
+            obs[v, l], seen_all[v, l] = kp[v, tk[v, l]], 1
+        mine = [v for v in has if usable[v]]
+        x, keptv, good, near, piv = _track_point(mine, [kp[v, tk[v, l]] for v in mine], k, r, tt, float(threshold) ** 2, rounds, order)
+        near_thr = min(near_thr, near)
+        if len(keptv) >= 2 and piv > 0:
+            ratio = piv / (PARALLAX_EPS * len(keptv))
+            near_piv = min(near_piv, max(ratio, 1.0 / ratio))
+        if good:
+            points[l], ok[l] = x, 1
+            seen[keptv, l] = 1
+    return obs, seen, n, points, ok, seen_all, (near_thr, near_piv)
+
+
+def window_points_converged(views, px, intrinsics, R, t):
+    """The converged minimiser of Σ squared reprojection error in px² of one track over the given views (indices into
+    intrinsics [V, 4], R, t; px [n, 2]) by another route: scipy.optimize.least_squares(method="lm") at its tolerance
+    floor with a numeric Jacobian, from the midpoint of the first two rays' closest points rather than the contract's
+    linear start."""
+    from scipy.optimize import least_squares
+
+    views, px = np.asarray(views, dtype=int), np.asarray(px, dtype=np.float64).reshape(-1, 2)
+    _, k, r, tt, _ = _window_views(np.zeros((len(_np(R)), 1, 2)), intrinsics, R, t, np.ones(len(_np(R))))
+    rays, cs = [], []
+    for v, p in zip(views[:2], px[:2]):
+        n = np.array([(p[0] - k[v, 2]) / k[v, 0], (p[1] - k[v, 3]) / k[v, 1], 1.0])
+        rays.append(r[v].T @ n / np.linalg.norm(n))
+        cs.append(-r[v].T @ tt[v])
+    s = np.linalg.lstsq(np.stack([rays[0], -rays[1]], 1), cs[1] - cs[0], rcond=None)[0]
+    x0 = 0.5 * ((cs[0] + s[0] * rays[0]) + (cs[1] + s[1] * rays[1]))
+    sol = least_squares(lambda x: _track_residuals(x, views, px, k, r, tt)[0].reshape(-1), x0, method="lm", xtol=1e-15, ftol=1e-15,
+                        gtol=1e-15, max_nfev=2000)
+    return sol.x

@@ -5,7 +5,8 @@ bit with their cameras (K, R, t) for the essential matrix and the pose polish. T
 the float64 contract's (geometry_contract.py). ``absolute_scene`` is a map of 3D points and one camera that sees it (the
 absolute pose), ``three_view_scene`` three cameras in a row and the match rows of the two pairs that share the middle
 one (the chain from a relative pose to the next camera's pose in the first pair's frame), ``multi_view_scene`` a window of
-up to 8 cameras in a row with a perturbed start (the bundle adjustment)."""
+up to 8 cameras in a row with a perturbed start (the bundle adjustment), ``sequence_scene`` those cameras and points as
+per-view keypoints and per-pair match rows (the sequence window)."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -337,3 +338,73 @@ def multi_view_scene(seed: int, views: int, k: int, noise_px: float, miss_fracti
     f32 = lambda m: torch.from_numpy(m.astype(np.float32))  # noqa: E731
     return MultiViews(f32(obs), torch.from_numpy(seen), torch.from_numpy(kk), torch.from_numpy(r), torch.from_numpy(t),
                       torch.from_numpy(xyz), f32(r0), f32(t0), f32(x0))
+
+
+class SequenceViews(NamedTuple):
+    """sequence_scene's result. kpts [V, k, 2] fp32: every view's keypoints; matches [V-1, k, 2] int32, counts [V-1] int32 and
+    mask [V-1, k] uint8: the rows of pair v = (view v, view v + 1); kp_counts [V] int32; K [3, 3]; R [V, 3, 3], t [V, 3] and
+    points [n_true, 3] float64: the truth (multi_view_scene's); n_true: keypoint j < n_true of every view belongs to point
+    j; seen [V, n_true] bool: the point is matched in the view; wrong [V, n_true] bool: its pixel there is a wrong one."""
+    kpts: torch.Tensor
+    matches: torch.Tensor
+    counts: torch.Tensor
+    mask: torch.Tensor
+    kp_counts: torch.Tensor
+    K: torch.Tensor
+    R: torch.Tensor
+    t: torch.Tensor
+    points: torch.Tensor
+    n_true: int
+    seen: torch.Tensor
+    wrong: torch.Tensor
+
+
+def sequence_scene(seed: int, views: int, k: int, outlier_fraction: float, noise_px: float, miss_fraction: float,
+                   size=(480, 640)) -> SequenceViews:
+    """multi_view_scene(seed, views, n_true, noise_px, miss_fraction)'s cameras and points as a sequence's inputs: k keypoints
+    a view and up to k match rows a pair, from synth.uniform24. Keypoint j < n_true = k - round(k outlier_fraction) of every
+    view is point j's observation, the others uniform pixels. Pair v's rows: (j, j) for every point seen in both views (a
+    miss splits a point's track in two; about one point in seven first appears in a later view); (o, o) for every other
+    keypoint, the outlier rows, which chain into tracks of no point; round(k outlier_fraction) / 2 rows that name a
+    keypoint some other row names too, with another keypoint on the other side (duplicates, non-mutual rows); from 16
+    keypoints on, two rows with an index out of range. From 4 views on, about one point in twenty has a wrong pixel in one
+    view from 2 on, 12.5 to 15 px from its observation (further, and a least-squares point leaves every view's threshold): an
+    observation its track must drop. The rows of each pair are
+    in an order of its own, cut at k, and padded past the count with indices out of range; the mask clears about one row in
+    twenty, and every other outlier row."""
+    h, w = int(size[0]), int(size[1])
+    n_out = int(round(k * outlier_fraction))
+    n_true = k - n_out
+    if k < 1 or n_true < 1 or n_out < 0:
+        raise ValueError(f"sequence_scene: bad k / outlier_fraction {k}, {outlier_fraction}")
+    mv = multi_view_scene(seed, views, n_true, noise_px, miss_fraction, size)
+    u = synth.uniform24(int(seed) + 0x5E90, 8 * k + 4 * views * k).astype(np.float64)
+    pt, u = u[:8 * k].reshape(8, k), u[8 * k:].reshape(4, views, k)
+    seen = mv.seen.numpy().astype(bool)
+    kpts = np.zeros((views, k, 2))
+    kpts[:, :n_true] = mv.obs.numpy()
+    kpts[:, n_true:] = np.stack([u[0, :, n_true:] * (w - 1), u[1, :, n_true:] * (h - 1)], -1)
+    wrong = np.zeros((views, n_true), dtype=bool)
+    for j in range(n_true):
+        if views >= 3 and pt[0, j] < 0.15:  # the point first appears in a later view
+            seen[:1 + int(pt[1, j] * (views - 2)), j] = False
+        v = 2 + int(pt[3, j] * (views - 2))
+        if views >= 4 and pt[2, j] < 0.05 and seen[v, j]:
+            turn, far = 2.0 * np.pi * u[0, v, j], 12.5 + 2.5 * u[1, v, j]
+            kpts[v, j], wrong[v, j] = kpts[v, j] + far * np.array([np.cos(turn), np.sin(turn)]), True
+    matches = np.zeros((views - 1, k, 2), dtype=np.int64)
+    counts, mask = np.zeros(views - 1, dtype=np.int32), np.ones((views - 1, k), dtype=np.uint8)
+    for v in range(views - 1):
+        rows = [(j, j) for j in range(n_true) if seen[v, j] and seen[v + 1, j]] + [(o, o) for o in range(n_true, k)]
+        first_out = len(rows) - n_out
+        rows += [(int(u[2, v, d] * k), int(u[3, v, d] * k)) for d in range(n_out // 2)]
+        if k >= 16:
+            rows += [(k + 3, 0), (1, -2)]
+        order = np.argsort(synth.uniform24(int(seed) + 0x5EED + v, len(rows)), kind="stable")
+        clear = np.array([(first_out <= i < first_out + n_out and i % 2 == 0) for i in range(len(rows))]) | (u[2, v, np.arange(len(rows)) % k] < 0.05)
+        n = min(len(rows), k)
+        matches[v, :n], mask[v, :n], counts[v] = np.array(rows).reshape(-1, 2)[order][:n], ~clear[order][:n], n
+        matches[v, n:] = (-1, 1 << 20)
+    return SequenceViews(torch.from_numpy(kpts.astype(np.float32)), torch.from_numpy(matches.astype(np.int32)), torch.from_numpy(counts),
+                         torch.from_numpy(mask), torch.full((views,), k, dtype=torch.int32), mv.K, mv.R, mv.t, mv.points, n_true,
+                         torch.from_numpy(seen), torch.from_numpy(wrong))

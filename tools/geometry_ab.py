@@ -233,12 +233,12 @@ def main():
     ap.add_argument("--polish", type=int, default=0, help="with --model essential: the A/B of verify at polish 0 and N")
     ap.add_argument("--part", choices=("all", "verify", "pipeline"), default="all")
     ap.add_argument("--form", choices=("mfma", "fma"), default="mfma", help="with --model bundle: the loaded library's Schur product")
-    ap.add_argument("--model", choices=("fundamental", "homography", "essential", "absolute", "bundle"), default="fundamental")
+    ap.add_argument("--model", choices=("fundamental", "homography", "essential", "absolute", "bundle", "window"), default="fundamental")
     args = ap.parse_args()
     if args.polish and args.model != "essential":
         sys.exit("geometry_ab.py: --polish goes with --model essential")
     if args.out is None:
-        name = "ab_polish.jsonl" if args.polish else {"absolute": "ab_absolute.jsonl", "bundle": "ab_bundle.jsonl"}.get(args.model, "ab.jsonl")
+        name = "ab_polish.jsonl" if args.polish else {"absolute": "ab_absolute.jsonl", "bundle": "ab_bundle.jsonl", "window": "ab_window.jsonl"}.get(args.model, "ab.jsonl")
         args.out = os.path.join(REPO, "profiles", "geometry", name)
     if not torch.cuda.is_available():
         sys.exit("geometry_ab.py: needs a GPU (timings from anywhere else mean nothing)")
@@ -262,6 +262,9 @@ def main():
         return
     if args.model == "bundle":
         bundle_part(args, dev, stream, emit)
+        return
+    if args.model == "window":
+        window_part(args, dev, stream, emit)
         return
     if args.model == "essential":
         if args.polish:
@@ -458,6 +461,37 @@ def bundle_part(args, dev, stream, emit):
                 t = [time_graph(g, stream, calls) for _ in range(max(args.repeats, 9))]
                 emit(dict(part="refine", model="bundle", form=form, V=views, L=lmax, B=bw, iterations=10, kept=int(out.kept.sum()),
                           num_obs=int(out.num_obs[0]), refine_us=spread(t), device=torch.cuda.get_device_name(0)))
+
+
+def window_part(args, dev, stream, emit):
+    """SequenceWindow.build by graph replay: at V = 3, k = 200 against window_from_chain on the same inputs (pair 0's rows as
+    the landmarks, the true poses, every row an inlier: the data movement alone), and build alone at V = 8, K = 2,048."""
+    from lightglue_amd import Landmarks, SequenceWindow, sequence_scene, window_from_chain
+    from lightglue_amd.geometry_contract import AbsolutePoseResult, PoseResult
+    from lightglue_amd.matches import MatchResult
+
+    sw, calls = SequenceWindow(THR), 4
+    for views, k in ((3, 200), (8, 2048)):
+        s = sequence_scene(11, views, k, 0.2, 0.5, 0.2)
+        kk = s.K
+        intr = torch.tensor([kk[0, 0], kk[1, 1], kk[0, 2], kk[1, 2]], dtype=torch.float32).repeat(1, views, 1).to(dev)
+        res = [MatchResult(None, None, None, None, s.matches[v][None].contiguous().to(dev), None, s.counts[v:v + 1].to(dev)) for v in range(views - 1)]
+        masks = [s.mask[v][None].contiguous().to(dev) for v in range(views - 1)]
+        kpts = [s.kpts[v][None].contiguous().to(dev) for v in range(views)]
+        r, t = s.R.float()[None].contiguous().to(dev), s.t.float()[None].contiguous().to(dev)
+        arms = {"build": lambda: sw.build(res, masks, kpts, intr, r, t, lmax=k)}
+        if views == 3:
+            pose = PoseResult(None, r[:, 1].contiguous(), t[:, 1].contiguous(), masks[0], None, None, None, None)
+            absolute = AbsolutePoseResult(r[:, 2].contiguous(), t[:, 2].contiguous(), None, None, None, None)
+            marks = Landmarks(None, None, torch.zeros((1, k), dtype=torch.int32, device=dev), None)
+            pts, ok = torch.zeros((1, k, 3), device=dev), torch.ones((1, k), dtype=torch.uint8, device=dev)
+            arms["window_from_chain"] = lambda: window_from_chain(res[0], res[1], kpts[0], kpts[1], kpts[2], pose, pts, ok, marks, absolute, masks[1])
+        for name, fn in arms.items():
+            g = graph_of(fn, stream, calls)
+            for _ in range(3):
+                time_graph(g, stream, calls)
+            us = [time_graph(g, stream, calls) for _ in range(max(args.repeats, 9))]
+            emit(dict(part=name, model="window", V=views, K=k, B=1, us=spread(us), device=torch.cuda.get_device_name(0)))
 
 
 def absolute_part(args, dev, stream, base, emit):
