@@ -176,6 +176,29 @@ size_t mha_hd64_launch_workspace_bytes(int32_t batch, int32_t heads, int32_t nq,
 size_t mha_hd64_launch_workspace_bytes_typed(int32_t batch, int32_t heads, int32_t nq, int32_t nkv,
                                              int32_t in_type);
 
+/* ---- backward (csrc/mha_hd64_backward.hip) ----
+ * dQ, dK and dV of O = softmax(Q K^T / 8) V from Q, K, V, the forward's output O and dO. All tensors
+ * are contiguous [batch, heads, n, 64] with 16-byte aligned pointers: q, o, dout, dq over nq rows,
+ * k, v, dk, dv over nkv rows, any nq >= 1 and nkv >= 1 (tails are masked in the kernels); nq, batch
+ * or heads of 0 is a successful no-op. _fp16: fp16 tensors. _fp32: fp32 tensors; the inputs are
+ * rounded to fp16 (RNE) into the workspace, as the forward's Float boundary does, and the gradients
+ * (of that rounded-input function) are stored as fp32. No floating-point atomics: results are bitwise
+ * reproducible. No allocation and no synchronisation inside: capturable in a graph.
+ * BAD_PARAM: a null or misaligned pointer, a negative size, nkv < 1 with nq > 0; WORKSPACE:
+ * ws_bytes below mha_hd64_backward_workspace_bytes(batch, heads, nq, nkv, in_type). */
+int32_t mha_hd64_backward_fp16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                               void* dq, void* dk, void* dv,
+                               int32_t batch, int32_t heads, int32_t nq, int32_t nkv,
+                               void* workspace, size_t ws_bytes, hipStream_t stream);
+int32_t mha_hd64_backward_fp32(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                               void* dq, void* dk, void* dv,
+                               int32_t batch, int32_t heads, int32_t nq, int32_t nkv,
+                               void* workspace, size_t ws_bytes, hipStream_t stream);
+/* Workspace bytes of a backward call with tensors of in_type (mha_hd64_dtype_t): the row statistics
+ * L and D (fp32 [batch, heads, nq] each), the fp16 copies for FLOAT, and the partial dK / dV of the
+ * column kernel's query split. 0 for an invalid in_type and for empty shapes. */
+size_t mha_hd64_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t nq, int32_t nkv, int32_t in_type);
+
 /* ---- grouped launcher ----
  * Several independent calls of (possibly) different shapes in one launch. A LightGlue layer
  * makes four attention calls whose inputs are all ready together: SelfBlock on image 0 and on

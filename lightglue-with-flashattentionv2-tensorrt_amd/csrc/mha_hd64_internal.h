@@ -100,6 +100,38 @@ hipError_t launch_attention(const Call& c, InType in, OutType out, void* workspa
                             hipStream_t stream, int force_q_waves = 0, int force_kv_waves = 0,
                             int force_splits = 0, int phase_mask = 3);
 
+// The backward (mha_hd64_backward.hip): dQ, dK, dV of one call from Q, K, V, the saved O and dO, all
+// [batch, heads, n, 64] of the type `in` (gradients: fp16 for fp16 inputs, fp32 for fp32 inputs).
+struct BwdCall {
+    const void* q;
+    const void* k;
+    const void* v;
+    const void* o;
+    const void* dout;
+    void* dq;
+    void* dk;
+    void* dv;
+    int batch;
+    int heads;
+    int nq;
+    int nkv;
+};
+// Its plan: 64-row / 64-key blocks, the column kernel's query split, and the workspace layout
+// [L][D] (fp32 [B, H, nq] each) [fp16 copies of Q, O, dO, K, V: fp32 inputs] [split partials of dK, dV].
+struct BwdPlan {
+    int qtiles;
+    int ktiles;
+    int splits;
+    int tiles_per_split;
+    size_t stats_bytes;
+    size_t copy_bytes;
+    size_t part_bytes;
+    size_t ws_bytes;
+};
+BwdPlan plan_backward(int batch, int heads, int nq, int nkv, InType in);
+// No allocation, no synchronisation: capturable. workspace holds plan_backward(...).ws_bytes.
+hipError_t launch_backward(const BwdCall& c, InType in, void* workspace, hipStream_t stream);
+
 // Record an error for mha_hd64_last_error() (and abort if abort-on-error is set); returns status.
 int32_t report_error(int32_t status, const char* where, const char* what);
 

@@ -318,6 +318,47 @@ size_t mha_hd64_launch_workspace_bytes_typed(int32_t batch, int32_t heads, int32
                                                                               : mha_hd64::InType::F16);
 }
 
+// ---- backward ----
+static int32_t run_backward(const mha_hd64::BwdCall& c, mha_hd64::InType in, void* ws, size_t ws_bytes,
+                            hipStream_t stream) {
+    MHA_CHECK(c.batch >= 0 && c.heads >= 0 && c.nq >= 0 && c.nkv >= 0);
+    if (c.batch == 0 || c.heads == 0 || c.nq == 0) return MHA_HD64_STATUS_SUCCESS;
+    MHA_CHECK(c.nkv >= 1);
+    // (a head's bytes fit a buffer descriptor; the grids, 16 splits at most, fit 31 bits)
+    MHA_CHECK(c.nq < (1 << 24) && c.nkv < (1 << 24));
+    MHA_CHECK((long long)c.batch * c.heads * ((c.nq > c.nkv ? c.nq : c.nkv) / 64 + 1) * 16 < (1ll << 31));
+    MHA_CHECK(c.q != nullptr && c.k != nullptr && c.v != nullptr && c.o != nullptr && c.dout != nullptr);
+    MHA_CHECK(c.dq != nullptr && c.dk != nullptr && c.dv != nullptr && ws != nullptr);
+    MHA_CHECK(((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v | (uintptr_t)c.o | (uintptr_t)c.dout | (uintptr_t)c.dq |
+               (uintptr_t)c.dk | (uintptr_t)c.dv | (uintptr_t)ws) % 16 == 0);
+    if (ws_bytes < mha_hd64::plan_backward(c.batch, c.heads, c.nq, c.nkv, in).ws_bytes)
+        return fail(MHA_HD64_STATUS_WORKSPACE, __FILE__, __LINE__,
+                    "workspace smaller than mha_hd64_backward_workspace_bytes");
+    return launch_status(mha_hd64::launch_backward(c, in, ws, stream), __FILE__, __LINE__);
+}
+
+int32_t mha_hd64_backward_fp16(const void* q, const void* k, const void* v, const void* o, const void* dout, void* dq,
+                               void* dk, void* dv, int32_t batch, int32_t heads, int32_t nq, int32_t nkv,
+                               void* workspace, size_t ws_bytes, hipStream_t stream) {
+    return run_backward(mha_hd64::BwdCall{q, k, v, o, dout, dq, dk, dv, batch, heads, nq, nkv}, mha_hd64::InType::F16,
+                        workspace, ws_bytes, stream);
+}
+
+int32_t mha_hd64_backward_fp32(const void* q, const void* k, const void* v, const void* o, const void* dout, void* dq,
+                               void* dk, void* dv, int32_t batch, int32_t heads, int32_t nq, int32_t nkv,
+                               void* workspace, size_t ws_bytes, hipStream_t stream) {
+    return run_backward(mha_hd64::BwdCall{q, k, v, o, dout, dq, dk, dv, batch, heads, nq, nkv}, mha_hd64::InType::F32,
+                        workspace, ws_bytes, stream);
+}
+
+size_t mha_hd64_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t nq, int32_t nkv, int32_t in_type) {
+    if (in_type != MHA_HD64_DT_HALF && in_type != MHA_HD64_DT_FLOAT) return 0;
+    if (batch <= 0 || heads <= 0 || nq <= 0 || nkv <= 0) return 0;
+    return mha_hd64::plan_backward(batch, heads, nq, nkv,
+                                   in_type == MHA_HD64_DT_FLOAT ? mha_hd64::InType::F32 : mha_hd64::InType::F16)
+        .ws_bytes;
+}
+
 // ---- grouped launcher ----
 static int32_t to_calls(const mha_hd64_call_t* calls, int32_t n, std::vector<mha_hd64::Call>& out) {
     MHA_CHECK(n >= 0 && (n == 0 || calls != nullptr));

@@ -4,6 +4,8 @@ PyTorch-ROCm module via a torch.library op that invokes enqueue on torch.cuda.cu
 * ``torch.ops.lightglue_amd.mha_hd64(q, k, v) -> o``: the plugin's ``enqueue`` (the TensorRT node
   ``CustomOp::MHAHeadDim64``, lightglue_pytorch_with_plugin/lightglue.py:16-46): [1, 4, N, 64],
   all fp16 (-> fp16) or all fp32 (-> fp32).
+* ``torch.ops.lightglue_amd.mha_hd64_backward(q, k, v, o, do) -> [dq, dk, dv]``: its gradient
+  (csrc/mha_hd64_backward.hip), registered as the autograd of ``mha_hd64``; [B, H, N, 64].
 * ``torch.ops.lightglue_amd.mha_hd64_grouped(qs, ks, vs) -> os``: up to any number of independent
   calls in grouped launches (4 per launch), e.g. the self0/self1 or the two cross directions of a
   LightGlue layer.
@@ -21,6 +23,7 @@ from typing import List
 import torch
 
 from .plugin import mha_hd64 as _enqueue
+from .plugin import mha_hd64_backward as _backward
 from .plugin import mha_hd64_grouped as _grouped
 
 
@@ -32,6 +35,31 @@ def mha_hd64_op(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor) -> 
 @mha_hd64_op.register_fake
 def _(query, key, value):
     return torch.empty_like(query, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("lightglue_amd::mha_hd64_backward", mutates_args=(), device_types="cuda")
+def mha_hd64_backward_op(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, out: torch.Tensor,
+                         dout: torch.Tensor) -> List[torch.Tensor]:
+    """(dQ, dK, dV) of mha_hd64 from its inputs, its output and dO (mha_hd64_backward_fp16 / _fp32)."""
+    return list(_backward(query.contiguous(), key.contiguous(), value.contiguous(), out.contiguous(), dout.contiguous()))
+
+
+@mha_hd64_backward_op.register_fake
+def _(query, key, value, out, dout):
+    return [torch.empty_like(t, memory_format=torch.contiguous_format) for t in (query, key, value)]
+
+
+def _mha_hd64_setup_context(ctx, inputs, output):
+    ctx.save_for_backward(*inputs, output)
+
+
+def _mha_hd64_backward(ctx, dout):
+    dq, dk, dv = torch.ops.lightglue_amd.mha_hd64_backward(*ctx.saved_tensors, dout)
+    need = ctx.needs_input_grad
+    return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None
+
+
+mha_hd64_op.register_autograd(_mha_hd64_backward, setup_context=_mha_hd64_setup_context)
 
 
 @torch.library.custom_op("lightglue_amd::mha_hd64_grouped", mutates_args=(), device_types="cuda")

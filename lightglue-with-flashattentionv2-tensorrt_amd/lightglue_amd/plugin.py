@@ -311,6 +311,48 @@ def mha_hd64_batched(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor
     return out
 
 
+_BACKWARD = {torch.float16: "mha_hd64_backward_fp16", torch.float32: "mha_hd64_backward_fp32"}
+
+
+def mha_hd64_backward(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, out: torch.Tensor,
+                      dout: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Gradient of O = softmax(Q·Kᵀ/8)·V on the current stream (csrc/mha_hd64_backward.hip): (dQ, dK, dV)
+    from Q, K, V, the forward's output O and dO. Contiguous [B, H, N, 64] tensors of one dtype, float16 or
+    float32 (float32: inputs rounded to fp16 as the forward does, fp32 gradients of that function).
+    Deterministic (no atomics) and capturable."""
+    _require_gpu(query, key, value, out, dout)
+    fn_name = _BACKWARD.get(query.dtype)
+    if fn_name is None:
+        raise PluginError(f"unsupported dtype {query.dtype}: the backward takes float16 or float32")
+    for t in (query, key, value, out, dout):
+        if not t.is_contiguous() or t.dim() != 4 or t.shape[-1] != 64 or t.dtype != query.dtype:
+            raise PluginError("expected contiguous [B, H, N, 64] tensors of one dtype")
+    if key.shape != value.shape or key.shape[:2] != query.shape[:2] or out.shape != query.shape or dout.shape != query.shape:
+        raise PluginError("shape mismatch in the backward call")
+    b, h, nq, _ = query.shape
+    nkv = key.shape[2]
+    dq, dk, dv = torch.empty_like(query), torch.empty_like(key), torch.empty_like(value)
+    lib = _lib.load()
+    stream = stream_of(query)
+    nbytes = lib.mha_hd64_backward_workspace_bytes(b, h, nq, nkv, DT[query.dtype])
+    ws = _workspace(query.device, stream, nbytes) if nbytes else None
+    status = getattr(lib, fn_name)(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                                   dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), b, h, nq, nkv,
+                                   ws.data_ptr() if ws is not None else None, nbytes, stream)
+    _check(status, fn_name)
+    return dq, dk, dv
+
+
+def attention_backward_reference(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, dout: torch.Tensor):
+    """(dQ, dK, dV) of O = softmax(Q·Kᵀ/8)·V in float64 framework ops, closed form, on the inputs as given:
+    D = Σ_d dO·O, dV = Pᵀ·dO, dP = dO·Vᵀ, dS = P∘(dP − D), dQ = dS·K/8, dK = dSᵀ·Q/8."""
+    q, k, v, do = (t.double() for t in (query, key, value, dout))
+    p = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
+    d = (do * (p @ v)).sum(-1, keepdim=True)
+    ds = p * (do @ v.transpose(-1, -2) - d)
+    return ds @ k * 0.125, ds.transpose(-1, -2) @ q * 0.125, p.transpose(-1, -2) @ do
+
+
 def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None):
     """Grouped launcher: several independent calls [(q, k, v), ...] of possibly different shapes
     ([B, H, Nq_i, 64] / [B, H, Nkv_i, 64]) in one launch (up to 4 per launch, chunked beyond).
@@ -397,7 +439,15 @@ class MHAHeadDim64(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, query, key, value):
-        return torch.ops.lightglue_amd.mha_hd64(query, key, value)  # ops.py: enqueue on the current stream
+        out = torch.ops.lightglue_amd.mha_hd64(query, key, value)  # ops.py: enqueue on the current stream
+        ctx.save_for_backward(query, key, value, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dq, dk, dv = torch.ops.lightglue_amd.mha_hd64_backward(*ctx.saved_tensors, dout)
+        need = ctx.needs_input_grad
+        return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None
 
 
 class Attention(nn.Module):
