@@ -247,6 +247,24 @@ int32_t lg_assign_matches_lens(const void* v, int64_t pair_stride, int32_t ld, i
                                int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1, int32_t* matches,
                                float* mscores, int32_t* counts, void* workspace, hipStream_t stream);
 
+/* ---- the assignment loss (csrc/lightglue_assign_nll.hip) ----
+ * The published LightGlue training loss (balancing 0.5) of the scores lg_assign_scores writes, and its
+ * gradient in v. New symbols only: LG_GLUE_ABI_VERSION stays 4. v, pair_stride, ld, zc, m, n, batch,
+ * m_len / n_len (device, nullable) and the limits are lg_assign_scores_lens' (m, n >= 1).
+ * gt0 int32 [batch][m] (device): j >= 0: row i matches column j; -1: unmatchable; any other negative:
+ * ignored, as is j >= the pair's n_len and every row or column past the pair's counts. gt1 int32 [batch][n]
+ * is read for its -1 entries (unmatchable columns). gt0 need not be injective. Per pair, with
+ * s = log_softmax(sim, 2) + log_softmax(sim, 1) + logsig(z0) + logsig(z1)^T, sim = fp16(m0 . m1^T):
+ *   loss = -0.5/Pn sum_pos s[i][gt0[i]] - 0.5/Nn (sum_{gt0 == -1} logsig(-z0[i]) + sum_{gt1 == -1} logsig(-z1[j]))
+ * Pn = max(#pos, 1), Nn = max(#{gt0 == -1} + #{gt1 == -1}, 1). loss fp32 [batch]; dv fp32
+ * [batch][m + n][ld] = dloss/dv (the rounding of sim passed straight through), every element written
+ * (zeros in channels 256.. other than zc and on padded rows), or null: the loss only. 16-B alignment
+ * of v, dv and workspace. No float atomics, no host synchronisation: capturable, bitwise reproducible. */
+size_t lg_assign_nll_workspace(int32_t m, int32_t n, int32_t batch);
+int32_t lg_assign_nll(const void* v, int64_t pair_stride, int32_t ld, int32_t zc, int32_t m, int32_t n, int32_t batch,
+                      const int32_t* m_len, const int32_t* n_len, const int32_t* gt0, const int32_t* gt1, float* loss,
+                      float* dv, void* workspace, hipStream_t stream);
+
 /* ---- adaptive depth and width (csrc/lightglue_adaptive.hip; fp16 rows of 256 channels) ----
  * The published LightGlue rules the reference ships the pieces of (TokenConfidence lightglue.py:54-66,
  * MatchAssignment.get_matchability :230-232) and never applies. New symbols only: LG_GLUE_ABI_VERSION

@@ -224,6 +224,26 @@ class _Hip:
              ws.data_ptr(), stream)
         return out
 
+    @staticmethod
+    def assign_nll(v, m, zc, gt0, gt1, lens=None, need_grad=True, out=None):
+        """v as for assign_scores, gt0 int32 [P, m] (column, -1 unmatchable, other negatives ignored), gt1 int32
+        [P, n] (read for its -1 entries) -> (loss fp32 [P], dv fp32 [P, m + n, C] = dloss/dv, or None without
+        need_grad): lg_assign_nll, the LightGlue training loss of the scores assign_scores writes. out = (loss, dv):
+        tensors to write instead of new ones."""
+        pr, n, ch = v.shape[0], v.shape[1] - m, v.shape[2]
+        lib = _lib.load()
+        if out is not None:
+            loss, dv = out
+        else:
+            loss = torch.empty((pr,), dtype=torch.float32, device=v.device)
+            dv = torch.empty((pr, m + n, ch), dtype=torch.float32, device=v.device) if need_grad else None
+        stream = stream_of(v)
+        ws = _workspace(v.device, stream, lib.lg_assign_nll_workspace(m, n, pr))
+        tables = (None, None) if lens is None else [t.data_ptr() for t in lens]
+        call("lg_assign_nll", v.data_ptr(), (m + n) * ch, ch, zc, m, n, pr, *tables, gt0.data_ptr(), gt1.data_ptr(),
+             loss.data_ptr(), _ptr(dv), ws.data_ptr(), stream)
+        return loss, dv
+
     # ---- adaptive depth / width (csrc/lightglue_adaptive.hip) ----
     @staticmethod
     def token_scores(x, m, n, pr, lens, w_tok, b_tok, w_match, b_match, t_conf, t_keep, flags):

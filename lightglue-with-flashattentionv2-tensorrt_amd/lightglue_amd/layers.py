@@ -281,6 +281,15 @@ class MatchAssignment(nn.Module):
         scores tensor (filter_matches_dense's semantics on the scores forward_rows would return)."""
         return _Hip.assign_matches(self.project_rows(x, pr, m, n), m, x.shape[-1], threshold)
 
+    def loss_rows(self, x: torch.Tensor, pr: int, m: int, n: int, gt0: torch.Tensor, gt1: torch.Tensor,
+                  lens=None) -> torch.Tensor:
+        """forward_rows' projection, then lg_assign_nll (loss.assignment_nll): the training loss of the scores
+        forward_rows would return, fp32 [P]. The gradient stops at v: project_rows has no backward yet, so
+        this trains nothing upstream of the head by itself; take dloss/dv from assignment_nll on a leaf v."""
+        from .loss import assignment_nll
+
+        return assignment_nll(self.project_rows(x, pr, m, n), m, x.shape[-1], gt0, gt1, lens)
+
     def forward(self, d0: torch.Tensor, d1: torch.Tensor, hip: bool = False) -> torch.Tensor:
         m0 = self.final_proj(d0) / self.scale
         m1 = self.final_proj(d1) / self.scale

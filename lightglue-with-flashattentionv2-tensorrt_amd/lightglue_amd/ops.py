@@ -13,12 +13,15 @@ PyTorch-ROCm module via a torch.library op that invokes enqueue on torch.cuda.cu
   ``mha_hd64_grouped_qkv_lens(qs, ks, vs, q_lens, kv_lens)``: the same on ragged batches, with int32
   device tables of per-item key (and query-row) counts (fp16 only).
 
+* ``torch.ops.lightglue_amd.assign_nll(v, m, zc, gt0, gt1, m_len=None, n_len=None) -> [loss, dv]``: the matcher's
+  training loss per pair and its gradient in v (csrc/lightglue_assign_nll.hip), differentiable in v.
+
 Only a CUDA (HIP) kernel is registered: a CPU tensor has no implementation to dispatch to and
 raises (no CPU fallback). The fake (meta) implementations give shapes/dtypes for tracing.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -100,3 +103,33 @@ def mha_hd64_grouped_qkv_lens_op(queries: List[torch.Tensor], keys: List[torch.T
 @mha_hd64_grouped_qkv_lens_op.register_fake
 def _(queries, keys, values, q_lens, kv_lens):
     return [torch.empty_like(q, memory_format=torch.contiguous_format) for q in queries]
+
+
+@torch.library.custom_op("lightglue_amd::assign_nll", mutates_args=(), device_types="cuda")
+def assign_nll_op(v: torch.Tensor, m: int, zc: int, gt0: torch.Tensor, gt1: torch.Tensor,
+                  m_len: Optional[torch.Tensor] = None, n_len: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """(loss fp32 [P], dloss/dv fp32 [P, m + n, C]) of the assignment head's input v (lg_assign_nll: loss.py)."""
+    from .glue import _Hip
+
+    lens = None if m_len is None else (m_len, n_len)
+    return list(_Hip.assign_nll(v.contiguous(), m, zc, gt0.contiguous(), gt1.contiguous(), lens))
+
+
+@assign_nll_op.register_fake
+def _(v, m, zc, gt0, gt1, m_len=None, n_len=None):
+    return [v.new_empty((v.shape[0],), dtype=torch.float32), torch.empty_like(v, dtype=torch.float32,
+                                                                              memory_format=torch.contiguous_format)]
+
+
+def _assign_nll_setup_context(ctx, inputs, output):
+    ctx.v_dtype = inputs[0].dtype
+    ctx.save_for_backward(output[1])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _assign_nll_backward(ctx, grads):
+    (dv,) = ctx.saved_tensors
+    return (dv * grads[0][:, None, None]).to(ctx.v_dtype), None, None, None, None, None, None
+
+
+assign_nll_op.register_autograd(_assign_nll_backward, setup_context=_assign_nll_setup_context)
