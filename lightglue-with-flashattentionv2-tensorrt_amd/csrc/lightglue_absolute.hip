@@ -94,7 +94,7 @@ __global__ __launch_bounds__(kHypThreads) void absolute_hypothesis_kernel(AbsArg
         p3p_setup(x, px, cam, s);
         double u;
         const bool has = p3p_root(s, sub, u);
-        AbsPose q;
+        Pose q;
         ok = p3p_pose(s, x, u, q.r, q.t, key) && has;
         float rounded[12];
         ok = absolute_round(q, rounded) && ok;
@@ -170,7 +170,7 @@ __device__ __forceinline__ int mark_abs(const float pose[12], const Camera& cam,
 // residual at a positive depth, which also defines fixed[k] : fixed[k]), the same bits in every thread. A thread reads
 // only the fixed[] entries it wrote. part: [kFinThreads / 64][kAbsSums] in LDS.
 template <bool FIRST>
-__device__ __forceinline__ void absolute_pass(const AbsPose& q, const Camera& cam, const float4* pa, const float* pb,
+__device__ __forceinline__ void absolute_pass(const Pose& q, const Camera& cam, const float4* pa, const float* pb,
                                               const uint8_t* mask, uint8_t* fixed, int count, double (*part)[kAbsSums], int tid,
                                               double sums[kAbsSums]) {
     double acc[kAbsSums];
@@ -189,16 +189,9 @@ __device__ __forceinline__ void absolute_pass(const AbsPose& q, const Camera& ca
         absolute_accumulate(acc, res, j);
     }
     __syncthreads();  // (the last pass's readers of part are done)
-#pragma unroll
-    for (int e = 0; e < kAbsSums; ++e) {
-        double v = acc[e];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-        if (tid % 64 == 0) part[tid / 64][e] = v;
-    }
+    wave_sums<kAbsSums>(acc, part, tid);
     __syncthreads();
-#pragma unroll
-    for (int e = 0; e < kAbsSums; ++e) sums[e] = ((part[0][e] + part[1][e]) + part[2][e]) + part[3][e];
+    waves_total<kAbsSums>(part, sums);
 }
 
 __global__ __launch_bounds__(kFinThreads) void absolute_finalize_kernel(AbsArgs a, int hypotheses, int refits, float thr2,
@@ -250,30 +243,15 @@ __global__ __launch_bounds__(kFinThreads) void absolute_finalize_kernel(AbsArgs 
         // (everything below that decides a branch is the same in every thread of the workgroup)
 #pragma unroll 1
         for (int round = 0; round < refits && num >= kMinInliersA; ++round) {
-            AbsPose st;
+            Pose st;
             if (!absolute_enter(pose, st)) break;
             double sums[kAbsSums];
             absolute_pass<true>(st, cam, pa, pb, mask, fixed, count, part, tid, sums);
-            if (!((int)sums[28] >= kMinAbsRows && finite64(sums[27]))) break;
-            double lambda = kLambdaStart;
-#pragma unroll 1
-            for (int it = 0; it < kAbsoluteLmRounds; ++it) {
-                double delta[6];
-                bool take = absolute_step(sums, lambda, delta);
-                if (take) {  // (a rejected solve spares the pass)
-                    AbsPose next;
-                    double again[kAbsSums];
-                    absolute_update(st, delta, next);
-                    absolute_pass<false>(next, cam, pa, pb, mask, fixed, count, part, tid, again);
-                    take = finite64(again[27]) && again[27] < sums[27];
-                    if (take) {
-                        st = next;
-#pragma unroll
-                        for (int e = 0; e < kAbsSums; ++e) sums[e] = again[e];
-                    }
-                }
-                lambda = take ? fmax(lambda * 0.1, kLambdaMin) : fmin(lambda * 10.0, kLambdaMax);
-            }
+            if (!((int)sums[AbsLm::kRows] >= kMinAbsRows && finite64(sums[AbsLm::kCost]))) break;
+            lm_rounds<6>(
+                st, sums, kAbsoluteLmRounds,
+                [&](const Pose& q, double* again) { absolute_pass<false>(q, cam, pa, pb, mask, fixed, count, part, tid, again); },
+                [](const Pose& q, const double* delta, Pose& next) { absolute_update(q, delta, next); });
             float fine[12];
             if (!absolute_round(st, fine)) break;  // a refit that is not finite keeps the previous pose and mask
             const int again = mark_abs(fine, cam, pa, pb, count, thr2, trial, buf, tid);

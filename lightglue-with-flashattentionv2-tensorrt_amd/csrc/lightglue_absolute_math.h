@@ -3,7 +3,8 @@
 // inlier test, and the pieces of the Levenberg-Marquardt refit on the 6 parameters of (R, t). The style is
 // lightglue_essential_math.h's: plain __host__ __device__ functions on values and small fixed-size arrays, every index
 // a compile-time constant after unrolling, selection by selects, every loop with a compile-time bound. From
-// lightglue_polish_math.h: finite64, cross_mul, sinc64 and the λ constants.
+// lightglue_lm_math.h: Pose, Camera, polar_step, rodrigues_update, the sums' layout LmSums<6> with lm_accumulate
+// (the step and the rounds are lm_step<6> and lm_rounds<6> there), finite64.
 //
 // The P3P route. Bearings f_i: the unit vectors of ((x - cx) / fx, (y - cy) / fy, 1); c_ij = f_i . f_j; the map
 // distances over the first: E = |X1 - X3|² / |X1 - X2|², F = |X2 - X3|² / |X1 - X2|². With the camera distances
@@ -21,7 +22,7 @@
 // anything not finite, or a sample triangle of area below kAreaEps of its longest side squared.
 #pragma once
 
-#include "lightglue_polish_math.h"
+#include "lightglue_lm_math.h"
 
 namespace lg_geom {
 
@@ -31,13 +32,10 @@ constexpr double kAreaEps = 1e-6;      // the sample triangle's area over its lo
 constexpr int kAbsBisections = 40;     // per piece: its width falls to 2^-40 of the root bound
 constexpr int kAbsNewton = 4;          // then Newton steps that may not leave the bracket
 constexpr int kAbsoluteLmRounds = 4;   // Levenberg-Marquardt rounds a refit (profiles/geometry/INDEX.md has the table)
-constexpr int kAbsSums = 29;           // JᵀJ's upper triangle (21), Jᵀr (6), Σ |r|² and the number of rows
+using AbsLm = LmSums<6>;               // JᵀJ's upper triangle (21), Jᵀr (6), Σ |r|² and the number of rows
+constexpr int kAbsSums = AbsLm::kCount;
 constexpr int kMinAbsRows = 3;         // the fixed set needs as many residuals as there are parameters
 constexpr int kAbsRecord = 16;         // floats per hypothesis in the workspace: R[9], t[3], count, pad
-
-struct Camera {  // (fx, fy, cx, cy) of the one camera
-    float fx, fy, cx, cy;
-};
 
 LG_HD bool camera_ok(const Camera& k) {
     return fabsf(k.fx) < INFINITY && fabsf(k.fy) < INFINITY && fabsf(k.cx) < INFINITY && fabsf(k.cy) < INFINITY && k.fx > 0.f &&
@@ -199,38 +197,22 @@ LG_HD bool p3p_pose(const P3p& s, const double x[3][3], double u, double r[9], d
 }
 
 // ---- the Levenberg-Marquardt refit --------------------------------------------------------------------------------
-struct AbsPose {
-    double r[9], t[3];
-};
-
-// The entering pose from one in fp32: R one Newton step of the polar iteration nearer the rotations (polish_enter's).
-// False where R or t is not finite.
-LG_HD bool absolute_enter(const float p[12], AbsPose& s) {
+// The entering pose from one in fp32: R one polar_step nearer the rotations. False where R or t is not finite.
+LG_HD bool absolute_enter(const float p[12], Pose& s) {
     bool ok = true;
     double m[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) m[k] = (double)p[k], ok = ok && finite64(m[k]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) s.t[k] = (double)p[9 + k], ok = ok && finite64(s.t[k]);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double v = 0.0;  // (R (3 I - Rᵀ R))[i][j]
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double g = m[k] * m[j] + m[3 + k] * m[3 + j] + m[6 + k] * m[6 + j];
-                v += m[3 * i + k] * ((k == j ? 3.0 : 0.0) - g);
-            }
-            s.r[3 * i + j] = 0.5 * v;
-        }
+    polar_step(m, s.r);
     return ok;
 }
 
 // The residual (px) of a row and its two Jacobian rows over (ω, δt): with Y = R X, Xc = Y + t,
 // u = fx Xc.x / Xc.z + cx, ∂u/∂Xc = a = (fx / z, 0, -fx Xc.x / z²), ∂u/∂ω = Y x a, ∂u/∂t = a; v alike. False where the
 // depth is not positive or the residual not finite.
-LG_HD bool absolute_row(const AbsPose& q, const Camera& k, double X, double Y, double Z, double x, double y, double res[2],
+LG_HD bool absolute_row(const Pose& q, const Camera& k, double X, double Y, double Z, double x, double y, double res[2],
                         double j[2][6]) {
     const double y0 = q.r[0] * X + q.r[1] * Y + q.r[2] * Z, y1 = q.r[3] * X + q.r[4] * Y + q.r[5] * Z;
     const double y2 = q.r[6] * X + q.r[7] * Y + q.r[8] * Z;
@@ -245,83 +227,22 @@ LG_HD bool absolute_row(const AbsPose& q, const Camera& k, double X, double Y, d
     return zc > 0.0 && finite64(res[0]) && finite64(res[1]);
 }
 
-// acc += the row's part of the kAbsSums sums: JᵀJ's upper triangle row by row, Jᵀr, |r|² and 1.
+// acc += the row's part of the kAbsSums sums: its two residuals in turn, then the row.
 LG_HD void absolute_accumulate(double acc[kAbsSums], const double res[2], const double j[2][6]) {
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-        int e = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) acc[e] = fma(j[w][a], j[w][b], acc[e]), ++e;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] = fma(j[w][a], res[w], acc[21 + a]);
-        acc[27] = fma(res[w], res[w], acc[27]);
-    }
-    acc[28] += 1.0;
+    lm_accumulate<6>(acc, res[0], j[0]);
+    lm_accumulate<6>(acc, res[1], j[1]);
+    acc[AbsLm::kRows] += 1.0;
 }
 
-// The Levenberg-Marquardt step of the sums: (JᵀJ + λ diag(JᵀJ)) δ = -Jᵀr by a 6 x 6 Cholesky factorisation
-// (polish_step's statements at another size). False where a pivot is not positive or not finite.
-LG_HD bool absolute_step(const double sums[kAbsSums], double lambda, double delta[6]) {
-    double l[6][6];
-    int e = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b) l[b][a] = sums[e] * (a == b ? 1.0 + lambda : 1.0), ++e;
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double piv = l[c][c];
-#pragma unroll
-        for (int k = 0; k < c; ++k) piv = fma(-l[c][k], l[c][k], piv);
-        ok = ok && piv > 0.0 && finite64(piv);  // (NaN: false)
-        const double root = sqrt(piv), inv = 1.0 / root;
-        l[c][c] = root;
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            double v = l[r][c];
-#pragma unroll
-            for (int k = 0; k < c; ++k) v = fma(-l[r][k], l[c][k], v);
-            l[r][c] = v * inv;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        double v = -sums[21 + r];
-#pragma unroll
-        for (int k = 0; k < r; ++k) v = fma(-l[r][k], y[k], v);
-        y[r] = v / l[r][r];
-    }
-#pragma unroll
-    for (int r = 5; r >= 0; --r) {
-        double v = y[r];
-#pragma unroll
-        for (int k = r + 1; k < 6; ++k) v = fma(-l[k][r], delta[k], v);
-        delta[r] = v / l[r][r];
-        ok = ok && finite64(delta[r]);
-    }
-    return ok;
-}
-
-// The trial pose: R <- exp([ω]x) R by the Rodrigues formula (polish_update's), t <- t + δt.
-LG_HD void absolute_update(const AbsPose& s, const double delta[6], AbsPose& out) {
-    const double w[3] = {delta[0], delta[1], delta[2]};
-    const double theta = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    const double ka = sinc64(theta), kh = sinc64(0.5 * theta), kb = 0.5 * kh * kh;
-    double g[9], h[9];
-    cross_mul(w, s.r, g);
-    cross_mul(w, g, h);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) out.r[k] = s.r[k] + ka * g[k] + kb * h[k];
+// The trial pose: R <- exp([ω]x) R (rodrigues_update), t <- t + δt.
+LG_HD void absolute_update(const Pose& s, const double delta[6], Pose& out) {
+    rodrigues_update(s.r, delta, out.r);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out.t[k] = s.t[k] + delta[3 + k];
 }
 
 // The pose rounded to the output's fp32 (R row-major then t); false where an entry is not finite there.
-LG_HD bool absolute_round(const AbsPose& s, float p[12]) {
+LG_HD bool absolute_round(const Pose& s, float p[12]) {
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 9; ++k) p[k] = (float)s.r[k], ok = ok && fabsf(p[k]) < INFINITY;

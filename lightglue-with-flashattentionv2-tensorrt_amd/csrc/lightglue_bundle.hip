@@ -6,7 +6,7 @@
 // bundle_adjust_kernel: one workgroup of 256 threads per window. A thread is an observation slot: thread tid is view
 // tid % 8 of the landmark tid / 8 of the current tile of 32 landmarks, so a wave holds 8 landmarks and the 8 views of a
 // landmark are 8 adjacent lanes. A landmark's 3 x 3 block V and its gradient are added over its 8 lanes by an xor
-// butterfly (every lane ends with the same bits, no LDS); each lane inverts the damped block alike, forms its own
+// butterfly (lanes_sum: every lane ends with the same bits, no LDS); each lane inverts the damped block alike, forms its own
 // W_vl = J_cᵀ J_x (6 x 3) and Y_vl = W_vl V*⁻¹ and keeps its view's sums (U's upper triangle, g_c, Σ Y g_x, Σ r²) in
 // registers. The poses are fp64 in LDS, the points and the trial points fp64 in the workspace; observations are read in
 // place.
@@ -60,7 +60,7 @@ struct BaShared {
     int flag[kMaxViews];
 };
 
-__device__ __forceinline__ void load_pose(const double* p, AbsPose& q) {
+__device__ __forceinline__ void load_pose(const double* p, Pose& q) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) q.r[k] = p[k];
 #pragma unroll
@@ -69,14 +69,6 @@ __device__ __forceinline__ void load_pose(const double* p, AbsPose& q) {
 
 __device__ __forceinline__ double sum4(const double (*part)[kMaxViews][kBaSums], int v, int e) {
     return ((part[0][v][e] + part[1][v][e]) + part[2][v][e]) + part[3][v][e];
-}
-
-// The sum over the 8 lanes of a landmark, the same bits in each (an addition is commutative, so both lanes of a pair
-// compute the same sum at every level).
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-    for (int d = 1; d < kMaxViews; d <<= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // What both passes derive for a thread's observation slot at the current state: the row (zeros where the slot is not in
@@ -88,7 +80,7 @@ struct BaSlot {
 };
 
 template <bool FIRST>
-__device__ __forceinline__ void slot_at(const BaArgs& a, int b, int count, int l, int v, const AbsPose& q, const Camera& cam,
+__device__ __forceinline__ void slot_at(const BaArgs& a, int b, int count, int l, int v, const Pose& q, const Camera& cam,
                                         const double sb[2][3], double lambda, const double* pts, uint8_t* fset, BaSlot& s) {
     s.inb = l < a.lmax;
     const int lc = s.inb ? l : 0;
@@ -131,9 +123,9 @@ __device__ __forceinline__ void slot_at(const BaArgs& a, int b, int count, int l
     s.gx[0] = s.gx[1] = s.gx[2] = 0.0;
     bundle_point_add(vv, s.gx, s.res, s.jx);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) vv[k] = group_sum(vv[k]);
+    for (int k = 0; k < 6; ++k) vv[k] = lanes_sum<kMaxViews>(vv[k]);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s.gx[k] = group_sum(s.gx[k]);
+    for (int k = 0; k < 3; ++k) s.gx[k] = lanes_sum<kMaxViews>(s.gx[k]);
     s.inverted = bundle_point_inverse(vv, lambda, s.inv);
 #pragma unroll
     for (int k = 0; k < 6; ++k) s.inv[k] = s.live && s.inverted ? s.inv[k] : 0.0;
@@ -145,7 +137,7 @@ template <bool FIRST>
 __device__ __forceinline__ void build_pass(const BaArgs& a, int b, int count, int cur, double scale, double lambda, double* pts,
                                            BaShared& sh, int tid) {
     const int v = tid % kMaxViews, li = tid / kMaxViews, wave = tid / 64, lane = tid % 64, lw = li % (kBaTile / 4);
-    AbsPose q;
+    Pose q;
     load_pose(sh.pose[cur][v], q);
     const float* kp = a.intr + ((size_t)b * a.views + (v < a.views ? v : 0)) * 4;
     const Camera cam{kp[0], kp[1], kp[2], kp[3]};
@@ -180,9 +172,9 @@ __device__ __forceinline__ void build_pass(const BaArgs& a, int b, int count, in
         bundle_w(s.jc, s.jx, s.inv, w, y);
         if (s.in) {
             bundle_view_add(acc, s.res, s.jc, y, s.gx);
-            acc[34] += 1.0;
+            acc[kBaObs] += 1.0;
         }
-        if (v == 0 && s.live && !s.inverted) acc[35] += 1.0;
+        if (v == 0 && s.live && !s.inverted) acc[kBaBad] += 1.0;
 #pragma unroll
         for (int r = 0; r < 7; ++r) {
             if (r >= rows) continue;
@@ -260,7 +252,7 @@ __device__ __forceinline__ void build_pass(const BaArgs& a, int b, int count, in
         if (vv < 1 || vv >= a.views || r >= bundle_width(vv) || k >= bundle_width(vv)) continue;
         const double u = sum4(sh.part, vv, upper6(min(r, k), max(r, k)));
         sh.s[bundle_row0(vv) + r][bundle_row0(vv) + k] += r == k ? u * (1.0 + lambda) : u;
-        if (k == 0) sh.rhs[bundle_row0(vv) + r] = -(sum4(sh.part, vv, 21 + r) - sum4(sh.part, vv, 27 + r));
+        if (k == 0) sh.rhs[bundle_row0(vv) + r] = -(sum4(sh.part, vv, BaLm::kGrad + r) - sum4(sh.part, vv, kBaYg + r));
     }
     __syncthreads();
 }
@@ -310,7 +302,7 @@ __device__ __forceinline__ bool solve_system(BaShared& sh, int n, int tid) {
 __device__ __forceinline__ double trial_pass(const BaArgs& a, int b, int cur, double scale, double lambda, const double* pts,
                                              double* trial, BaShared& sh, int tid) {
     const int v = tid % kMaxViews, li = tid / kMaxViews, wave = tid / 64, lane = tid % 64;
-    AbsPose q, qn;
+    Pose q, qn;
     load_pose(sh.pose[cur][v], q);
     load_pose(sh.pose[1 - cur][v], qn);
     const float* kp = a.intr + ((size_t)b * a.views + (v < a.views ? v : 0)) * 4;
@@ -332,7 +324,7 @@ __device__ __forceinline__ double trial_pass(const BaArgs& a, int b, int cur, do
             double x = 0.0;
 #pragma unroll
             for (int r = 0; r < 6; ++r) x = fma(s.jc[0][r] * s.jx[0][k] + s.jc[1][r] * s.jx[1][k], d[r], x);
-            wd[k] = s.gx[k] + group_sum(x);
+            wd[k] = s.gx[k] + lanes_sum<kMaxViews>(x);
         }
         sym3_mul(s.inv, wd, dx);  // (zeros where the landmark is not live)
 #pragma unroll
@@ -376,7 +368,7 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(BaArgs a, dou
                 for (int k = 0; k < 3; ++k) p[9 + k] = a.t[((size_t)b * a.views + tid) * 3 + k];
             }
         }
-        AbsPose q;
+        Pose q;
         ok = absolute_enter(p, q) && ok;
         if (tid == 1) ok = ok && (p[9] != 0.f || p[10] != 0.f || p[11] != 0.f);
 #pragma unroll
@@ -404,24 +396,24 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(BaArgs a, dou
         bool enough = true;
 #pragma unroll
         for (int v = 0; v < kMaxViews; ++v) {
-            const int mine = (int)sum4(sh.part, v, 34);  // (exact: integers below 2^53)
-            cost += sum4(sh.part, v, 33), nobs += mine;
+            const int mine = (int)sum4(sh.part, v, kBaObs);  // (exact: integers below 2^53)
+            cost += sum4(sh.part, v, BaLm::kCost), nobs += mine;
             enough = enough && (v < 1 || v >= a.views || mine >= kMinViewObs);
         }
-        bad = sum4(sh.part, 0, 35);
+        bad = sum4(sh.part, 0, kBaBad);
         cost0 = cost1 = cost;
         if (enough && finite64(cost)) {
 #pragma unroll 1
             for (int round = 0; round < a.iterations; ++round) {
                 if (round > 0) {
                     build_pass<false>(a, b, count, cur, scale, lambda, pts, sh, tid);
-                    bad = sum4(sh.part, 0, 35);
+                    bad = sum4(sh.part, 0, kBaBad);
                 }
                 bool take = bad == 0.0;
                 if (take) take = solve_system(sh, n, tid);
                 if (take) {  // (a rejected solve spares the pass)
                     if (tid >= 1 && tid < a.views) {
-                        AbsPose q, next;
+                        Pose q, next;
                         double d[6];
                         load_pose(sh.pose[cur][tid], q);
 #pragma unroll
@@ -434,14 +426,14 @@ __global__ __launch_bounds__(kBaThreads) void bundle_adjust_kernel(BaArgs a, dou
                     }
                     __syncthreads();
                     const double again = trial_pass(a, b, cur, scale, lambda, pts, trial, sh, tid);
-                    take = finite64(again) && again < cost;
+                    take = lm_accept(again, cost);
                     if (take) {
                         cost = again, cur = 1 - cur, kept = true;
                         double* swap = pts;
                         pts = trial, trial = swap;
                     }
                 }
-                lambda = take ? fmax(lambda * 0.1, kLambdaMin) : fmin(lambda * 10.0, kLambdaMax);
+                lambda = lm_lambda(lambda, take);
             }
             cost1 = cost;
         }

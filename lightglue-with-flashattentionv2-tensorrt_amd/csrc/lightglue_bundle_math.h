@@ -3,9 +3,11 @@
 // analytic Jacobians over the view's parameters and over the landmark, the damped 3 x 3 landmark block and its inverse,
 // the parameter layout of a window, the views' updates and the Cholesky solve of the reduced camera system. All fp64.
 // The style is lightglue_absolute_math.h's: plain __host__ __device__ functions on values and small fixed-size arrays,
-// selection by selects, every loop with a compile-time bound. From lightglue_polish_math.h: tangent_basis,
-// polish_update (view 1's step in t's tangent plane), finite64 and the λ constants; from lightglue_absolute_math.h:
-// absolute_row (the residual and the Jacobian over (ω, δt)), absolute_enter, absolute_update.
+// selection by selects, every loop with a compile-time bound. From lightglue_lm_math.h: Pose, Camera, rodrigues_update,
+// LmSums<6> with lm_accumulate, chol3, lm_accept and lm_lambda (the rounds' rules), finite64; from
+// lightglue_polish_math.h: tangent_basis, tangent_move (view 1's step in t's tangent plane); from
+// lightglue_absolute_math.h: absolute_row (the residual and the Jacobian over (ω, δt)), absolute_enter, absolute_round,
+// camera_ok.
 //
 // The parameters of a window of V views: view 0 has none; view 1 has 5, (ω, τ1, τ2), at columns 0..4: its t keeps the
 // entering length s (the gauge), t = s u with u moving in its tangent plane, ∂t/∂τ_j = s b_j; view v >= 2 has 6,
@@ -13,6 +15,7 @@
 // view 1's sixth column is zeros and is never written into the system.
 #pragma once
 
+#include "lightglue_polish_math.h"
 #include "lightglue_absolute_math.h"
 
 namespace lg_geom {
@@ -22,15 +25,17 @@ constexpr int kMaxBundle = 32;         // rounds at most
 constexpr int kMinViewObs = 4;         // a view from 1 on needs as many observations of live landmarks
 constexpr int kBaParams = 41;          // 6 * kMaxViews - 7
 constexpr int kBaPad = 48;             // the parameters padded to three 16-row tiles
-constexpr int kBaSums = 36;            // a view's U upper triangle (21), g_c (6), Σ Y g_x (6), Σ r², its observations in the
-                                       // fixed set, and (view 0's) the landmark blocks that did not invert
+// A view's sums: U's upper triangle (21), g_c (6) and Σ r² as LmSums<6> lays them out, then Σ Y g_x (6), its observations
+// in the fixed set, and (view 0's) the landmark blocks that did not invert.
+using BaLm = LmSums<6>;
+constexpr int kBaYg = BaLm::kCost + 1, kBaObs = kBaYg + 6, kBaBad = kBaObs + 1, kBaSums = kBaBad + 1;
 
 LG_HD int bundle_params(int views) { return 6 * views - 7; }
 LG_HD int bundle_row0(int v) { return v <= 1 ? 0 : 5 + 6 * (v - 2); }   // the first column of view v's block
 LG_HD int bundle_width(int v) { return v == 0 ? 0 : (v == 1 ? 5 : 6); }
 
 // view 1's ∂t/∂τ: sb[j] = scale b_j for the tangent basis (b1, b2) of t / scale (a pass derives it from the pose once).
-LG_HD void bundle_basis(const AbsPose& q, double scale, double sb[2][3]) {
+LG_HD void bundle_basis(const Pose& q, double scale, double sb[2][3]) {
     double u[3], b[2][3];
     const double inv = 1.0 / scale;
 #pragma unroll
@@ -44,7 +49,7 @@ LG_HD void bundle_basis(const AbsPose& q, double scale, double sb[2][3]) {
 
 // An observation's row: res [2] (px), jc [2][6] over the view's block (zeros for view 0), jx [2][3] over the landmark.
 // sb: bundle_basis' (read for view 1 only). False where the depth is not positive or the residual not finite.
-LG_HD bool bundle_row(const AbsPose& q, const Camera& k, int v, const double sb[2][3], const double x[3], double px, double py,
+LG_HD bool bundle_row(const Pose& q, const Camera& k, int v, const double sb[2][3], const double x[3], double px, double py,
                       double res[2], double jc[2][6], double jx[2][3]) {
     double j[2][6];
     const bool ok = absolute_row(q, k, x[0], x[1], x[2], px, py, res, j);
@@ -65,7 +70,7 @@ LG_HD bool bundle_row(const AbsPose& q, const Camera& k, int v, const double sb[
 }
 
 // The residual alone (the trial's cost). False as bundle_row.
-LG_HD bool bundle_residual(const AbsPose& q, const Camera& k, const double x[3], double px, double py, double res[2]) {
+LG_HD bool bundle_residual(const Pose& q, const Camera& k, const double x[3], double px, double py, double res[2]) {
     const double xc = q.r[0] * x[0] + q.r[1] * x[1] + q.r[2] * x[2] + q.t[0];
     const double yc = q.r[3] * x[0] + q.r[4] * x[1] + q.r[5] * x[2] + q.t[1];
     const double zc = q.r[6] * x[0] + q.r[7] * x[1] + q.r[8] * x[2] + q.t[2];
@@ -88,23 +93,15 @@ LG_HD void bundle_point_add(double vv[6], double gx[3], const double res[2], con
     }
 }
 
-// The inverse (upper triangle) of V* = V + λ diag V by a 3 x 3 Cholesky factorisation. False where a pivot is not
-// positive or not finite.
+// The inverse (upper triangle) of V* = V + λ diag V by chol3. False where a pivot is not positive or not finite.
 LG_HD bool bundle_point_inverse(const double vv[6], double lambda, double inv[6]) {
     const double d = 1.0 + lambda;
-    const double a00 = vv[0] * d, a01 = vv[1], a02 = vv[2], a11 = vv[3] * d, a12 = vv[4], a22 = vv[5] * d;
-    bool ok = a00 > 0.0 && finite64(a00);
-    const double l00 = sqrt(a00), i00 = 1.0 / l00;
-    const double l10 = a01 * i00, l20 = a02 * i00;
-    const double p1 = fma(-l10, l10, a11);
-    ok = ok && p1 > 0.0 && finite64(p1);
-    const double l11 = sqrt(p1), i11 = 1.0 / l11;
-    const double l21 = fma(-l20, l10, a12) * i11;
-    const double p2 = fma(-l21, l21, fma(-l20, l20, a22));
-    ok = ok && p2 > 0.0 && finite64(p2);
-    const double i22 = 1.0 / sqrt(p2);
+    const double a[6] = {vv[0] * d, vv[1], vv[2], vv[3] * d, vv[4], vv[5] * d};
+    Chol3 c;
+    const bool ok = chol3(a, c);
+    const double i00 = c.i00, i11 = c.i11, i22 = c.i22;
     // M = L⁻¹ (lower), V*⁻¹ = Mᵀ M
-    const double m10 = -l10 * i00 * i11, m21 = -l21 * i11 * i22, m20 = -(l20 * i00 + l21 * m10) * i22;
+    const double m10 = -c.l10 * i00 * i11, m21 = -c.l21 * i11 * i22, m20 = -(c.l20 * i00 + c.l21 * m10) * i22;
     inv[0] = i00 * i00 + m10 * m10 + m20 * m20, inv[1] = m10 * i11 + m20 * m21, inv[2] = m20 * i22;
     inv[3] = i11 * i11 + m21 * m21, inv[4] = m21 * i22, inv[5] = i22 * i22;
     return ok;
@@ -127,42 +124,27 @@ LG_HD void bundle_w(const double jc[2][6], const double jx[2][3], const double i
     }
 }
 
-// acc += the observation's part of its view's sums: U's upper triangle row by row, g_c = J_cᵀ r, Σ Y g_x (gx: the
-// landmark's whole J_xᵀ r) and Σ r².
+// acc += the observation's part of its view's sums: its two residuals in turn (U, g_c = J_cᵀ r, Σ r²), then Σ Y g_x
+// (gx: the landmark's whole J_xᵀ r).
 LG_HD void bundle_view_add(double acc[kBaSums], const double res[2], const double jc[2][6], const double y[6][3], const double gx[3]) {
+    lm_accumulate<6>(acc, res[0], jc[0]);
+    lm_accumulate<6>(acc, res[1], jc[1]);
 #pragma unroll
-    for (int w = 0; w < 2; ++w) {
-        int e = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int c = a; c < 6; ++c) acc[e] = fma(jc[w][a], jc[w][c], acc[e]), ++e;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] = fma(jc[w][a], res[w], acc[21 + a]);
-        acc[33] = fma(res[w], res[w], acc[33]);
-    }
-#pragma unroll
-    for (int a = 0; a < 6; ++a) acc[27 + a] += y[a][0] * gx[0] + y[a][1] * gx[1] + y[a][2] * gx[2];
+    for (int a = 0; a < 6; ++a) acc[kBaYg + a] += y[a][0] * gx[0] + y[a][1] * gx[1] + y[a][2] * gx[2];
 }
 
 LG_HD int upper6(int a, int c) { return a * 6 - a * (a - 1) / 2 + (c - a); }  // (a <= c) in a 6 x 6 upper triangle by rows
 
-// The trial pose of view v >= 1 from its block d [6] of the step: view 1 by polish_update on (R, t / scale), its t then
-// at the entering length again; the others by absolute_update.
-LG_HD void bundle_update(const AbsPose& s, int v, double scale, const double d[6], AbsPose& out) {
-    PolishPose p, pn;
+// The trial pose of view v >= 1 from its block d [6] of the step: R by rodrigues_update; view 1's t by tangent_move on
+// t / scale, then at the entering length again; the others' t + δt.
+LG_HD void bundle_update(const Pose& s, int v, double scale, const double d[6], Pose& out) {
     const double inv = 1.0 / scale;
+    const double u[3] = {s.t[0] * inv, s.t[1] * inv, s.t[2] * inv};
+    double un[3];
+    rodrigues_update(s.r, d, out.r);
+    tangent_move(u, d[3], d[4], un);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) p.r[k] = s.r[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p.t[k] = s.t[k] * inv;
-    polish_update(p, d, pn);
-    AbsPose an;
-    absolute_update(s, d, an);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) out.r[k] = an.r[k];  // (the same Rodrigues statements in both)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out.t[k] = v == 1 ? pn.t[k] * scale : an.t[k];
+    for (int k = 0; k < 3; ++k) out.t[k] = v == 1 ? un[k] * scale : s.t[k] + d[3 + k];
 }
 
 // The solve of the reduced camera system S δ = rhs for the n <= kBaParams leading rows, serially (the host's route; the

@@ -106,16 +106,35 @@ __device__ __forceinline__ void hartley(const float4* pts, const uint8_t* use, i
     for (int i = 0; i < 2; ++i) s[i] = 1.4142135623730951 / (block_sum<NT>(dist[i], buf, tid) / n);
 }
 
-// The 45 sums of a thread's inliers (the upper triangle of the normal matrix) added over each wave's lanes in a tree;
-// lane 0 of wave w leaves them in part[w].
-__device__ __forceinline__ void wave_sums(const double acc[45], double (*part)[45], int tid) {
+// N sums a thread (the 45 of the normal matrix's upper triangle; a refit's packed sums) added over each wave's lanes in a
+// tree; lane 0 of wave w leaves them in part[w].
+template <int N>
+__device__ __forceinline__ void wave_sums(const double acc[N], double (*part)[N], int tid) {
 #pragma unroll
-    for (int e = 0; e < 45; ++e) {
+    for (int e = 0; e < N; ++e) {
         double v = acc[e];
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
         if (tid % 64 == 0) part[tid / 64][e] = v;
     }
+}
+
+// wave_sums' parts of the four waves of kFinThreads added in index order, after a barrier: every thread reads the same
+// bits.
+template <int N>
+__device__ __forceinline__ void waves_total(const double (*part)[N], double sums[N]) {
+    static_assert(kFinThreads == 4 * 64, "four waves a workgroup");
+#pragma unroll
+    for (int e = 0; e < N; ++e) sums[e] = ((part[0][e] + part[1][e]) + part[2][e]) + part[3][e];
+}
+
+// The sum over the LANES adjacent lanes of a group (the 8 views of a landmark or of a track) by an xor butterfly, the
+// same bits in each (an addition is commutative, so both lanes of a pair compute the same sum at every level).
+template <int LANES, class T>
+__device__ __forceinline__ T lanes_sum(T v) {
+#pragma unroll
+    for (int d = 1; d < LANES; d <<= 1) v += __shfl_xor(v, d);
+    return v;
 }
 
 // Jacobi on the symmetric 9 x 9 am with the eigenvectors accumulated in vm (both row-major in LDS, vm the identity
@@ -159,7 +178,7 @@ __device__ __forceinline__ void jacobi9(double* am, double* vm, double (*rot)[2]
 // smallest eigenvalue is then the column of vm at am's smallest diagonal entry. part, am, vm, rot: in LDS.
 __device__ __forceinline__ void normal_eigenvector(const double acc[45], double (*part)[45], double* am, double* vm,
                                                    double (*rot)[2], int tid) {
-    wave_sums(acc, part, tid);
+    wave_sums<45>(acc, part, tid);
     __syncthreads();
     if (tid < 45) {
         int i, j;

@@ -12,7 +12,8 @@
 // index order from LDS, so every thread reads the same bits. Every thread then solves the 5 x 5 system alike (no
 // barrier, no broadcast; the solve's registers are dead before the next pass, whose row loop is what fills the register
 // file), builds the same trial pose, and the pass at the trial pose gives both the trial's cost and, where it is
-// accepted, the next round's sums: one pass a round. triangulate_kernel: a flat grid over (rows, pairs), a thread a correspondence.
+// accepted, the next round's sums: one pass a round (lm_rounds' rounds, written out here: through lm_rounds the kernel measured
+// 0.2 to 0.9 µs a call slower). triangulate_kernel: a flat grid over (rows, pairs), a thread a correspondence.
 // No atomics, no workspace, no host synchronisation.
 #include "lightglue_essential_device.h"
 #include "lightglue_polish_math.h"
@@ -23,7 +24,7 @@ namespace {
 // residual, which also defines fixed[k] : fixed[k]), the same bits in every thread. A thread reads only the fixed[]
 // entries it wrote. part: [kFinThreads / 64][kPolishSums] in LDS.
 template <bool FIRST>
-__device__ __forceinline__ void polish_pass(const PolishPose& q, const PolishWeights& pw, const Intrinsics& kk, const float4* pts,
+__device__ __forceinline__ void polish_pass(const Pose& q, const PolishWeights& pw, const Intrinsics& kk, const float4* pts,
                                             const uint8_t* mask, uint8_t* fixed, int count, double (*part)[kPolishSums], int tid,
                                             double sums[kPolishSums]) {
     double acc[kPolishSums];
@@ -44,16 +45,9 @@ __device__ __forceinline__ void polish_pass(const PolishPose& q, const PolishWei
         polish_accumulate(acc, s, j);
     }
     __syncthreads();  // (the last pass's readers of part are done)
-#pragma unroll
-    for (int e = 0; e < kPolishSums; ++e) {
-        double v = acc[e];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-        if (tid % 64 == 0) part[tid / 64][e] = v;
-    }
+    wave_sums<kPolishSums>(acc, part, tid);
     __syncthreads();
-#pragma unroll
-    for (int e = 0; e < kPolishSums; ++e) sums[e] = ((part[0][e] + part[1][e]) + part[2][e]) + part[3][e];
+    waves_total<kPolishSums>(part, sums);
 }
 
 // The inliers of `mask` that triangulate in front of both cameras under (r, t) (every thread).
@@ -92,7 +86,7 @@ __global__ __launch_bounds__(kFinThreads) void pose_polish_kernel(PairArgs a, co
     for (int k = 0; k < 9; ++k) rg[k] = r_in[(size_t)p * 9 + k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) tg[k] = t_in[(size_t)p * 3 + k];
-    PolishPose st;
+    Pose st;
     const bool pose_ok = polish_enter(rg, tg, st);
     const PolishWeights pw = polish_weights(kk);
 
@@ -116,28 +110,28 @@ __global__ __launch_bounds__(kFinThreads) void pose_polish_kernel(PairArgs a, co
         if (pose_ok) {
             double sums[kPolishSums];
             polish_pass<true>(st, pw, kk, pts, mask, fixed, count, part, tid, sums);
-            cost0 = cost1 = sums[20];
-            if ((int)sums[21] >= kMinPolishRows && finite64(cost0)) {
+            cost0 = cost1 = sums[PolishLm::kCost];
+            if ((int)sums[PolishLm::kRows] >= kMinPolishRows && finite64(cost0)) {
                 double lambda = kLambdaStart;
 #pragma unroll 1
                 for (int round = 0; round < iterations; ++round) {
                     double delta[5];
-                    bool take = polish_step(sums, lambda, delta);
+                    bool take = lm_step<5>(sums, lambda, delta);
                     if (take) {  // (a rejected solve spares the pass)
-                        PolishPose next;
+                        Pose next;
                         double again[kPolishSums];
                         polish_update(st, delta, next);
                         polish_pass<false>(next, pw, kk, pts, mask, fixed, count, part, tid, again);
-                        take = finite64(again[20]) && again[20] < sums[20];
+                        take = lm_accept(again[PolishLm::kCost], sums[PolishLm::kCost]);
                         if (take) {
                             st = next;
 #pragma unroll
                             for (int e = 0; e < kPolishSums; ++e) sums[e] = again[e];
                         }
                     }
-                    lambda = take ? fmax(lambda * 0.1, kLambdaMin) : fmin(lambda * 10.0, kLambdaMax);
+                    lambda = lm_lambda(lambda, take);
                 }
-                cost1 = sums[20];
+                cost1 = sums[PolishLm::kCost];
                 // the mask of the polished pose over all the pair's correspondences, and the keep rule
                 double e[9];
                 float f[9];

@@ -1,37 +1,22 @@
 // lightglue_polish_math.h — the arithmetic of the pose polish and of the triangulation (csrc/lightglue_polish.hip;
 // include/lightglue_glue.h, "the pose polish"): the signed Sampson residual of a correspondence in pixels with its
 // analytic Jacobian row over the 5 parameters (ω, τ), the state (R, t) with the derivative matrices of E = [t]x R, the
-// Levenberg-Marquardt step by a 5 x 5 Cholesky, the update by the exact Rodrigues formula, and the midpoint
-// triangulation. All fp64. The style is lightglue_essential_math.h's: plain __host__ __device__ functions on values
-// and small fixed-size arrays, every index a compile-time constant after unrolling, selection by selects, every loop
-// with a compile-time bound.
+// entering and the trial pose, and the midpoint triangulation. All fp64. The style is lightglue_essential_math.h's:
+// plain __host__ __device__ functions on values and small fixed-size arrays, every index a compile-time constant after
+// unrolling, selection by selects, every loop with a compile-time bound. From lightglue_lm_math.h: Pose, polar_step,
+// rodrigues_update, the sums' layout LmSums<5> with lm_accumulate (the step and the rounds are lm_step<5> and
+// lm_rounds<5> there), finite64, cross_mul.
 #pragma once
 
 #include "lightglue_essential_math.h"
+#include "lightglue_lm_math.h"
 
 namespace lg_geom {
 
 constexpr int kMaxPolish = 16;         // rounds at most
 constexpr int kMinPolishRows = 5;      // the fixed set needs as many rows as there are parameters
-constexpr int kPolishSums = 22;        // JᵀJ's upper triangle (15), Jᵀs (5), Σ s² and the number of rows
-constexpr double kLambdaStart = 1e-3, kLambdaMin = 1e-12, kLambdaMax = 1e12;
-
-LG_HD bool finite64(double v) { return fabs(v) < INFINITY; }  // (NaN: false)
-
-// out = [v]x m (row-major 3 x 3): column c of out is v x (column c of m).
-LG_HD void cross_mul(const double v[3], const double m[9], double out[9]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        out[c] = v[1] * m[6 + c] - v[2] * m[3 + c];
-        out[3 + c] = v[2] * m[c] - v[0] * m[6 + c];
-        out[6 + c] = v[0] * m[3 + c] - v[1] * m[c];
-    }
-}
-
-// The pose being polished: R, t at unit length.
-struct PolishPose {
-    double r[9], t[3];
-};
+using PolishLm = LmSums<5>;            // JᵀJ's upper triangle (15), Jᵀs (5), Σ s² and the number of rows
+constexpr int kPolishSums = PolishLm::kCount;
 
 // What a pass over the rows derives from the pose once: E = [t]x R and the five derivative matrices
 // ∂E/∂ω_i = [t]x [e_i]x R, ∂E/∂τ_j = [b_j]x R for the tangent basis (b1, b2) of t. (Not kept between the passes: the
@@ -53,7 +38,7 @@ LG_HD void tangent_basis(const double t[3], double b[2][3]) {
 }
 
 // E and the derivative matrices of the pose.
-LG_HD void polish_derive(const PolishPose& q, PolishState& s) {
+LG_HD void polish_derive(const Pose& q, PolishState& s) {
     double b[2][3];
     cross_mul(q.t, q.r, s.e);
     tangent_basis(q.t, b);
@@ -68,10 +53,20 @@ LG_HD void polish_derive(const PolishPose& q, PolishState& s) {
     for (int j = 0; j < 2; ++j) cross_mul(b[j], q.r, s.de[3 + j]);
 }
 
-// The entering pose from one given in fp32: t at unit length, R one Newton step of the polar iteration nearer the
-// rotations (R (3 I - Rᵀ R) / 2: the defect of a rotation rounded to fp32 falls from 1e-7 to 1e-14). False where R or
+// t moved in its tangent plane and back to unit length: normalise(t + τ1 b1 + τ2 b2).
+LG_HD void tangent_move(const double t[3], double tau1, double tau2, double out[3]) {
+    double b[2][3], m[3];
+    tangent_basis(t, b);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m[k] = t[k] + tau1 * b[0][k] + tau2 * b[1][k];
+    const double inv = 1.0 / sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = m[k] * inv;
+}
+
+// The entering pose from one given in fp32: t at unit length, R one polar_step nearer the rotations. False where R or
 // t is not finite or t has zero length (the pose is then not to be used).
-LG_HD bool polish_enter(const float r[9], const float t[3], PolishPose& s) {
+LG_HD bool polish_enter(const float r[9], const float t[3], Pose& s) {
     bool ok = true;
     double m[9];
 #pragma unroll
@@ -81,18 +76,7 @@ LG_HD bool polish_enter(const float r[9], const float t[3], PolishPose& s) {
     ok = ok && finite64(len) && len > 0.0;
     const double inv = 1.0 / len;
     s.t[0] = tx * inv, s.t[1] = ty * inv, s.t[2] = tz * inv;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double v = 0.0;  // (R (3 I - Rᵀ R))[i][j]
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double g = m[k] * m[j] + m[3 + k] * m[3 + j] + m[6 + k] * m[6 + j];  // (Rᵀ R)[k][j]
-                v += m[3 * i + k] * ((k == j ? 3.0 : 0.0) - g);
-            }
-            s.r[3 * i + j] = 0.5 * v;
-        }
+    polar_step(m, s.r);
     return ok;
 }
 
@@ -127,84 +111,16 @@ LG_HD double sampson_row(const PolishState& st, const PolishWeights& pw, double 
     return s;
 }
 
-// acc += the row's part of the kPolishSums sums: JᵀJ's upper triangle row by row, Jᵀs, s² and 1.
+// acc += the row's part of the kPolishSums sums.
 LG_HD void polish_accumulate(double acc[kPolishSums], double s, const double j[5]) {
-    int e = 0;
-#pragma unroll
-    for (int a = 0; a < 5; ++a)
-#pragma unroll
-        for (int b = a; b < 5; ++b) acc[e] = fma(j[a], j[b], acc[e]), ++e;
-#pragma unroll
-    for (int a = 0; a < 5; ++a) acc[15 + a] = fma(j[a], s, acc[15 + a]);
-    acc[20] = fma(s, s, acc[20]);
-    acc[21] += 1.0;
+    lm_accumulate<5>(acc, s, j);
+    acc[PolishLm::kRows] += 1.0;
 }
 
-// The Levenberg-Marquardt step of the sums: (JᵀJ + λ diag(JᵀJ)) δ = -Jᵀs by a Cholesky factorisation. False where
-// a pivot is not positive or not finite (δ is then not to be used).
-LG_HD bool polish_step(const double sums[kPolishSums], double lambda, double delta[5]) {
-    double l[5][5];
-    int e = 0;
-#pragma unroll
-    for (int a = 0; a < 5; ++a)
-#pragma unroll
-        for (int b = a; b < 5; ++b) l[b][a] = sums[e] * (a == b ? 1.0 + lambda : 1.0), ++e;
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        double piv = l[c][c];
-#pragma unroll
-        for (int k = 0; k < c; ++k) piv = fma(-l[c][k], l[c][k], piv);
-        ok = ok && piv > 0.0 && finite64(piv);  // (NaN: false)
-        const double root = sqrt(piv), inv = 1.0 / root;
-        l[c][c] = root;
-#pragma unroll
-        for (int r = c + 1; r < 5; ++r) {
-            double v = l[r][c];
-#pragma unroll
-            for (int k = 0; k < c; ++k) v = fma(-l[r][k], l[c][k], v);
-            l[r][c] = v * inv;
-        }
-    }
-    double y[5];
-#pragma unroll
-    for (int r = 0; r < 5; ++r) {
-        double v = -sums[15 + r];
-#pragma unroll
-        for (int k = 0; k < r; ++k) v = fma(-l[r][k], y[k], v);
-        y[r] = v / l[r][r];
-    }
-#pragma unroll
-    for (int r = 4; r >= 0; --r) {
-        double v = y[r];
-#pragma unroll
-        for (int k = r + 1; k < 5; ++k) v = fma(-l[k][r], delta[k], v);
-        delta[r] = v / l[r][r];
-        ok = ok && finite64(delta[r]);
-    }
-    return ok;
-}
-
-LG_HD double sinc64(double x) { return x == 0.0 ? 1.0 : sin(x) / x; }
-
-// The trial pose: R <- exp([ω]x) R by the Rodrigues formula, exp = I + (sin θ / θ) [ω]x + ((1 - cos θ) / θ²) [ω]x²
-// with (1 - cos θ) / θ² = (sin(θ / 2) / (θ / 2))² / 2 (no cancellation at small θ), and t <- normalise(t + τ1 b1 + τ2 b2).
-LG_HD void polish_update(const PolishPose& s, const double delta[5], PolishPose& out) {
-    const double w[3] = {delta[0], delta[1], delta[2]};
-    const double theta = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    const double ka = sinc64(theta), kh = sinc64(0.5 * theta), kb = 0.5 * kh * kh;
-    double g[9], h[9], b[2][3];
-    tangent_basis(s.t, b);
-    cross_mul(w, s.r, g);
-    cross_mul(w, g, h);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) out.r[k] = s.r[k] + ka * g[k] + kb * h[k];
-    double t[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = s.t[k] + delta[3] * b[0][k] + delta[4] * b[1][k];
-    const double inv = 1.0 / sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out.t[k] = t[k] * inv;
+// The trial pose: R <- exp([ω]x) R (rodrigues_update) and t <- tangent_move(t, τ1, τ2).
+LG_HD void polish_update(const Pose& s, const double delta[5], Pose& out) {
+    rodrigues_update(s.r, delta, out.r);
+    tangent_move(s.t, delta[3], delta[4], out.t);
 }
 
 // The midpoint triangulation of a correspondence (camera coordinates) under X1 = R X0 + t: in_front's depths

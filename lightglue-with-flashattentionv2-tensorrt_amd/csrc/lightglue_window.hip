@@ -131,19 +131,6 @@ struct PointArgs {
     int views, lmax, kp;
 };
 
-// The sum over the 8 lanes of a track, the same bits in each (lightglue_bundle.hip's group_sum).
-__device__ __forceinline__ double lanes_sum(double v) {
-#pragma unroll
-    for (int d = 1; d < kMaxViews; d <<= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ int lanes_count(bool x) {
-    int v = x ? 1 : 0;
-#pragma unroll
-    for (int d = 1; d < kMaxViews; d <<= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 __global__ __launch_bounds__(kWinThreads) void window_points_kernel(PointArgs a, double thr2, float* __restrict__ obs,
                                                                      uint8_t* __restrict__ seen, int32_t* __restrict__ counts,
                                                                      float* __restrict__ points, uint8_t* __restrict__ ok_out,
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(kWinThreads) void window_points_kernel(PointArgs a,
                 for (int k = 0; k < 3; ++k) p[9 + k] = a.t[at * 3 + k];
             }
         }
-        AbsPose q;
+        Pose q;
         ok = absolute_enter(p, q) && ok;
 #pragma unroll
         for (int k = 0; k < 9; ++k) pose[tid][k] = q.r[k];
@@ -188,7 +175,7 @@ __global__ __launch_bounds__(kWinThreads) void window_points_kernel(PointArgs a,
     const bool has = kp >= 0 && kp < a.kp;
     float2 px = make_float2(0.f, 0.f);
     if (has) px = *reinterpret_cast<const float2*>(a.kpts + (((size_t)b * a.views + v) * a.kp + kp) * 2);
-    AbsPose q;
+    Pose q;
 #pragma unroll
     for (int k = 0; k < 9; ++k) q.r[k] = pose[v][k];
 #pragma unroll
@@ -203,20 +190,20 @@ __global__ __launch_bounds__(kWinThreads) void window_points_kernel(PointArgs a,
         double s[kWindowSums], res[2], jx[2][3];
         window_ray(q, cam, (double)px.x, (double)px.y, s);
 #pragma unroll
-        for (int e = 0; e < kWindowSums; ++e) s[e] = lanes_sum(set ? s[e] : 0.0);
-        nset = lanes_count(set);
+        for (int e = 0; e < kWindowSums; ++e) s[e] = lanes_sum<kMaxViews>(set ? s[e] : 0.0);
+        nset = lanes_sum<kMaxViews>(set ? 1 : 0);
         solved = window_start(s, x, piv);
 #pragma unroll 1
         for (int round = 0; round < kWindowGnRounds; ++round) {
             const bool row_ok = window_row(q, cam, x, (double)px.x, (double)px.y, res, jx);
             window_row_sums(set && row_ok, res, jx, s);
 #pragma unroll
-            for (int e = 0; e < kWindowSums; ++e) s[e] = lanes_sum(s[e]);
+            for (int e = 0; e < kWindowSums; ++e) s[e] = lanes_sum<kMaxViews>(s[e]);
             window_step(s, x);
         }
         const bool row_ok = window_row(q, cam, x, (double)px.x, (double)px.y, res, jx);
         const bool pass_v = window_pass(set, row_ok, res, thr2);
-        all_pass = lanes_count(set && !pass_v) == 0;
+        all_pass = lanes_sum<kMaxViews>(set && !pass_v ? 1 : 0) == 0;
         if (pass == 0) set = pass_v;
     }
     const bool ok = window_ok(solved, nset, all_pass, x, piv);

@@ -1,10 +1,11 @@
 // lightglue_window_math.h — the arithmetic of the sequence window (csrc/lightglue_window.hip;
 // include/lightglue_glue.h, "the sequence window"): a posed view's ray through an observation and its part of the
 // normal equations of the point closest to the rays, the 3 x 3 Cholesky solve with its smallest pivot, an observation's
-// reprojection residual with its Jacobian over the point, the Gauss-Newton step and the rule for a track that is ok. All fp64. The style is lightglue_bundle_math.h's: plain __host__ __device__ functions on values and
-// small fixed-size arrays, selection by selects, every loop with a compile-time bound. From lightglue_bundle_math.h:
-// bundle_point_add, bundle_point_inverse, sym3_mul, kMaxViews; from lightglue_absolute_math.h: absolute_row, AbsPose,
-// Camera.
+// reprojection residual with its Jacobian over the point, the Gauss-Newton step and the rule for a track that is ok.
+// All fp64. The style is lightglue_bundle_math.h's: plain __host__ __device__ functions on values and small fixed-size
+// arrays, selection by selects, every loop with a compile-time bound. From lightglue_lm_math.h: Pose, Camera, chol3,
+// finite64; from lightglue_bundle_math.h: bundle_point_add, bundle_point_inverse, sym3_mul, kMaxViews; from
+// lightglue_absolute_math.h: absolute_row, absolute_enter, camera_ok.
 #pragma once
 
 #include "lightglue_bundle_math.h"
@@ -19,7 +20,7 @@ constexpr int kNoLink = 0xffff;         // a 16-bit next / prev entry without a 
 // A posed view's part of Σ (I - d dᵀ) X = Σ (I - d dᵀ) c: d the unit ray of the pixel in the frame's coordinates,
 // Rᵀ ((px - cx) / fx, (py - cy) / fy, 1) normalised, c = -Rᵀ t the camera's centre. a[0..5]: the upper triangle
 // (00 01 02 11 12 22), a[6..8]: the right side.
-LG_HD void window_ray(const AbsPose& q, const Camera& k, double px, double py, double a[kWindowSums]) {
+LG_HD void window_ray(const Pose& q, const Camera& k, double px, double py, double a[kWindowSums]) {
     const double n0 = (px - (double)k.cx) / (double)k.fx, n1 = (py - (double)k.cy) / (double)k.fy;
     const double inv = 1.0 / sqrt(n0 * n0 + n1 * n1 + 1.0);
     double d[3], c[3];
@@ -35,33 +36,24 @@ LG_HD void window_ray(const AbsPose& q, const Camera& k, double px, double py, d
     for (int i = 0; i < 3; ++i) a[6 + i] = c[i] - d[i] * dc;
 }
 
-// The solve of the summed system by a 3 x 3 Cholesky factorisation: x, and piv the smallest pivot. False where a pivot
-// is not positive or not finite; x is then zeros.
+// The solve of the summed system by chol3: x, and piv the smallest pivot. False where a pivot is not positive or not
+// finite; x is then zeros.
 LG_HD bool window_start(const double a[kWindowSums], double x[3], double& piv) {
-    const double p0 = a[0];
-    bool ok = p0 > 0.0 && finite64(p0);
-    const double l00 = sqrt(p0), i00 = 1.0 / l00;
-    const double l10 = a[1] * i00, l20 = a[2] * i00;
-    const double p1 = fma(-l10, l10, a[3]);
-    ok = ok && p1 > 0.0 && finite64(p1);
-    const double l11 = sqrt(p1), i11 = 1.0 / l11;
-    const double l21 = fma(-l20, l10, a[4]) * i11;
-    const double p2 = fma(-l21, l21, fma(-l20, l20, a[5]));
-    ok = ok && p2 > 0.0 && finite64(p2);
-    const double i22 = 1.0 / sqrt(p2);
-    const double y0 = a[6] * i00, y1 = fma(-l10, y0, a[7]) * i11, y2 = fma(-l21, y1, fma(-l20, y0, a[8])) * i22;
-    x[2] = y2 * i22;
-    x[1] = fma(-l21, x[2], y1) * i11;
-    x[0] = fma(-l20, x[2], fma(-l10, x[1], y0)) * i00;
+    Chol3 c;
+    const bool ok = chol3(a, c);
+    const double y0 = a[6] * c.i00, y1 = fma(-c.l10, y0, a[7]) * c.i11, y2 = fma(-c.l21, y1, fma(-c.l20, y0, a[8])) * c.i22;
+    x[2] = y2 * c.i22;
+    x[1] = fma(-c.l21, x[2], y1) * c.i11;
+    x[0] = fma(-c.l20, x[2], fma(-c.l10, x[1], y0)) * c.i00;
 #pragma unroll
     for (int i = 0; i < 3; ++i) x[i] = ok ? x[i] : 0.0;  // (the rounds then start from the frame's origin, as the contract's)
-    piv = fmin(p0, fmin(p1, p2));
+    piv = fmin(c.p0, fmin(c.p1, c.p2));
     return ok;
 }
 
 // An observation's residual (px) at the point x and its Jacobian over x. False where the depth is not positive or the
 // residual not finite.
-LG_HD bool window_row(const AbsPose& q, const Camera& k, const double x[3], double px, double py, double res[2], double jx[2][3]) {
+LG_HD bool window_row(const Pose& q, const Camera& k, const double x[3], double px, double py, double res[2], double jx[2][3]) {
     double j[2][6];
     const bool ok = absolute_row(q, k, x[0], x[1], x[2], px, py, res, j);
 #pragma unroll

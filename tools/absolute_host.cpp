@@ -30,7 +30,7 @@ int solve_one(const float* pts, const Camera& cam, const int32_t* idx, int count
     for (int sub = 0; sub < 4; ++sub) {
         double u;
         const bool has = p3p_root(s, sub, u);
-        AbsPose q;
+        Pose q;
         ok[sub] = p3p_pose(s, x, u, q.r, q.t, key[sub]) && has;
         ok[sub] = absolute_round(q, pose[sub]) && ok[sub];
     }
@@ -58,7 +58,7 @@ int count_mask(const float pose[12], const Camera& cam, const float* pts, int co
 
 // One pass over the rows, serially: the sums at the pose q over the rows with (first ? mask and a usable residual, which
 // defines fixed : fixed).
-void pass(const AbsPose& q, const Camera& cam, const float* pts, const uint8_t* mask, uint8_t* fixed, int count, bool first,
+void pass(const Pose& q, const Camera& cam, const float* pts, const uint8_t* mask, uint8_t* fixed, int count, bool first,
           double sums[kAbsSums]) {
     for (int e = 0; e < kAbsSums; ++e) sums[e] = 0.0;
     for (int k = 0; k < count; ++k) {
@@ -79,30 +79,16 @@ void pass(const AbsPose& q, const Camera& cam, const float* pts, const uint8_t* 
 // Levenberg-Marquardt -> the pose rounded to fp32. False where there is no refit. cost: the entering and the final.
 bool refit(const float pose[12], const Camera& cam, const float* pts, const uint8_t* mask, uint8_t* fixed, int count, int rounds,
            float out[12], double cost[2]) {
-    AbsPose st;
+    Pose st;
     if (!absolute_enter(pose, st)) return false;
     double sums[kAbsSums];
     pass(st, cam, pts, mask, fixed, count, true, sums);
-    cost[0] = cost[1] = sums[27];
-    if (!((int)sums[28] >= kMinAbsRows && finite64(sums[27]))) return false;
-    double lambda = kLambdaStart;
-    for (int it = 0; it < rounds; ++it) {
-        double delta[6];
-        bool take = absolute_step(sums, lambda, delta);
-        if (take) {
-            AbsPose next;
-            double again[kAbsSums];
-            absolute_update(st, delta, next);
-            pass(next, cam, pts, mask, fixed, count, false, again);
-            take = finite64(again[27]) && again[27] < sums[27];
-            if (take) {
-                st = next;
-                for (int e = 0; e < kAbsSums; ++e) sums[e] = again[e];
-            }
-        }
-        lambda = take ? fmax(lambda * 0.1, kLambdaMin) : fmin(lambda * 10.0, kLambdaMax);
-    }
-    cost[1] = sums[27];
+    cost[0] = cost[1] = sums[AbsLm::kCost];
+    if (!((int)sums[AbsLm::kRows] >= kMinAbsRows && finite64(sums[AbsLm::kCost]))) return false;
+    lm_rounds<6>(
+        st, sums, rounds, [&](const Pose& q, double* again) { pass(q, cam, pts, mask, fixed, count, false, again); },
+        [](const Pose& q, const double* delta, Pose& next) { absolute_update(q, delta, next); });
+    cost[1] = sums[AbsLm::kCost];
     return absolute_round(st, out);
 }
 

@@ -30,7 +30,7 @@ struct Block {
     bool in[kMaxViews], live, inverted;
 };
 
-void block_at(Window& w, const AbsPose* q, const double* x, int l, double lambda, bool first, Block& k) {
+void block_at(Window& w, const Pose* q, const double* x, int l, double lambda, bool first, Block& k) {
     int bits = first ? 0 : w.fset[l];
     for (int v = 0; v < w.views; ++v) {
         double sb[2][3];
@@ -77,7 +77,7 @@ void host_bundle(const float* obs, const uint8_t* seen, int count, const float* 
         }
     for (int e = 0; e < 3 * lmax; ++e) points_out[e] = points[e];
     cost[0] = cost[1] = 0.0, out[0] = out[1] = 0;
-    AbsPose cur[kMaxViews], next[kMaxViews];
+    Pose cur[kMaxViews], next[kMaxViews];
     bool staged = true;
     for (int v = 0; v < views; ++v) {
         float p[12];
@@ -116,7 +116,7 @@ void host_bundle(const float* obs, const uint8_t* seen, int count, const float* 
                 double ww[6][3], yy[6][3];
                 bundle_w(k.jc[v], k.jx[v], k.inv, ww, yy);
                 bundle_view_add(sums[v], k.res[v], k.jc[v], yy, k.gx);
-                sums[v][34] += 1.0;
+                sums[v][kBaObs] += 1.0;
                 for (int a = 0; a < bundle_width(v); ++a)
                     for (int c = 0; c < 3; ++c) wl[bundle_row0(v) + a][c] = ww[a][c], yl[bundle_row0(v) + a][c] = yy[a][c];
             }
@@ -127,8 +127,8 @@ void host_bundle(const float* obs, const uint8_t* seen, int count, const float* 
         if (round == 0) {
             bool enough = true;
             for (int v = 0; v < views; ++v) {
-                now += sums[v][33], out[0] += (int)sums[v][34];
-                enough = enough && (v < 1 || (int)sums[v][34] >= kMinViewObs);
+                now += sums[v][BaLm::kCost], out[0] += (int)sums[v][kBaObs];
+                enough = enough && (v < 1 || (int)sums[v][kBaObs] >= kMinViewObs);
             }
             cost[0] = cost[1] = now;
             if (!(enough && finite64(now))) return;
@@ -139,7 +139,7 @@ void host_bundle(const float* obs, const uint8_t* seen, int count, const float* 
                     const double u = sums[v][upper6(a < c ? a : c, a < c ? c : a)];
                     s[bundle_row0(v) + a][bundle_row0(v) + c] += a == c ? u * (1.0 + lambda) : u;
                 }
-                rhs[bundle_row0(v) + a] = -(sums[v][21 + a] - sums[v][27 + a]);
+                rhs[bundle_row0(v) + a] = -(sums[v][BaLm::kGrad + a] - sums[v][kBaYg + a]);
             }
         bool take = bad == 0;
         if (take) take = bundle_solve(s, rhs, n, delta);
@@ -170,14 +170,14 @@ void host_bundle(const float* obs, const uint8_t* seen, int count, const float* 
                     again += res[0] * res[0] + res[1] * res[1];
                 }
             }
-            take = finite64(again) && again < now;
+            take = lm_accept(again, now);
             if (take) {
                 now = again, kept = true;
                 for (int v = 1; v < views; ++v) cur[v] = next[v];
                 pts.swap(trial);
             }
         }
-        lambda = take ? fmax(lambda * 0.1, kLambdaMin) : fmin(lambda * 10.0, kLambdaMax);
+        lambda = lm_lambda(lambda, take);
     }
     for (int v = 1; v < views && kept; ++v) {
         float p[12];

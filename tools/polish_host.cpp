@@ -20,7 +20,7 @@ void camera(const float* q, const Intrinsics& k, double c[4]) {
 }
 
 // polish_pass: first also defines fixed[].
-void pass(const PolishPose& q, const PolishWeights& pw, const Intrinsics& kk, const float* pts, const uint8_t* mask, uint8_t* fixed,
+void pass(const Pose& q, const PolishWeights& pw, const Intrinsics& kk, const float* pts, const uint8_t* mask, uint8_t* fixed,
           int count, bool first, double sums[kPolishSums]) {
     PolishState st;
     polish_derive(q, st);
@@ -62,7 +62,7 @@ void host_polish(const float* pts, int count, const float* intrinsics, const flo
     const Intrinsics kk = intrinsics_of(intrinsics);
     const float thr2 = threshold * threshold;
     const bool valid = valid_in != 0, staged = valid && intrinsics_ok(kk);
-    PolishPose st;
+    Pose st;
     const bool pose_ok = polish_enter(r, t, st);
     const PolishWeights pw = polish_weights(kk);
     uint8_t* mask = new uint8_t[3 * (count + 1)];
@@ -81,29 +81,17 @@ void host_polish(const float* pts, int count, const float* intrinsics, const flo
         if (pose_ok) {
             double sums[kPolishSums];
             pass(st, pw, kk, pts, mask, fixed, count, true, sums);
-            cost0 = cost1 = sums[20];
-            if ((int)sums[21] >= kMinPolishRows && finite64(cost0)) {
-                double lambda = kLambdaStart;
-                for (int round = 0; round < iterations; ++round) {
-                    double delta[5];
-                    bool take = polish_step(sums, lambda, delta);
-                    if (take) {
-                        PolishPose next;
-                        double again[kPolishSums];
-                        polish_update(st, delta, next);
-                        pass(next, pw, kk, pts, mask, fixed, count, false, again);
-                        take = finite64(again[20]) && again[20] < sums[20];
-                        if (take) {
-                            st = next;
-                            for (int e = 0; e < kPolishSums; ++e) sums[e] = again[e];
-                            double ss = 0.0;
-                            for (int e = 0; e < 5; ++e) ss += delta[e] * delta[e];
-                            steps[round] = sqrt(ss);
-                        }
-                    }
-                    lambda = take ? fmax(lambda * 0.1, kLambdaMin) : fmin(lambda * 10.0, kLambdaMax);
-                }
-                cost1 = sums[20];
+            cost0 = cost1 = sums[PolishLm::kCost];
+            if ((int)sums[PolishLm::kRows] >= kMinPolishRows && finite64(cost0)) {
+                lm_rounds<5>(
+                    st, sums, iterations, [&](const Pose& q, double* again) { pass(q, pw, kk, pts, mask, fixed, count, false, again); },
+                    [](const Pose& q, const double* delta, Pose& next) { polish_update(q, delta, next); },
+                    [&](int round, const double* delta) {
+                        double ss = 0.0;
+                        for (int e = 0; e < 5; ++e) ss += delta[e] * delta[e];
+                        steps[round] = sqrt(ss);
+                    });
+                cost1 = sums[PolishLm::kCost];
                 double e[9];
                 float f[9];
                 cross_mul(st.t, st.r, e);

@@ -30,7 +30,7 @@ void lanes_sums(const double lane[kMaxViews][kWindowSums], double s[kWindowSums]
 extern "C" void host_window_points(const int32_t* track_kp, int32_t kept_in, const float* kpts, const float* intr, const float* r,
                                    const float* t, const uint8_t* posed, int32_t views, int32_t lmax, int32_t kp, float threshold,
                                    float* obs, uint8_t* seen, float* points, uint8_t* ok_out, uint8_t* seen_all) {
-    AbsPose pose[kMaxViews];
+    Pose pose[kMaxViews];
     Camera cam[kMaxViews];
     bool usable[kMaxViews];
     for (int v = 0; v < kMaxViews; ++v) {
