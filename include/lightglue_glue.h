@@ -265,6 +265,32 @@ int32_t lg_assign_nll(const void* v, int64_t pair_stride, int32_t ld, int32_t zc
                       const int32_t* m_len, const int32_t* n_len, const int32_t* gt0, const int32_t* gt1, float* loss,
                       float* dv, void* workspace, hipStream_t stream);
 
+/* ---- the FFN block's backward (csrc/lightglue_ffn_backward.hip) ----
+ * The gradients of lg_linear_cat_ffn's out = x + fp16(W2 GELU(LN(fp16(W1 c + b1))) + b2), c = [x | merge_heads(ctx0,
+ * ctx1)], from its inputs and dy = dL/dout; the forward saves nothing, a and the statistics are recomputed. New symbols
+ * only: LG_GLUE_ABI_VERSION stays 4. fp16 model only, heads == 4 (d = 256): x, dy, dx [m, 256] with m = pairs * (n0 + n1);
+ * ctx_i, dctx_i [pairs, 4, ni, 64] (dctx_i is the dO mha_hd64_backward reads); w1 [512, 512] the folded first weight,
+ * b1, gamma, beta [512], w2 [256, 512] as lg_linear_cat_ffn takes them. A loss scale is the caller's business.
+ *   a = fp16(c W1^T + b1); mu, rstd over a in fp32 (the variance from the squares about the mean);
+ *   n = (a - mu) rstd; u = n gamma + beta; g = fp16(GELU(u)); dg = dy W2; du = dg (Phi(u) + u phi(u)); dn = du gamma;
+ *   da = rstd (dn - mean(dn) - n mean(dn n)); dc = da W1
+ *   dx = fp16(dy + dc[:, :256]) (the residual included), dctx = fp16(dc[:, 256:]) split per image, head-major
+ *   dw2 = dy^T g, db2 = sum dy, dw1 = da^T c, db1 = sum da, dgamma = sum du n, dbeta = sum du (fp32, sums over rows)
+ * Rounding points: a and g to fp16 as the forward rounds them; da to fp16 where it becomes the operand of dc, dw1 and
+ * db1; du and du n to fp16 where they become the operands of dbeta's and dgamma's sums; dx one rounding of the fp32
+ * sum; fp32 accumulation and fp32 element-wise arithmetic otherwise, the erf lg_linear_cat_ffn uses.
+ * Every element of every output is written on every call (m == 0: zeros in the parameter gradients). The six
+ * parameter-gradient pointers are all given or all null (null: dx and dctx only, with the same bits). Pointers 16-B
+ * aligned (b1, gamma, beta 8-B); dx must not alias x or dy, nor dctx_i ctx_i (the weight gradients gather c again
+ * after dctx is written); m <= 2^20; workspace >= lg_ffn_backward_workspace(m) bytes.
+ * Arguments are checked before any device call. No float atomics, no host synchronisation, no allocation: capturable,
+ * bitwise reproducible. */
+size_t lg_ffn_backward_workspace(int32_t m_rows);
+int32_t lg_ffn_backward(const void* x, const void* ctx0, const void* ctx1, int32_t heads, int32_t n0, int32_t n1,
+                        int32_t pairs, const void* w1, const void* b1, const void* gamma, const void* beta, float eps,
+                        const void* w2, const void* dy, void* dx, void* dctx0, void* dctx1, float* dw1, float* db1,
+                        float* dgamma, float* dbeta, float* dw2, float* db2, void* workspace, hipStream_t stream);
+
 /* ---- adaptive depth and width (csrc/lightglue_adaptive.hip; fp16 rows of 256 channels) ----
  * The published LightGlue rules the reference ships the pieces of (TokenConfidence lightglue.py:54-66,
  * MatchAssignment.get_matchability :230-232) and never applies. New symbols only: LG_GLUE_ABI_VERSION

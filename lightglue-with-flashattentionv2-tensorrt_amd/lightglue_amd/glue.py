@@ -7,7 +7,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._host import DT, _workspace, call, stream_of
+from ._host import DT, PluginError, _workspace, call, stream_of
 from .matches import MatchResult
 
 
@@ -97,6 +97,32 @@ class _Hip:
              ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w2.data_ptr(), b2.data_ptr(), _ptr(packed),
              h.data_ptr(), out.data_ptr(), stream_of(x))
         return out
+
+    @staticmethod
+    def ffn_backward(x, c0, c1, w, b, ln: nn.LayerNorm, w2, dy, need_params=True, out=None):
+        """lg_ffn_backward: the gradients of ffn(x, c0, c1, w, b, ln, w2, b2) from dy = dL/dout [1, M, 256] ->
+        (dx, dc0, dc1, dw, db, dgamma, dbeta, dw2, db2): dx and the head-major dc fp16, the parameter gradients fp32
+        (None without need_params: the data-only call). out: tensors to write instead of new ones, in that order
+        (contiguous, of those shapes and dtypes)."""
+        pr, heads, n0, n1 = c0.shape[0], c0.shape[1], c0.shape[2], c1.shape[2]
+        m = pr * (n0 + n1)
+        want = ((x, (1, m, 256)), (dy, (1, m, 256)), (c0, (pr, 4, n0, 64)), (c1, (pr, 4, n1, 64)), (w, (512, 512)), (b, (512,)),
+                (ln.weight, (512,)), (ln.bias, (512,)), (w2, (256, 512)))
+        for t, shape in want:  # (the kernels hard-code these widths: a mismatch would read or write out of bounds)
+            if tuple(t.shape) != shape or t.dtype != torch.float16 or not t.is_contiguous() or t.device != x.device:
+                raise PluginError(f"ffn_backward: expected a contiguous fp16 tensor {shape} on {x.device}, got "
+                                  f"{tuple(t.shape)} {t.dtype} on {t.device}")
+        if out is None:
+            f32 = dict(dtype=torch.float32, device=x.device)
+            out = [torch.empty_like(x), torch.empty_like(c0), torch.empty_like(c1)]
+            out += [torch.empty(s, **f32) for s in (w.shape, b.shape, b.shape, b.shape, w2.shape, (w2.shape[0],))] \
+                if need_params else [None] * 6
+        stream = stream_of(x)
+        ws = _workspace(x.device, stream, _lib.load().lg_ffn_backward_workspace(m))
+        call("lg_ffn_backward", x.data_ptr(), c0.data_ptr(), c1.data_ptr(), heads, n0, n1, pr, w.data_ptr(), b.data_ptr(),
+             ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), w2.data_ptr(), dy.data_ptr(), *(_ptr(t) for t in out),
+             ws.data_ptr(), stream)
+        return tuple(out)
 
     @staticmethod
     def ffn_proj(x, c0, c1, b, ln: nn.LayerNorm, b2, packed, kind, b3, splits, cos=None, sin=None, n_store=0):

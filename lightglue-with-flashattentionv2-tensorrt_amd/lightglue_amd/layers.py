@@ -162,6 +162,23 @@ class CrossBlock(nn.Module):
         return x + _ffn_apply(self.ffn, torch.cat((x, self.to_out(merged)), -1), hip)
 
 
+def ffn_residual(block: nn.Module, proj: nn.Linear, x: torch.Tensor, ctx0: torch.Tensor, ctx1: torch.Tensor) -> torch.Tensor:
+    """SelfBlock.finish / CrossBlock.finish for training (fp16, 4 x 64 heads, on the GPU): x + ffn([x | proj(merged
+    contexts)]) as torch.ops.lightglue_amd.ffn, whose backward is lg_ffn_backward. proj (out_proj / to_out) is folded
+    into ffn[0] by _ffn_in_fused's formula, here in fp32 framework ops that autograd sees (not the cached, no_grad
+    copy the inference paths use), so gradients reach ffn[0], proj, the LayerNorm and ffn[3] as well as x and the
+    contexts [P, 4, ni, 64]."""
+    if not _fused_ok(x, block):
+        raise PluginError("ffn_residual: the fp16 model with 4 heads of 64 only")
+    lin, ln, out = block.ffn[0], block.ffn[1], block.ffn[3]
+    d = proj.weight.shape[0]
+    w = lin.weight.float()
+    wm = w[:, d:]
+    w1 = torch.cat((w[:, :d], wm @ proj.weight.float()), 1).to(x.dtype)
+    b1 = (lin.bias.float() + wm @ proj.bias.float()).to(x.dtype)
+    return torch.ops.lightglue_amd.ffn(x, ctx0, ctx1, w1, b1, ln.weight, ln.bias, float(ln.eps), out.weight, out.bias)
+
+
 class TransformerLayer(nn.Module):
     def __init__(self, d: int, heads: int) -> None:
         super().__init__()

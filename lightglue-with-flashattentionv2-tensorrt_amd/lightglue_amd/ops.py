@@ -16,11 +16,16 @@ PyTorch-ROCm module via a torch.library op that invokes enqueue on torch.cuda.cu
 * ``torch.ops.lightglue_amd.assign_nll(v, m, zc, gt0, gt1, m_len=None, n_len=None) -> [loss, dv]``: the matcher's
   training loss per pair and its gradient in v (csrc/lightglue_assign_nll.hip), differentiable in v.
 
+* ``torch.ops.lightglue_amd.ffn(x, ctx0, ctx1, w1, b1, gamma, beta, eps, w2, b2) -> out``: the matcher's FFN block
+  with its residual on unpacked (training) weights (lg_linear_cat_ffn), differentiable in everything but eps through
+  ``ffn_backward(x, ctx0, ctx1, w1, b1, gamma, beta, eps, w2, dy)`` (csrc/lightglue_ffn_backward.hip).
+
 Only a CUDA (HIP) kernel is registered: a CPU tensor has no implementation to dispatch to and
 raises (no CPU fallback). The fake (meta) implementations give shapes/dtypes for tracing.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
@@ -133,3 +138,65 @@ def _assign_nll_backward(ctx, grads):
 
 
 assign_nll_op.register_autograd(_assign_nll_backward, setup_context=_assign_nll_setup_context)
+
+
+@torch.library.custom_op("lightglue_amd::ffn", mutates_args=(), device_types="cuda")
+def ffn_op(x: torch.Tensor, ctx0: torch.Tensor, ctx1: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, gamma: torch.Tensor,
+           beta: torch.Tensor, eps: float, w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """x + ffn([x | merge_heads(ctx0, ctx1)]) [1, M, 256] fp16 with w1 the folded first weight (lg_linear_cat_ffn, no
+    packed stream: training weights change every step)."""
+    from .glue import _Hip
+
+    ln = SimpleNamespace(weight=gamma.contiguous(), bias=beta.contiguous(), eps=eps)
+    return _Hip.ffn(x.contiguous(), ctx0.contiguous(), ctx1.contiguous(), w1.contiguous(), b1.contiguous(), ln,
+                    w2.contiguous(), b2.contiguous())
+
+
+@ffn_op.register_fake
+def _(x, ctx0, ctx1, w1, b1, gamma, beta, eps, w2, b2):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("lightglue_amd::ffn_backward", mutates_args=(), device_types="cuda")
+def ffn_backward_op(x: torch.Tensor, ctx0: torch.Tensor, ctx1: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                    gamma: torch.Tensor, beta: torch.Tensor, eps: float, w2: torch.Tensor, dout: torch.Tensor,
+                    need_params: bool = True) -> List[torch.Tensor]:
+    """(dx, dctx0, dctx1 fp16; dw1, db1, dgamma, dbeta, dw2, db2 fp32) of ffn from its inputs and dout (lg_ffn_backward);
+    without need_params the three data gradients alone (its data-only form: the same bits, no weight kernel)."""
+    from .glue import _Hip
+
+    ln = SimpleNamespace(weight=gamma.contiguous(), bias=beta.contiguous(), eps=eps)
+    out = _Hip.ffn_backward(x.contiguous(), ctx0.contiguous(), ctx1.contiguous(), w1.contiguous(), b1.contiguous(), ln,
+                            w2.contiguous(), dout.contiguous(), need_params)
+    return list(out if need_params else out[:3])
+
+
+@ffn_backward_op.register_fake
+def _(x, ctx0, ctx1, w1, b1, gamma, beta, eps, w2, dout, need_params=True):
+    data = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in (x, ctx0, ctx1)]
+    if not need_params:
+        return data
+    f32 = [w1, b1, gamma, beta, w2, w2.new_empty((w2.shape[0],))]
+    return data + [torch.empty_like(t, dtype=torch.float32, memory_format=torch.contiguous_format) for t in f32]
+
+
+def _ffn_setup_context(ctx, inputs, output):
+    x, ctx0, ctx1, w1, b1, gamma, beta, eps, w2, b2 = inputs
+    ctx.eps = eps
+    ctx.save_for_backward(x, ctx0, ctx1, w1, b1, gamma, beta, w2, b2)
+
+
+def _ffn_backward(ctx, dout):
+    x, ctx0, ctx1, w1, b1, gamma, beta, w2, b2 = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    params = any(need[i] for i in (3, 4, 5, 6, 8, 9))  # (frozen FFN weights: the data-only call)
+    got = torch.ops.lightglue_amd.ffn_backward(x, ctx0, ctx1, w1, b1, gamma, beta, ctx.eps, w2, dout, params)
+    grads = list(got[:3]) + [None] * 7
+    if params:
+        dw1, db1, dg, dbe, dw2, db2 = got[3:]
+        grads[3:] = [dw1.to(w1.dtype), db1.to(b1.dtype), dg.to(gamma.dtype), dbe.to(beta.dtype), None, dw2.to(w2.dtype),
+                     db2.to(b2.dtype)]
+    return tuple(g if g is not None and n else None for g, n in zip(grads, need))
+
+
+ffn_op.register_autograd(_ffn_backward, setup_context=_ffn_setup_context)
