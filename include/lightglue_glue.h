@@ -291,6 +291,36 @@ int32_t lg_ffn_backward(const void* x, const void* ctx0, const void* ctx1, int32
                         const void* w2, const void* dy, void* dx, void* dctx0, void* dctx1, float* dw1, float* db1,
                         float* dgamma, float* dbeta, float* dw2, float* db2, void* workspace, hipStream_t stream);
 
+/* ---- the fused projections' backward (csrc/lightglue_proj_backward.hip) ----
+ * The gradients of a projection Y [m, n] = X [m, 256] W^T + b whose outputs left through a layout epilogue:
+ * lg_linear_qkv_rotary (kind LG_PROJ_QKV), lg_linear_split2 (LG_PROJ_SPLIT2) and lg_linear on the head's
+ * [W_final / scale ; w_match ; 0] (LG_PROJ_PLAIN). New symbols only: LG_GLUE_ABI_VERSION stays 4. fp16 model only,
+ * heads == 4, k = 256; rows pair-major, m = pairs * (n0 + n1) (pair p's n0 rows, then its n1 rows).
+ * G [m, n] = dL/dY in W's row order is gathered from grads[] by kind (an entry may be null: zeros):
+ *   LG_PROJ_QKV    n = 768, W permuted to [q|k|v][head][dim]; grads = dq0, dk0, dv0, dq1, dk1, dv1, fp16
+ *                  [pairs, 4, ni, 64] as mha_hd64_backward writes them; cos, sin [m, 64] fp16 as the forward took
+ *                  them. The q and k parts pass through the transposed rotary, a pair (g0, g1) at (d, d + 1) ->
+ *                  (g0 cos[d] + g1 sin[d + 1], g1 cos[d + 1] - g0 sin[d]) in fp32, rounded once; the v part is copied.
+ *   LG_PROJ_SPLIT2 n = 512, W = [W_qk; W_v]; grads = da0, da1, db0, db1 head-major; G = [merge(da) | merge(db)].
+ *   LG_PROJ_PLAIN  n = n_store, a multiple of 64 in [64, 512] (W's first n_store rows); grads[0] fp32 [m, grad_ld]
+ *                  (lg_assign_nll's dv), grad_ld >= n_store and a multiple of 4; G = fp16 of its first n_store
+ *                  columns. n0, n1, pairs only give m.
+ *   dx [m, 256] = fp16(G W (+ dx_add)): one rounding of the fp32 sum. dx_add (nullable) fp16 [m, 256] is the gradient
+ *                 x already has from the block's residual (lg_ffn_backward's dx); dx may be dx_add itself.
+ *   dw [n, 256] = G^T X and db [n] = column sums of G, fp32 (either may be null; both null: the data-only call, the
+ *                 pack and rows kernels alone, dx with the same bits).
+ * m == 0 succeeds without a launch and writes nothing. Otherwise every element of every output given is written.
+ * Pointers 16-B aligned (cos, sin 8-B); dx's bytes must overlap neither x's nor a gradient's, nor dx_add's unless
+ * dx == dx_add; m <= 2^20; workspace >=
+ * lg_proj_backward_workspace(kind, m, n_store) bytes (0 for an unknown kind or width). cos, sin, grad_ld and n_store
+ * are read only by the kinds that name them. Arguments are checked before any device call. No float atomics, no
+ * host synchronisation, no allocation: capturable, bitwise reproducible. */
+size_t lg_proj_backward_workspace(int32_t kind, int32_t m_rows, int32_t n_store);
+int32_t lg_proj_backward(int32_t kind, const void* x, const void* w, const void* cosv, const void* sinv,
+                         const void* const* grads, int32_t grad_ld, int32_t n_store, int32_t heads, int32_t n0,
+                         int32_t n1, int32_t pairs, const void* dx_add, void* dx, float* dw, float* db, void* workspace,
+                         hipStream_t stream);
+
 /* ---- adaptive depth and width (csrc/lightglue_adaptive.hip; fp16 rows of 256 channels) ----
  * The published LightGlue rules the reference ships the pieces of (TokenConfidence lightglue.py:54-66,
  * MatchAssignment.get_matchability :230-232) and never applies. New symbols only: LG_GLUE_ABI_VERSION

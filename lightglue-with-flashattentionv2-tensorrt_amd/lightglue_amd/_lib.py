@@ -171,6 +171,8 @@ SIGNATURES.update({
     "lg_ffn_backward_workspace": ([_I], _S),
     "lg_ffn_backward": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                          _P, _P, _P], _I),
+    "lg_proj_backward_workspace": ([_I, _I, _I], _S),
+    "lg_proj_backward": ([_I, _P, _P, _P, _P, ctypes.POINTER(_P), _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     # adaptive depth / width (csrc/lightglue_adaptive.hip)
     "lg_token_scores": ([_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P, _P, _P], _I),
     "lg_compact_rows": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I,

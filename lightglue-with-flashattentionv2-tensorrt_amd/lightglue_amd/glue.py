@@ -125,6 +125,47 @@ class _Hip:
         return tuple(out)
 
     @staticmethod
+    def proj_backward(kind, x, w, grads, splits, cos=None, sin=None, n_store=None, dx_add=None, need_params=True, out=None):
+        """lg_proj_backward: the gradients of a fused projection of x [1, M, 256] with w [n, 256] -> (dx fp16 [1, M, 256],
+        dw fp32 [n, 256], db fp32 [n]; dw, db None without need_params: the data-only call). kind 2 (Wqkv + rotary,
+        n = 768): grads = (dq0, dk0, dv0, dq1, dk1, dv1) head-major, cos / sin [1, M, 64]; kind 1 (to_qk | to_v, n = 512):
+        grads = (da0, da1, db0, db1); kind 3 (the head's rows, n = n_store): grads = (dv,) fp32 with M rows of any
+        width >= n_store. An entry of grads may be None (zeros). dx_add [1, M, 256]: added to dx before its rounding.
+        out = (dx, dw, db): tensors to write instead of new ones."""
+        n0, n1, pr = _sp(splits)
+        m = pr * (n0 + n1)
+        n = {1: 512, 2: 768, 3: n_store}.get(kind)
+        if n is None or n < 64 or n > 768 or n % 64:
+            raise PluginError(f"proj_backward: kind {kind} with n_store {n_store}")
+        head = [(pr, 4, ni, 64) for ni in (n0, n1)]
+        shapes = {1: [head[0], head[1]] * 2, 2: [head[0]] * 3 + [head[1]] * 3, 3: [None]}[kind]
+        if len(grads) != len(shapes):
+            raise PluginError(f"proj_backward: kind {kind} takes {len(shapes)} gradients, got {len(grads)}")
+        ld = n
+        if kind == 3 and grads[0] is not None:  # M rows of ld >= n channels, 16-B rows
+            ld = grads[0].shape[-1]
+            shapes = [tuple(grads[0].shape) if grads[0].numel() == m * ld and ld >= n and ld % 4 == 0 else (m, f">= {n}, % 4")]
+        want = [(x, (1, m, 256)), (w, (max(n, w.shape[0]) if kind == 3 else n, 256))]
+        want += [(dx_add, (1, m, 256))] if dx_add is not None else []
+        want += [(cos, (1, m, 64)), (sin, (1, m, 64))] if kind == 2 else []
+        want += [(g, shape) for g, shape in zip(grads, shapes) if g is not None]
+        for t, shape in want:  # (the kernels hard-code these widths: a mismatch would read or write out of bounds)
+            dt = torch.float32 if kind == 3 and t is grads[0] else torch.float16
+            if t is None or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != x.device:
+                raise PluginError(f"proj_backward: expected a contiguous {dt} tensor {shape} on {x.device}, got "
+                                  f"{None if t is None else (tuple(t.shape), t.dtype, t.device)}")
+        if out is None:
+            f32 = dict(dtype=torch.float32, device=x.device)
+            make = torch.zeros if m == 0 else torch.empty  # (no rows: nothing is launched)
+            out = [torch.empty_like(x)] + ([make((n, 256), **f32), make((n,), **f32)] if need_params else [None, None])
+        stream = stream_of(x)
+        ws = _workspace(x.device, stream, _lib.load().lg_proj_backward_workspace(kind, m, n))
+        ptrs = (ctypes.c_void_p * 6)(*([_ptr(g) for g in grads] + [None] * (6 - len(grads))))
+        call("lg_proj_backward", kind, x.data_ptr(), w.data_ptr(), _ptr(cos), _ptr(sin), ptrs, ld, n, 4, n0, n1, pr,
+             _ptr(dx_add), *(_ptr(t) for t in out), ws.data_ptr(), stream)
+        return tuple(out)
+
+    @staticmethod
     def ffn_proj(x, c0, c1, b, ln: nn.LayerNorm, b2, packed, kind, b3, splits, cos=None, sin=None, n_store=0):
         """lg_linear_cat_ffn_proj: (x' = x + ffn([x | merge_heads(c0, c1)]), the next projection of x')
         in one launch; kind 1 -> ((a0, a1), (b0, b1)) per-image heads (to_qk | to_v), kind 2 -> q/k/v

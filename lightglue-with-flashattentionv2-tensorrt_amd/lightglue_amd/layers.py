@@ -121,6 +121,20 @@ class SelfBlock(nn.Module):
             a += ni
         return out
 
+    def qkv_train(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, splits: Sequence[int]):
+        """The fused Wqkv + rotary for training (fp16, 4 x 64 heads, on the GPU): [q0, k0, v0, q1, k1, v1] head-major
+        [P, 4, ni, 64] as torch.ops.lightglue_amd.qkv_rotary, whose backward is lg_proj_backward. The rows are put in
+        _qkv_perm's order here, by fp32 indexing that autograd sees (not the cached, no_grad copy), so the kernel's dW
+        and db reach Wqkv; cos and sin get no gradient."""
+        if not _fused_ok(x, self):
+            raise PluginError("qkv_train: the fp16 model with 4 heads of 64 only")
+        hd = self.heads * self.head_dim
+        new = torch.arange(3 * hd, device=x.device)
+        old = (new % hd) * 3 + new // hd
+        n0, n1, pr = splits[0], splits[1], splits[2] if len(splits) > 2 else 1
+        return torch.ops.lightglue_amd.qkv_rotary(x, self.Wqkv.weight.float()[old], self.Wqkv.bias.float()[old], cos, sin,
+                                                  n0, n1, pr)
+
     def finish(self, x: torch.Tensor, contexts: Sequence[torch.Tensor], hip: bool = False) -> torch.Tensor:
         if hip:  # [x | heads merged] in one pass, out_proj folded into ffn[0]
             w, b = _ffn_in_fused(self, self.out_proj, x.dtype)
@@ -153,6 +167,15 @@ class CrossBlock(nn.Module):
         """hip path: to_qk and to_v as ONE GEMM on stacked weights, heads split from its halves."""
         w, b = _cross_qkv(self, x.dtype)
         return _Hip.split_heads2_ld(F.linear(x, w, b), self.heads, splits)
+
+    def qk_v_train(self, x: torch.Tensor, splits: Sequence[int]):
+        """qk_v for training: [qk0, qk1, v0, v1] head-major as torch.ops.lightglue_amd.split2 (backward:
+        lg_proj_backward) on [to_qk ; to_v] stacked in fp32 framework ops that autograd sees."""
+        if not _fused_ok(x, self):
+            raise PluginError("qk_v_train: the fp16 model with 4 heads of 64 only")
+        w = torch.cat((self.to_qk.weight.float(), self.to_v.weight.float()), 0)
+        b = torch.cat((self.to_qk.bias.float(), self.to_v.bias.float()), 0)
+        return torch.ops.lightglue_amd.split2(x, w, b, splits[0], splits[1], splits[2] if len(splits) > 2 else 1)
 
     def finish(self, x: torch.Tensor, ms: Sequence[torch.Tensor], hip: bool = False) -> torch.Tensor:
         if hip:  # [x | heads merged] in one pass, to_out folded into ffn[0]
@@ -276,10 +299,18 @@ class MatchAssignment(nn.Module):
 
         return _cached(self, f"_assign_aug{rows}", (fp.weight, fp.bias, mt.weight, mt.bias), dtype, build)
 
-    def project_rows(self, x: torch.Tensor, pr: int, m: int, n: int) -> torch.Tensor:
+    def project_rows(self, x: torch.Tensor, pr: int, m: int, n: int, train: bool = False) -> torch.Tensor:
         """The head's ONE projection of both images' rows x [1, P*(m+n), d] with [W_final / scale ;
         w_match ; 0] -> v [P, m + n, 384]: the scaled descriptors at channels 0..d-1, the matchability
-        logit at channel d."""
+        logit at channel d. train: the same kernel and bits as torch.ops.lightglue_amd.project (backward:
+        lg_proj_backward) on aug_weights' formula in fp32 framework ops that autograd sees (not the cached, no_grad
+        copy), so gradients reach x, final_proj and matchability."""
+        if train:
+            fp, mt = self.final_proj, self.matchability
+            d = fp.weight.shape[1]
+            w = torch.cat((fp.weight.float() / self.scale, mt.weight.float(), fp.weight.new_zeros((383 - d, d), dtype=torch.float32)), 0)
+            b = torch.cat((fp.bias.float() / self.scale, mt.bias.float(), fp.bias.new_zeros((383 - d,), dtype=torch.float32)), 0)
+            return torch.ops.lightglue_amd.project(x, w, b).view(pr, m + n, 384)
         w, b = self.aug_weights(x.dtype, 384)
         return _Hip.linear(x, w, b).view(pr, m + n, 384)
 
@@ -301,11 +332,13 @@ class MatchAssignment(nn.Module):
     def loss_rows(self, x: torch.Tensor, pr: int, m: int, n: int, gt0: torch.Tensor, gt1: torch.Tensor,
                   lens=None) -> torch.Tensor:
         """forward_rows' projection, then lg_assign_nll (loss.assignment_nll): the training loss of the scores
-        forward_rows would return, fp32 [P]. The gradient stops at v: project_rows has no backward yet, so
-        this trains nothing upstream of the head by itself; take dloss/dv from assignment_nll on a leaf v."""
+        forward_rows would return, fp32 [P], differentiable in x, final_proj and matchability (project_rows' training
+        form; dloss/dv passes to lg_proj_backward in v's fp16). Where nothing asks for a gradient (no_grad, or x and the
+        head's parameters all frozen) it takes the cached weights as forward_rows does: the same bits."""
         from .loss import assignment_nll
 
-        return assignment_nll(self.project_rows(x, pr, m, n), m, x.shape[-1], gt0, gt1, lens)
+        train = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        return assignment_nll(self.project_rows(x, pr, m, n, train=train), m, x.shape[-1], gt0, gt1, lens)
 
     def forward(self, d0: torch.Tensor, d1: torch.Tensor, hip: bool = False) -> torch.Tensor:
         m0 = self.final_proj(d0) / self.scale

@@ -20,6 +20,11 @@ PyTorch-ROCm module via a torch.library op that invokes enqueue on torch.cuda.cu
   with its residual on unpacked (training) weights (lg_linear_cat_ffn), differentiable in everything but eps through
   ``ffn_backward(x, ctx0, ctx1, w1, b1, gamma, beta, eps, w2, dy)`` (csrc/lightglue_ffn_backward.hip).
 
+* ``torch.ops.lightglue_amd.qkv_rotary(x, w_perm, b_perm, cos, sin, n0, n1, pairs) -> [q0, k0, v0, q1, k1, v1]``,
+  ``split2(x, w, b, n0, n1, pairs) -> [a0, a1, b0, b1]`` and ``project(x, w, b) -> v``: the fused projections
+  (lg_linear_qkv_rotary, lg_linear_split2, lg_linear), differentiable in x, w and b through
+  ``proj_backward(kind, x, w, grads, n0, n1, pairs, ...)`` (csrc/lightglue_proj_backward.hip).
+
 Only a CUDA (HIP) kernel is registered: a CPU tensor has no implementation to dispatch to and
 raises (no CPU fallback). The fake (meta) implementations give shapes/dtypes for tracing.
 """
@@ -200,3 +205,102 @@ def _ffn_backward(ctx, dout):
 
 
 ffn_op.register_autograd(_ffn_backward, setup_context=_ffn_setup_context)
+
+
+# ---- the fused projections, differentiable (csrc/lightglue_proj_backward.hip) ----
+# Their forwards are the inference kernels (lg_linear_qkv_rotary, lg_linear_split2, lg_linear); w and b may be of any
+# floating dtype and are cast to x's here, so that a caller who derives them in fp32 gets fp32 gradients back.
+def _as(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    return t.to(like.dtype).contiguous()
+
+
+@torch.library.custom_op("lightglue_amd::qkv_rotary", mutates_args=(), device_types="cuda")
+def qkv_rotary_op(x: torch.Tensor, w_perm: torch.Tensor, b_perm: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                  n0: int, n1: int, pairs: int) -> List[torch.Tensor]:
+    """x [1, M, 256] -> [q0, k0, v0, q1, k1, v1] head-major [pairs, 4, ni, 64]: Wqkv (rows in _qkv_perm's order) + rotary."""
+    from .glue import _Hip
+
+    i0, i1 = _Hip.linear_qkv_rotary(x.contiguous(), _as(w_perm, x), _as(b_perm, x), cos.contiguous(), sin.contiguous(), 4,
+                                    (n0, n1, pairs))
+    return [*i0, *i1]
+
+
+@qkv_rotary_op.register_fake
+def _(x, w_perm, b_perm, cos, sin, n0, n1, pairs):
+    return [x.new_empty((pairs, 4, n, 64)) for n in (n0, n0, n0, n1, n1, n1)]
+
+
+@torch.library.custom_op("lightglue_amd::split2", mutates_args=(), device_types="cuda")
+def split2_op(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, n0: int, n1: int, pairs: int) -> List[torch.Tensor]:
+    """x [1, M, 256] -> [a0, a1, b0, b1] head-major: [to_qk ; to_v] as one GEMM."""
+    from .glue import _Hip
+
+    (a0, a1), (b0, b1) = _Hip.linear_split2(x.contiguous(), _as(w, x), _as(b, x), 4, (n0, n1, pairs))
+    return [a0, a1, b0, b1]
+
+
+@split2_op.register_fake
+def _(x, w, b, n0, n1, pairs):
+    return [x.new_empty((pairs, 4, n, 64)) for n in (n0, n1, n0, n1)]
+
+
+@torch.library.custom_op("lightglue_amd::project", mutates_args=(), device_types="cuda")
+def project_op(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """x [1, M, 256] -> x w^T + b [1, M, n], n a multiple of 64 up to 512 (the head's rows)."""
+    from .glue import _Hip
+
+    return _Hip.linear(x.contiguous(), _as(w, x), _as(b, x))
+
+
+@project_op.register_fake
+def _(x, w, b):
+    return x.new_empty((1, x.shape[1], w.shape[0]))
+
+
+@torch.library.custom_op("lightglue_amd::proj_backward", mutates_args=(), device_types="cuda")
+def proj_backward_op(kind: int, x: torch.Tensor, w: torch.Tensor, grads: List[Optional[torch.Tensor]], n0: int, n1: int,
+                     pairs: int, cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
+                     dx_add: Optional[torch.Tensor] = None, need_params: bool = True) -> List[torch.Tensor]:
+    """[dx fp16, dw fp32 [n, 256], db fp32 [n]] of the projection of kind 1 (split2), 2 (qkv_rotary) or 3 (project, n =
+    w's rows) from the gradients of its outputs, None for an unused one (lg_proj_backward); without need_params [dx]
+    alone (the data-only form: the same bits, no weight kernel)."""
+    from .glue import _Hip
+
+    cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    out = _Hip.proj_backward(kind, x.contiguous(), _as(w, x), [cont(g) for g in grads], (n0, n1, pairs), cont(cos), cont(sin),
+                             w.shape[0], cont(dx_add), need_params)
+    return list(out if need_params else out[:1])
+
+
+@proj_backward_op.register_fake
+def _(kind, x, w, grads, n0, n1, pairs, cos=None, sin=None, dx_add=None, need_params=True):
+    dx = torch.empty_like(x, memory_format=torch.contiguous_format)
+    f32 = dict(dtype=torch.float32)
+    return [dx, w.new_empty(tuple(w.shape), **f32), w.new_empty((w.shape[0],), **f32)] if need_params else [dx]
+
+
+def _proj_autograd(op, kind, nw, n_in):
+    """Registers op's backward: inputs (x, w, b, ...) with the integers (n0, n1, pairs) last where the op has them."""
+
+    def setup(ctx, inputs, output):
+        x, w, b = inputs[:3]
+        ctx.tail = inputs[3 + nw:]
+        ctx.b_dtype = b.dtype
+        ctx.set_materialize_grads(False)  # (an unused output's gradient stays None: a null pointer, not a zero tensor)
+        ctx.save_for_backward(x, w, *inputs[3:3 + nw])
+
+    def backward(ctx, grads):
+        x, w, *cs = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = list(grads) if kind != 3 else [None if grads is None else grads.float()]
+        n0, n1, pairs = ctx.tail if kind != 3 else (x.shape[1], 0, 1)
+        got = torch.ops.lightglue_amd.proj_backward(kind, x, w, grads, n0, n1, pairs, *cs, need_params=need[1] or need[2])
+        dw, db = (got[1].to(w.dtype), got[2].to(ctx.b_dtype)) if len(got) > 1 else (None, None)
+        return (got[0] if need[0] else None, dw if need[1] else None, db if need[2] else None) + (None,) * (n_in - 3)
+
+    op.register_autograd(backward, setup_context=setup)
+
+
+_proj_autograd(qkv_rotary_op, 2, 2, 8)
+_proj_autograd(split2_op, 1, 0, 6)
+_proj_autograd(project_op, 3, 0, 3)
