@@ -199,6 +199,40 @@ int32_t mha_hd64_backward_fp32(const void* q, const void* k, const void* v, cons
  * column kernel's query split. 0 for an invalid in_type and for empty shapes. */
 size_t mha_hd64_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t nq, int32_t nkv, int32_t in_type);
 
+/* ---- grouped, ragged backward (csrc/mha_hd64_backward.hip; no reference counterpart) ----
+ * The backward of several calls of (possibly) different shapes, each item of each call with its own count
+ * of real query rows and keys, in one set of launches: what a matcher layer's grouped attention launches
+ * (self0 | self1, cross 0->1 | 1->0, all pairs inside) need on a padded batch. Tensors as for
+ * mha_hd64_backward_fp16; in_type HALF only.
+ * q_lens[i] / kv_lens[i] are DEVICE tables of calls[i].batch int32 values; an entry may be NULL, and so may
+ * either array: NULL means all rows. The counts are read on the device when the kernels run (one scalar
+ * load each) and clamped into [1, n]: a captured launch replays with whatever the tables hold then. No
+ * host synchronisation, no allocation, no floating-point atomics: results are bitwise reproducible.
+ * For item b of call i, rows of q, o and dout at or past q_lens[i][b] and rows of k and v at or past
+ * kv_lens[i][b] are never read (the buffer descriptors end at the count: padding may hold NaN or Inf).
+ * The gradients are those of attention over the item's first kv_len keys, for its first q_len query rows,
+ * with the arithmetic of the backward above in its order: with one query split the valid region has the
+ * bits of the single-call backward on the contiguous slices. Every element of dq, dk and dv is written on
+ * every call; dq rows at or past q_len and dk, dv rows at or past kv_len are zeros.
+ * One rows, one cols and (when a call splits its queries) one reduce launch per chunk of 4 calls; the
+ * query split is planned from the padded shapes over the chunk's workgroups together. Chunks reuse the
+ * workspace in stream order, and the query returns the largest chunk's need.
+ * BAD_PARAM before any device call: FLOAT, null calls with n_calls > 0, a null or misaligned tensor,
+ * table or workspace pointer, a negative size, nkv < 1 with nq > 0. WORKSPACE: ws_bytes below the
+ * query's value. n_calls == 0, and calls with nq, batch or heads of 0, are successful no-ops. */
+typedef struct mha_hd64_bwd_call {
+    const void *q, *k, *v, *o, *dout;   /* fp16 [batch, heads, nq | nkv, 64], contiguous, 16-B aligned */
+    void *dq, *dk, *dv;
+    int32_t batch, heads, nq, nkv;
+} mha_hd64_bwd_call_t;
+
+int32_t mha_hd64_backward_grouped_lens(const mha_hd64_bwd_call_t* calls, const int32_t* const* q_lens,
+                                       const int32_t* const* kv_lens, int32_t n_calls, int32_t in_type,
+                                       void* workspace, size_t ws_bytes, hipStream_t stream);
+/* Workspace bytes of that call: per call of the largest chunk L and D (fp32 [batch, heads, nq] each) and
+ * the partial dK / dV of its query split. 0 for an empty group, an invalid in_type and FLOAT. */
+size_t  mha_hd64_backward_grouped_workspace_bytes(const mha_hd64_bwd_call_t* calls, int32_t n_calls, int32_t in_type);
+
 /* ---- grouped launcher ----
  * Several independent calls of (possibly) different shapes in one launch. A LightGlue layer
  * makes four attention calls whose inputs are all ready together: SelfBlock on image 0 and on

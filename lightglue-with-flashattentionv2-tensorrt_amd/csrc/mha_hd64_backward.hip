@@ -21,6 +21,14 @@
 // P and dS are rounded to fp16 once, where they become MFMA operands; everything else stays fp32 until
 // the final store. Tails are masked in the kernels: loads past nq / nkv return zeros (buffer
 // descriptors sized per head), masked keys and queries get P = 0 exactly, and no row past the end is stored.
+//
+// The grouped form (mha_hd64_backward_grouped_lens) runs up to 4 calls of different shapes, each item with
+// its own query and key count, as one rows, one cols and at most one reduce launch. The tile code is the
+// same (the bodies below are templates over LENS); what differs is where a workgroup gets its shape from:
+// it finds its call by comparing its index with the calls' prefix sums in the kernel arguments, reads its
+// item's two counts by scalar loads, ends its buffer descriptors at the counts (padding is never read),
+// streams only the tiles below them, and writes zeros into the padded rows of dQ, dK and dV. A workgroup
+// with nothing below its counts writes its zeros and leaves before the first barrier.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,6 +66,40 @@ struct BwdArgs {
     int splits;           // query splits of the cols kernel
     int tiles_per_split;  // query blocks per split
 };
+
+// One launch of n <= kGroupCalls calls: call i owns workgroups [end[i - 1], end[i]) of the rows and of the cols
+// grid (end[i] of an unused slot = the grid, so that no workgroup selects it). q_lens / kv_lens: per call a
+// device table of `batch` int32 counts, or null (every row); heads turns a workgroup's batch·head into its item.
+struct BwdGroupArgs {
+    BwdArgs c[kGroupCalls];
+    const int* q_lens[kGroupCalls];
+    const int* kv_lens[kGroupCalls];
+    int heads[kGroupCalls];
+    int rows_end[kGroupCalls];
+    int cols_end[kGroupCalls];
+};
+// A workgroup's call and its index inside it, from the prefix sums (wave-uniform compares and selects).
+__device__ __forceinline__ int group_call(const int (&end)[kGroupCalls], int block, int& local) {
+    const int ci = (block >= end[0]) + (block >= end[1]) + (block >= end[2]);
+    local = block - (ci == 0 ? 0 : ci == 1 ? end[0] : ci == 2 ? end[1] : end[2]);
+    return ci;
+}
+template <typename T>
+__device__ __forceinline__ T group_pick(const T (&tab)[kGroupCalls], int ci) {
+    T x = tab[0];
+#pragma unroll
+    for (int i = 1; i < kGroupCalls; ++i)
+        if (ci == i) x = tab[i];
+    return x;
+}
+// An item's count: one scalar load (a uniform address in the constant address space), clamped into [1, n];
+// a null table means n.
+__device__ __forceinline__ int group_len(const int* tab, int item, int n) {
+    typedef const __attribute__((address_space(4))) int* const_int_t;
+    int len = n;
+    if (tab) len = ((const_int_t)(uintptr_t)tab)[__builtin_amdgcn_readfirstlane(item)];
+    return min(max(len, 1), n);
+}
 
 __device__ __forceinline__ float xhalf_sum(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -111,22 +153,41 @@ __device__ __forceinline__ f16x8 acc_frag(const f32x16& c, int ss) {
     return b;
 }
 
+// One query row of dQᵀ (dims 0..31 in dq0, 32..63 in dq1, times 1/8): this lane's 4-dim groups.
+template <typename TOut>
+__device__ __forceinline__ void store_dq_row(TOut* dst, const f32x16& dq0, const f32x16& dq1) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        store4<TOut>(dst + 8 * g, dq0[4 * g] * 0.125f, dq0[4 * g + 1] * 0.125f, dq0[4 * g + 2] * 0.125f,
+                     dq0[4 * g + 3] * 0.125f);
+        store4<TOut>(dst + 32 + 8 * g, dq1[4 * g] * 0.125f, dq1[4 * g + 1] * 0.125f, dq1[4 * g + 2] * 0.125f,
+                     dq1[4 * g + 3] * 0.125f);
+    }
+}
+
 // ----------------------------------------------------------------------------------------
 // rows: grid = qtiles * bh. Lane = query (r = lane & 31 of the wave's 32), registers = keys.
+// `block` is the workgroup's index inside its call. LENS: the item has q_len real query rows and kv_len
+// real keys inside its [a.nq] / [a.nkv] slabs (the strides stay the padded sizes).
 // ----------------------------------------------------------------------------------------
-template <typename TOut>
-__global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_rows_kernel(BwdArgs a) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * kRowStage];
-    lds_char* const lds = (lds_char*)smem;
+template <typename TOut, bool LENS>
+__device__ __forceinline__ void bwd_rows_body(const BwdArgs& a, int block, int q_len, int kv_len, lds_char* lds) {
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bh = blockIdx.x / a.qtiles, qtile = blockIdx.x % a.qtiles;
-    const int nq = a.nq, nkv = a.nkv;
-    const size_t qo = (size_t)bh * nq * kHeadDim, ko = (size_t)bh * nkv * kHeadDim;
+    const int bh = block / a.qtiles, qtile = block % a.qtiles;
+    const int nq = LENS ? q_len : a.nq, nkv = LENS ? kv_len : a.nkv;
+    const size_t qo = (size_t)bh * a.nq * kHeadDim, ko = (size_t)bh * a.nkv * kHeadDim;
     const auto q_rs = make_rsrc(a.q + qo, (unsigned)nq * 128u), o_rs = make_rsrc(a.o + qo, (unsigned)nq * 128u);
     const auto do_rs = make_rsrc(a.dout + qo, (unsigned)nq * 128u);
     const auto k_rs = make_rsrc(a.k + ko, (unsigned)nkv * 128u), v_rs = make_rsrc(a.v + ko, (unsigned)nkv * 128u);
     const int q = qtile * 64 + 32 * wave + r;
+    TOut* const dq_row = reinterpret_cast<TOut*>(a.dq) + qo + (size_t)q * kHeadDim + 4 * hh;
+    if constexpr (LENS) {
+        if (qtile * 64 >= nq) {  // (workgroup-uniform) a block of padding: zeros, and no barrier was reached
+            if (q < a.nq) store_dq_row<TOut>(dq_row, f32x16{}, f32x16{});
+            return;
+        }
+    }
 
     // Q and dO fragments (B operands: lane holds dims 16s + 8hh .. +7 of its query) and D
     f16x8 qf[4], dof[4];
@@ -147,7 +208,7 @@ __global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_rows_kernel(BwdArgs 
 
     unsigned tr0, tr1;
     trans_lane(lane, tr0, tr1);
-    const int nt = a.ktiles;
+    const int nt = LENS ? (nkv + 63) / 64 : a.ktiles;
 
     // Sᵀ·log2e/8 of the tile at `base`, masked keys at kMaskedScore; ok bit 16h + i = key of register i, half h, is real
     auto scores = [&](unsigned base, int t, f32x16 (&x)[2], unsigned& ok) {
@@ -248,38 +309,51 @@ __global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_rows_kernel(BwdArgs 
     });
 
     if (q < nq) {
-        TOut* const dst = reinterpret_cast<TOut*>(a.dq) + qo + (size_t)q * kHeadDim + 4 * hh;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            store4<TOut>(dst + 8 * g, dq0[4 * g] * 0.125f, dq0[4 * g + 1] * 0.125f, dq0[4 * g + 2] * 0.125f,
-                         dq0[4 * g + 3] * 0.125f);
-            store4<TOut>(dst + 32 + 8 * g, dq1[4 * g] * 0.125f, dq1[4 * g + 1] * 0.125f, dq1[4 * g + 2] * 0.125f,
-                         dq1[4 * g + 3] * 0.125f);
-        }
+        store_dq_row<TOut>(dq_row, dq0, dq1);
         if (hh == 0) {
-            a.lse[(size_t)bh * nq + q] = L;
-            a.delta[(size_t)bh * nq + q] = D;
+            a.lse[(size_t)bh * a.nq + q] = L;
+            a.delta[(size_t)bh * a.nq + q] = D;
         }
+    } else if (LENS && q < a.nq) {  // padded rows of a live block (their L and D are never read)
+        store_dq_row<TOut>(dq_row, f32x16{}, f32x16{});
     }
+}
+
+template <typename TOut>
+__global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_rows_kernel(BwdArgs a) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * kRowStage];
+    bwd_rows_body<TOut, false>(a, blockIdx.x, 0, 0, (lds_char*)smem);
+}
+// grouped: grid = the calls' qtiles * bh, one after the other
+template <typename TOut>
+__global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_rows_group_kernel(BwdGroupArgs g) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * kRowStage];
+    int block;
+    const int ci = group_call(g.rows_end, blockIdx.x, block);
+    const BwdArgs a = group_pick(g.c, ci);
+    const int item = (block / a.qtiles) / group_pick(g.heads, ci);
+    bwd_rows_body<TOut, true>(a, block, group_len(group_pick(g.q_lens, ci), item, a.nq),
+                              group_len(group_pick(g.kv_lens, ci), item, a.nkv), (lds_char*)smem);
 }
 
 // ----------------------------------------------------------------------------------------
 // cols: grid = splits * ktiles * bh. Lane = key (r of the wave's 32), registers = queries.
+// `block` and LENS as for the rows. LENS: a split's query blocks end at ceil(q_len / 64); a workgroup whose
+// keys or query blocks all lie past the counts runs no tile and stores zeros (outputs or partials alike, so
+// the reduce needs no condition), and so do the padded keys of a live block.
 // ----------------------------------------------------------------------------------------
-template <typename TOut>
-__global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_kernel(BwdArgs a) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * kColStage];
-    lds_char* const lds = (lds_char*)smem;
+template <typename TOut, bool LENS>
+__device__ __forceinline__ void bwd_cols_body(const BwdArgs& a, int block, int q_len, int kv_len, lds_char* lds) {
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int split = blockIdx.x % a.splits, ktile = (blockIdx.x / a.splits) % a.ktiles;
-    const int bh = blockIdx.x / (a.splits * a.ktiles);
-    const int nq = a.nq, nkv = a.nkv;
-    const size_t qo = (size_t)bh * nq * kHeadDim, ko = (size_t)bh * nkv * kHeadDim;
+    const int split = block % a.splits, ktile = (block / a.splits) % a.ktiles;
+    const int bh = block / (a.splits * a.ktiles);
+    const int nq = LENS ? q_len : a.nq, nkv = LENS ? kv_len : a.nkv;
+    const size_t qo = (size_t)bh * a.nq * kHeadDim, ko = (size_t)bh * a.nkv * kHeadDim;
     const auto q_rs = make_rsrc(a.q + qo, (unsigned)nq * 128u), do_rs = make_rsrc(a.dout + qo, (unsigned)nq * 128u);
     const auto k_rs = make_rsrc(a.k + ko, (unsigned)nkv * 128u), v_rs = make_rsrc(a.v + ko, (unsigned)nkv * 128u);
-    const auto l_rs = make_rsrc(a.lse + (size_t)bh * nq, (unsigned)nq * 4u);
-    const auto d_rs = make_rsrc(a.delta + (size_t)bh * nq, (unsigned)nq * 4u);
+    const auto l_rs = make_rsrc(a.lse + (size_t)bh * a.nq, (unsigned)nq * 4u);
+    const auto d_rs = make_rsrc(a.delta + (size_t)bh * a.nq, (unsigned)nq * 4u);
     const int key = ktile * 64 + 32 * wave + r;
     const bool key_ok = key < nkv;
 
@@ -298,7 +372,9 @@ __global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_kernel(BwdArgs 
     trans_lane(lane, tr0, tr1);
 
     // The Q/dO stream, as the rows kernel's: stage = Q rows, Qᵀ image, dO rows, dOᵀ image, L[64], D[64]
-    const int t_begin = split * a.tiles_per_split, t_end = min(a.qtiles, t_begin + a.tiles_per_split);
+    const int t_begin = split * a.tiles_per_split;
+    const int t_end = min(LENS ? (nq + 63) / 64 : a.qtiles, t_begin + a.tiles_per_split);
+    const bool live = !LENS || (ktile * 64 < nkv && t_begin < t_end);  // (workgroup-uniform)
     Raw8<f16> qst[4], dst[4];
     unsigned ldst;
     auto issue = [&](int t) {
@@ -312,10 +388,12 @@ __global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_kernel(BwdArgs 
         *(__attribute__((address_space(3))) unsigned*)(lds + base + 4 * kTileBytes + 4 * tid) = ldst;
     };
     f32x16 dk0 = {}, dk1 = {}, dv0 = {}, dv1 = {};  // dKᵀ, dVᵀ: dims 0..31 and 32..63, key on the lane
-    issue(t_begin);
-    write(0);
-    __syncthreads();
-    for (int t = t_begin; t < t_end; ++t) {
+    if (live) {
+        issue(t_begin);
+        write(0);
+        __syncthreads();
+    }
+    for (int t = t_begin; live && t < t_end; ++t) {
         const unsigned base = ((t - t_begin) & 1) * kColStage;
         issue(t + 1);  // (past the last block: a stage nobody reads)
         const bool qtail = (t + 1) * 64 > nq;  // wave-uniform: the last block only
@@ -356,7 +434,12 @@ __global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_kernel(BwdArgs 
         __syncthreads();
     }
 
-    if (!key_ok) return;
+    if constexpr (LENS) {
+        if (key >= a.nkv) return;
+        if (!key_ok) dk0 = dk1 = dv0 = dv1 = f32x16{};  // a padded key: zeros, whatever the tiles gave
+    } else {
+        if (!key_ok) return;
+    }
     auto store_row = [&](auto* out, size_t at) {
         typedef std::remove_pointer_t<decltype(out)> T;
 #pragma unroll
@@ -374,7 +457,7 @@ __global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_kernel(BwdArgs 
         dk1 = dv1;
         store_row(reinterpret_cast<TOut*>(a.dv), row);
     } else {
-        const size_t tensor = (size_t)a.bh * nkv * kHeadDim;
+        const size_t tensor = (size_t)a.bh * a.nkv * kHeadDim;
         store_row(a.part + (size_t)split * tensor, row);
         dk0 = dv0;
         dk1 = dv1;
@@ -382,9 +465,26 @@ __global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_kernel(BwdArgs 
     }
 }
 
+template <typename TOut>
+__global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_kernel(BwdArgs a) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * kColStage];
+    bwd_cols_body<TOut, false>(a, blockIdx.x, 0, 0, (lds_char*)smem);
+}
+// grouped: grid = the calls' splits * ktiles * bh, one after the other
+template <typename TOut>
+__global__ __launch_bounds__(kBwdThreads) void mha_hd64_bwd_cols_group_kernel(BwdGroupArgs g) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * kColStage];
+    int block;
+    const int ci = group_call(g.cols_end, blockIdx.x, block);
+    const BwdArgs a = group_pick(g.c, ci);
+    const int item = (block / (a.splits * a.ktiles)) / group_pick(g.heads, ci);
+    bwd_cols_body<TOut, true>(a, block, group_len(group_pick(g.q_lens, ci), item, a.nq),
+                              group_len(group_pick(g.kv_lens, ci), item, a.nkv), (lds_char*)smem);
+}
+
 // Partial dK / dV of the query splits, added in split order: grid = (blocks of 256 x 4 elements, 2).
 template <typename TOut>
-__global__ __launch_bounds__(256) void mha_hd64_bwd_reduce_kernel(BwdArgs a) {
+__device__ __forceinline__ void bwd_reduce_body(const BwdArgs& a) {
     const size_t tensor = (size_t)a.bh * a.nkv * kHeadDim;
     const size_t at = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (at >= tensor) return;
@@ -392,6 +492,16 @@ __global__ __launch_bounds__(256) void mha_hd64_bwd_reduce_kernel(BwdArgs a) {
     f32x4 acc = *reinterpret_cast<const f32x4*>(p);
     for (int s = 1; s < a.splits; ++s) acc += *reinterpret_cast<const f32x4*>(p + (size_t)s * tensor);
     store4<TOut>(reinterpret_cast<TOut*>(blockIdx.y ? a.dv : a.dk) + at, acc[0], acc[1], acc[2], acc[3]);
+}
+template <typename TOut>
+__global__ __launch_bounds__(256) void mha_hd64_bwd_reduce_kernel(BwdArgs a) {
+    bwd_reduce_body<TOut>(a);
+}
+// grouped: grid = (the largest splitting call's blocks, 2, calls); a call without a split wrote its outputs itself
+template <typename TOut>
+__global__ __launch_bounds__(256) void mha_hd64_bwd_reduce_group_kernel(BwdGroupArgs g) {
+    const BwdArgs a = group_pick(g.c, (int)blockIdx.z);
+    if (a.splits > 1) bwd_reduce_body<TOut>(a);
 }
 
 template <typename TOut>
@@ -409,15 +519,18 @@ hipError_t launch_kernels(const BwdArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// The cols kernel's query split: while its 64-key workgroups number at most half the CUs' worth
-// (256 / 2), the query blocks are dealt to up to 16 splits so that about 256 workgroups run.
-BwdPlan plan_backward(int batch, int heads, int nq, int nkv, InType in) {
+// The cols kernel's query split: while the launch's 64-key workgroups (`groups`: this call's, or all of its
+// chunk's in a grouped launch, since the calls of a launch fill the chip together) number at most half of
+// `target`, the query blocks are dealt to up to 16 splits so that about `target` workgroups run. A lone call
+// aims at 256 (one per CU); a grouped launch at 512, which measured faster there (2 calls of P x 4 x 1024 x 1024:
+// P = 1 4 splits 69.7 us against 72.4 with 2, P = 2 2 splits 77.0 against 82.8 with 1, P = 4 1 split 98.9 against
+// 111.4 with 2; profiles/attention_backward/INDEX.md).
+static BwdPlan plan_call(int batch, int heads, int nq, int nkv, InType in, long long groups, int target) {
     BwdPlan p{};
     const long long bh = (long long)batch * heads;
     p.qtiles = (nq + 63) / 64;
     p.ktiles = (nkv + 63) / 64;
-    const long long groups = bh * p.ktiles;
-    int splits = groups > 128 ? 1 : (int)std::min<long long>(std::min(p.qtiles, 16), 256 / groups);
+    int splits = groups > target / 2 ? 1 : (int)std::min<long long>(std::min(p.qtiles, 16), target / groups);
     // measurement hook (tools/attention_backward_ab.py): MHA_HD64_BWD_SPLITS=n forces up to n splits
     if (const char* e = std::getenv("MHA_HD64_BWD_SPLITS"))
         if (std::atoi(e) >= 1) splits = std::min(std::min(p.qtiles, 16), std::atoi(e));
@@ -429,6 +542,74 @@ BwdPlan plan_backward(int batch, int heads, int nq, int nkv, InType in) {
     p.part_bytes = p.splits > 1 ? (size_t)2 * p.splits * bh * nkv * kHeadDim * 4 : 0;
     p.ws_bytes = 2 * p.stats_bytes + p.copy_bytes + p.part_bytes;
     return p;
+}
+
+BwdPlan plan_backward(int batch, int heads, int nq, int nkv, InType in) {
+    return plan_call(batch, heads, nq, nkv, in, (long long)batch * heads * ((nkv + 63) / 64), 256);
+}
+
+BwdGroupPlan plan_backward_group(const BwdCall* calls, int n) {
+    BwdGroupPlan g{};
+    long long groups = 0;
+    for (int i = 0; i < n; ++i) groups += (long long)calls[i].batch * calls[i].heads * ((calls[i].nkv + 63) / 64);
+    for (int i = 0; i < n; ++i) {
+        g.call[i] = plan_call(calls[i].batch, calls[i].heads, calls[i].nq, calls[i].nkv, InType::F16, groups, 512);
+        g.ws_offset[i] = g.ws_bytes;
+        g.ws_bytes += g.call[i].ws_bytes;
+    }
+    return g;
+}
+
+hipError_t launch_backward_group(const BwdCall* calls, const int* const* q_lens, const int* const* kv_lens, int n,
+                                 void* workspace, hipStream_t stream) {
+    const BwdGroupPlan gp = plan_backward_group(calls, n);
+    BwdGroupArgs g{};
+    int rows = 0, cols = 0;
+    size_t reduce_quads = 0;
+    for (int i = 0; i < n; ++i) {
+        const BwdCall& c = calls[i];
+        const BwdPlan& p = gp.call[i];
+        char* ws = reinterpret_cast<char*>(workspace) + gp.ws_offset[i];
+        BwdArgs& a = g.c[i];
+        a.q = reinterpret_cast<const f16*>(c.q);
+        a.k = reinterpret_cast<const f16*>(c.k);
+        a.v = reinterpret_cast<const f16*>(c.v);
+        a.o = reinterpret_cast<const f16*>(c.o);
+        a.dout = reinterpret_cast<const f16*>(c.dout);
+        a.dq = c.dq;
+        a.dk = c.dk;
+        a.dv = c.dv;
+        a.lse = reinterpret_cast<float*>(ws);
+        a.delta = reinterpret_cast<float*>(ws + p.stats_bytes);
+        a.part = reinterpret_cast<float*>(ws + 2 * p.stats_bytes);
+        a.nq = c.nq;
+        a.nkv = c.nkv;
+        a.bh = c.batch * c.heads;
+        a.qtiles = p.qtiles;
+        a.ktiles = p.ktiles;
+        a.splits = p.splits;
+        a.tiles_per_split = p.tiles_per_split;
+        g.q_lens[i] = q_lens ? q_lens[i] : nullptr;
+        g.kv_lens[i] = kv_lens ? kv_lens[i] : nullptr;
+        g.heads[i] = c.heads;
+        rows += a.qtiles * a.bh;
+        cols += a.splits * a.ktiles * a.bh;
+        g.rows_end[i] = rows;
+        g.cols_end[i] = cols;
+        if (p.splits > 1) reduce_quads = std::max(reduce_quads, (size_t)a.bh * a.nkv * kHeadDim / 4);
+    }
+    for (int i = n; i < kGroupCalls; ++i) {  // unused slots: a copy of the last call that no workgroup selects
+        g.c[i] = g.c[n - 1];
+        g.heads[i] = g.heads[n - 1];
+        g.rows_end[i] = rows;
+        g.cols_end[i] = cols;
+    }
+    hipLaunchKernelGGL(mha_hd64_bwd_rows_group_kernel<f16>, dim3((unsigned)rows), dim3(kBwdThreads), 0, stream, g);
+    hipLaunchKernelGGL(mha_hd64_bwd_cols_group_kernel<f16>, dim3((unsigned)cols), dim3(kBwdThreads), 0, stream, g);
+    if (reduce_quads)
+        hipLaunchKernelGGL(mha_hd64_bwd_reduce_group_kernel<f16>, dim3((unsigned)((reduce_quads + 255) / 256), 2, (unsigned)n),
+                           dim3(256), 0, stream, g);
+    return hipGetLastError();
 }
 
 hipError_t launch_backward(const BwdCall& c, InType in, void* workspace, hipStream_t stream) {

@@ -132,6 +132,19 @@ BwdPlan plan_backward(int batch, int heads, int nq, int nkv, InType in);
 // No allocation, no synchronisation: capturable. workspace holds plan_backward(...).ws_bytes.
 hipError_t launch_backward(const BwdCall& c, InType in, void* workspace, hipStream_t stream);
 
+// The grouped, ragged backward (fp16): n <= kGroupCalls calls in one rows, one cols and at most one reduce launch.
+// q_lens / kv_lens (either may be null, and so may any entry): per call a device table of `batch` int32 counts of
+// real query rows / keys, read and clamped into [1, n] by the kernels. The plan is made from the padded shapes; the
+// query split sees the whole launch's workgroups. Workspace: the calls' [L][D][partials], one call after the other.
+struct BwdGroupPlan {
+    BwdPlan call[kGroupCalls];
+    size_t ws_offset[kGroupCalls];
+    size_t ws_bytes;
+};
+BwdGroupPlan plan_backward_group(const BwdCall* calls, int n);
+hipError_t launch_backward_group(const BwdCall* calls, const int* const* q_lens, const int* const* kv_lens, int n,
+                                 void* workspace, hipStream_t stream);
+
 // Record an error for mha_hd64_last_error() (and abort if abort-on-error is set); returns status.
 int32_t report_error(int32_t status, const char* where, const char* what);
 

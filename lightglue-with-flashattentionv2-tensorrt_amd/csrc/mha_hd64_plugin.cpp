@@ -17,6 +17,7 @@
 //  * no pad / unpad / convert launches: tails and the fp32->fp16 rounding happen inside the kernel.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -357,6 +358,76 @@ size_t mha_hd64_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t n
     return mha_hd64::plan_backward(batch, heads, nq, nkv,
                                    in_type == MHA_HD64_DT_FLOAT ? mha_hd64::InType::F32 : mha_hd64::InType::F16)
         .ws_bytes;
+}
+
+// ---- grouped, ragged backward ----
+// The calls with something to compute, validated, with their lens tables beside them (null where none is given).
+// pointers false: the workspace query, which reads the shapes only.
+static int32_t to_bwd_calls(const mha_hd64_bwd_call_t* calls, const int32_t* const* q_lens, const int32_t* const* kv_lens,
+                            int32_t n, std::vector<mha_hd64::BwdCall>& out, std::vector<const int32_t*>& ql,
+                            std::vector<const int32_t*>& kl, bool pointers = true) {
+    MHA_CHECK(n >= 0 && (n == 0 || calls != nullptr));
+    for (int32_t i = 0; i < n; ++i) {
+        const mha_hd64_bwd_call_t& c = calls[i];
+        MHA_CHECK(c.batch >= 0 && c.heads >= 0 && c.nq >= 0 && c.nkv >= 0);
+        if (c.batch == 0 || c.heads == 0 || c.nq == 0) continue;
+        MHA_CHECK(c.nkv >= 1);
+        // (a head's bytes fit a buffer descriptor; a chunk of 4 grids, 16 splits at most, fits 31 bits)
+        MHA_CHECK(c.nq < (1 << 24) && c.nkv < (1 << 24));
+        MHA_CHECK((long long)c.batch * c.heads * ((c.nq > c.nkv ? c.nq : c.nkv) / 64 + 1) * 16 < (1ll << 29));
+        if (pointers) {
+            MHA_CHECK(c.q != nullptr && c.k != nullptr && c.v != nullptr && c.o != nullptr && c.dout != nullptr);
+            MHA_CHECK(c.dq != nullptr && c.dk != nullptr && c.dv != nullptr);
+            MHA_CHECK(((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v | (uintptr_t)c.o | (uintptr_t)c.dout |
+                       (uintptr_t)c.dq | (uintptr_t)c.dk | (uintptr_t)c.dv) % 16 == 0);
+        }
+        MHA_CHECK(q_lens == nullptr || (uintptr_t)q_lens[i] % 4 == 0);
+        MHA_CHECK(kv_lens == nullptr || (uintptr_t)kv_lens[i] % 4 == 0);
+        out.push_back(mha_hd64::BwdCall{c.q, c.k, c.v, c.o, c.dout, c.dq, c.dk, c.dv, c.batch, c.heads, c.nq, c.nkv});
+        ql.push_back(q_lens ? q_lens[i] : nullptr);
+        kl.push_back(kv_lens ? kv_lens[i] : nullptr);
+    }
+    return MHA_HD64_STATUS_SUCCESS;
+}
+
+// The largest chunk's workspace (chunks of kGroupCalls reuse it in stream order).
+static size_t bwd_group_bytes(const std::vector<mha_hd64::BwdCall>& v) {
+    size_t need = 0;
+    for (size_t at = 0; at < v.size(); at += mha_hd64::kGroupCalls) {
+        const int n = (int)std::min<size_t>(mha_hd64::kGroupCalls, v.size() - at);
+        need = std::max(need, mha_hd64::plan_backward_group(v.data() + at, n).ws_bytes);
+    }
+    return need;
+}
+
+int32_t mha_hd64_backward_grouped_lens(const mha_hd64_bwd_call_t* calls, const int32_t* const* q_lens,
+                                       const int32_t* const* kv_lens, int32_t n_calls, int32_t in_type, void* workspace,
+                                       size_t ws_bytes, hipStream_t stream) {
+    MHA_CHECK(in_type == MHA_HD64_DT_HALF);  // fp16 tensors only
+    std::vector<mha_hd64::BwdCall> v;
+    std::vector<const int32_t*> ql, kl;
+    const int32_t st = to_bwd_calls(calls, q_lens, kv_lens, n_calls, v, ql, kl);
+    if (st != MHA_HD64_STATUS_SUCCESS || v.empty()) return st;
+    MHA_CHECK(workspace != nullptr && (uintptr_t)workspace % 16 == 0);
+    if (ws_bytes < bwd_group_bytes(v))
+        return fail(MHA_HD64_STATUS_WORKSPACE, __FILE__, __LINE__,
+                    "workspace smaller than mha_hd64_backward_grouped_workspace_bytes");
+    for (size_t at = 0; at < v.size(); at += mha_hd64::kGroupCalls) {
+        const int n = (int)std::min<size_t>(mha_hd64::kGroupCalls, v.size() - at);
+        const int32_t s = launch_status(
+            mha_hd64::launch_backward_group(v.data() + at, ql.data() + at, kl.data() + at, n, workspace, stream), __FILE__,
+            __LINE__);
+        if (s != MHA_HD64_STATUS_SUCCESS) return s;
+    }
+    return MHA_HD64_STATUS_SUCCESS;
+}
+
+size_t mha_hd64_backward_grouped_workspace_bytes(const mha_hd64_bwd_call_t* calls, int32_t n_calls, int32_t in_type) {
+    if (in_type != MHA_HD64_DT_HALF) return 0;
+    std::vector<mha_hd64::BwdCall> v;
+    std::vector<const int32_t*> ql, kl;
+    if (to_bwd_calls(calls, nullptr, nullptr, n_calls, v, ql, kl, false) != MHA_HD64_STATUS_SUCCESS) return 0;
+    return bwd_group_bytes(v);
 }
 
 // ---- grouped launcher ----

@@ -89,6 +89,12 @@ class CallDesc(ctypes.Structure):
                 ("nkv", ctypes.c_int32)]
 
 
+class BwdCallDesc(ctypes.Structure):
+    """Mirrors mha_hd64_bwd_call_t (one call of a grouped backward)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("q", "k", "v", "o", "dout", "dq", "dk", "dv")] + \
+               [(name, ctypes.c_int32) for name in ("batch", "heads", "nq", "nkv")]
+
+
 class ImgSrc(ctypes.Structure):
     """Mirrors lg_img_src (include/lightglue_glue.h, "image input"): one source image of lg_img_prepare's table."""
     _fields_ = [("data", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("channels", ctypes.c_int32),
@@ -135,6 +141,9 @@ SIGNATURES = {
     "mha_hd64_backward_fp16": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _S, _P], _I),
     "mha_hd64_backward_fp32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _S, _P], _I),
     "mha_hd64_backward_workspace_bytes": ([_I, _I, _I, _I, _I], _S),
+    "mha_hd64_backward_grouped_lens": ([ctypes.POINTER(BwdCallDesc), ctypes.POINTER(_P), ctypes.POINTER(_P), _I, _I, _P, _S,
+                                        _P], _I),
+    "mha_hd64_backward_grouped_workspace_bytes": ([ctypes.POINTER(BwdCallDesc), _I, _I], _S),
     "mha_hd64_launch_grouped": ([ctypes.POINTER(CallDesc), _I, _I, _I, _P, _S, _P], _I),
     "mha_hd64_grouped_workspace_bytes": ([ctypes.POINTER(CallDesc), _I], _S),
     "mha_hd64_grouped_workspace_bytes_typed": ([ctypes.POINTER(CallDesc), _I, _I], _S),

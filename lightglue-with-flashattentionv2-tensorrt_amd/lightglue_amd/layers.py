@@ -221,6 +221,36 @@ class TransformerLayer(nn.Module):
             v0, v1 = ca.heads_of(ca.to_v(x), splits)
         return ca.finish(x, attention([(qk0, qk1, v1), (qk1, qk0, v0)]), hip)  # one grouped launch (cross)
 
+    def forward_train(self, x, cos, sin, splits, lens=None):
+        """The layer for training (fp16, 4 x 64 heads, on the GPU), every step an op with a gfx950 backward:
+        SelfBlock.qkv_train, the grouped attention (self0, self1), ffn_residual with out_proj, CrossBlock.qk_v_train,
+        the grouped attention (both cross directions), ffn_residual with to_out. x [1, P*(m+n), 256] -> the same.
+
+        lens = (counts0, counts1), int32 [P] on the device: a padded batch. The attention is then
+        mha_hd64_grouped_lens, which takes KEY counts only (self attention of image i reads counts_i, cross attention
+        i -> j counts_j), and not mha_hd64_grouped_qkv_lens: that one writes NaN into padded query rows, and 0 x NaN
+        would poison the weight gradients, which sum over all rows. With key counts only a padded row is computed
+        like any other (from real keys: finite wherever the padded inputs are finite) and its gradient is exactly zero, by
+        induction from the loss backwards: lg_assign_nll writes zero dv on padded rows; lg_proj_backward and
+        lg_ffn_backward map a zero gradient row to a zero row; the attention backward gives zero dK and dV on padded
+        keys, and zero dQ on padded queries because their dO is zero (dP = dO V^T = 0 and D = 0, so dS = 0). A zero
+        row adds nothing to a weight gradient, so padded rows change no bit of any parameter's gradient.
+        cos and sin get no gradient (posenc.Wr is not trained through this path)."""
+        sa, ca = self.self_attn, self.cross_attn
+        ops = torch.ops.lightglue_amd
+
+        def attend(qs, ks, vs, key_lens):
+            if lens is None:
+                return ops.mha_hd64_grouped(qs, ks, vs)
+            return ops.mha_hd64_grouped_lens(qs, ks, vs, key_lens)
+
+        q0, k0, v0, q1, k1, v1 = sa.qkv_train(x, cos, sin, splits)
+        c0, c1 = attend([q0, q1], [k0, k1], [v0, v1], lens and [lens[0], lens[1]])
+        x = ffn_residual(sa, sa.out_proj, x, c0, c1)
+        qk0, qk1, v0, v1 = ca.qk_v_train(x, splits)
+        m0, m1 = attend([qk0, qk1], [qk1, qk0], [v1, v0], lens and [lens[1], lens[0]])
+        return ffn_residual(ca, ca.to_out, x, m0, m1)
+
     def _forward_fused(self, x, cos, sin, splits, attention: AttnFn):
         """The fp16 hip layer on its own (no chain): fused_step with nothing folded."""
         return self.fused_step(x, cos, sin, splits, None, attention, attention)[0]

@@ -264,6 +264,28 @@ class LightGlueMatcher(nn.Module):
             return x, v
         return x, _Hip.assign_scores(v, m, x.shape[-1], lens)
 
+    def loss(self, kpts0, kpts1, desc0, desc1, gt0, gt1, counts0=None, counts1=None, deep: bool = True) -> torch.Tensor:
+        """The training loss of P pairs, fp32 [P], differentiable in every parameter but posenc.Wr: _inputs, then per
+        layer TransformerLayer.forward_train and, on its output, log_assignment[i].loss_rows (lg_assign_nll; gt0 / gt1
+        as loss.py describes them). deep: the published LightGlue deep supervision, the mean over all layers' heads;
+        else the last head alone. counts0 / counts1: a padded batch, as for forward; padded rows may hold any finite
+        values and change no bit of the loss or of a gradient (forward_train's docstring has the argument). Every
+        step's backward is a gfx950 kernel. posenc.Wr gets no gradient: cos and sin have none in the projections'
+        backward. The fp16 hip path only (chain_ok, the kernel attention): PluginError elsewhere."""
+        pr, m, n = desc0.shape[0], desc0.shape[1], desc1.shape[1]
+        if not self._lens_fast(desc0, m, n):
+            raise PluginError("LightGlueMatcher.loss: the fp16 model with glue='hip' and the kernel attention, on the GPU")
+        lens = None
+        if counts0 is not None or counts1 is not None:
+            lens = (self._counts(counts0, pr, m, "counts0", desc0.device)[1], self._counts(counts1, pr, n, "counts1", desc0.device)[1])
+        x, cos, sin = self._inputs(kpts0, kpts1, desc0, desc1, True)
+        terms = []
+        for li, layer in enumerate(self.transformers):
+            x = layer.forward_train(x, cos, sin, (m, n, pr), lens)
+            if deep or li + 1 == self.n_layers:
+                terms.append(self.log_assignment[li].loss_rows(x, pr, m, n, gt0, gt1, lens))
+        return torch.stack(terms).mean(0)
+
     def match(self, kpts0, kpts1, desc0, desc1):
         """forward + filter_matches (the demo's post-processing); for P > 1 pairs a list of
         (matches, scores), one per pair."""

@@ -12,6 +12,9 @@ PyTorch-ROCm module via a torch.library op that invokes enqueue on torch.cuda.cu
 * ``torch.ops.lightglue_amd.mha_hd64_grouped_lens(qs, ks, vs, lens) -> os`` and
   ``mha_hd64_grouped_qkv_lens(qs, ks, vs, q_lens, kv_lens)``: the same on ragged batches, with int32
   device tables of per-item key (and query-row) counts (fp16 only).
+* ``torch.ops.lightglue_amd.mha_hd64_grouped_backward(qs, ks, vs, os, dos, q_lens, kv_lens) -> [dq_0, dk_0, dv_0, ...]``:
+  the gradient of all three grouped ops in one set of launches (mha_hd64_backward_grouped_lens), registered as their
+  autograd; padded rows get zero gradients.
 
 * ``torch.ops.lightglue_amd.assign_nll(v, m, zc, gt0, gt1, m_len=None, n_len=None) -> [loss, dv]``: the matcher's
   training loss per pair and its gradient in v (csrc/lightglue_assign_nll.hip), differentiable in v.
@@ -37,6 +40,7 @@ import torch
 
 from .plugin import mha_hd64 as _enqueue
 from .plugin import mha_hd64_backward as _backward
+from .plugin import mha_hd64_backward_grouped as _grouped_backward
 from .plugin import mha_hd64_grouped as _grouped
 
 
@@ -113,6 +117,50 @@ def mha_hd64_grouped_qkv_lens_op(queries: List[torch.Tensor], keys: List[torch.T
 @mha_hd64_grouped_qkv_lens_op.register_fake
 def _(queries, keys, values, q_lens, kv_lens):
     return [torch.empty_like(q, memory_format=torch.contiguous_format) for q in queries]
+
+
+@torch.library.custom_op("lightglue_amd::mha_hd64_grouped_backward", mutates_args=(), device_types="cuda")
+def mha_hd64_grouped_backward_op(queries: List[torch.Tensor], keys: List[torch.Tensor], values: List[torch.Tensor],
+                                 outs: List[torch.Tensor], douts: List[torch.Tensor], q_lens: List[Optional[torch.Tensor]],
+                                 kv_lens: List[Optional[torch.Tensor]]) -> List[torch.Tensor]:
+    """[dq_0, dk_0, dv_0, dq_1, ...] of the grouped ops from their inputs, outputs and the outputs' gradients
+    (mha_hd64_backward_grouped_lens); q_lens / kv_lens: per call the int32 [B] counts or None, an empty list for none
+    at all. Gradients of padded rows are zeros. fp16 only."""
+    cont = [[t.contiguous() for t in ts] for ts in (queries, keys, values, outs, douts)]
+    grads = _grouped_backward(list(zip(*cont[:3])), cont[3], cont[4], kv_lens=list(kv_lens) or None,
+                              q_lens=list(q_lens) or None)
+    return [g for triple in grads for g in triple]
+
+
+@mha_hd64_grouped_backward_op.register_fake
+def _(queries, keys, values, outs, douts, q_lens, kv_lens):
+    return [torch.empty_like(t, memory_format=torch.contiguous_format) for qkv in zip(queries, keys, values) for t in qkv]
+
+
+def _grouped_autograd(op, n_lens):
+    """Registers mha_hd64_grouped_backward as op's autograd: inputs (queries, keys, values) and n_lens lists of counts
+    (one: the key counts; two: query rows, then keys)."""
+
+    def setup(ctx, inputs, output):
+        ctx.n = len(output)
+        ctx.lens = [list(l) for l in inputs[3:]]  # (int32 tables: no gradient, kept as they are)
+        ctx.save_for_backward(*inputs[0], *inputs[1], *inputs[2], *output)
+
+    def backward(ctx, douts):
+        n, saved = ctx.n, ctx.saved_tensors
+        qs, ks, vs, os_ = (list(saved[i * n:(i + 1) * n]) for i in range(4))
+        q_lens, kv_lens = ([], []) if n_lens == 0 else ([], ctx.lens[0]) if n_lens == 1 else ctx.lens
+        got = torch.ops.lightglue_amd.mha_hd64_grouped_backward(qs, ks, vs, os_, list(douts), q_lens, kv_lens)
+        need = ctx.needs_input_grad
+        grads = tuple([got[3 * i + j] if need[j][i] else None for i in range(n)] for j in range(3))
+        return grads + tuple([None] * n for _ in range(n_lens))  # (a list input's gradient is a list)
+
+    op.register_autograd(backward, setup_context=setup)
+
+
+_grouped_autograd(mha_hd64_grouped_op, 0)
+_grouped_autograd(mha_hd64_grouped_lens_op, 1)
+_grouped_autograd(mha_hd64_grouped_qkv_lens_op, 2)
 
 
 @torch.library.custom_op("lightglue_amd::assign_nll", mutates_args=(), device_types="cuda")

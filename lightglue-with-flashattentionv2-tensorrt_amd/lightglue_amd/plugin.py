@@ -392,25 +392,11 @@ def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None
     if kv_lens is not None:
         if in_dtype != torch.float16:
             raise PluginError("kv_lens / q_lens: float16 inputs only")
-
-        def table(lens, what):
-            lens = list(lens)
-            if len(lens) != len(calls):
-                raise PluginError(f"{what}: one entry per call")
-            ptrs = (ctypes.c_void_p * len(calls))()
-            for i, (t, (q, _, _)) in enumerate(zip(lens, calls)):
-                if t is None:
-                    continue
-                if t.dtype != torch.int32 or t.device != q.device or not t.is_contiguous() or tuple(t.shape) != (q.shape[0],):
-                    raise PluginError(f"{what}[i]: a contiguous int32 tensor [B] on the call's device, or None")
-                ptrs[i] = t.data_ptr()
-            return ptrs
-
-        kp = table(kv_lens, "kv_lens")
+        kp = _lens_table(kv_lens, calls, "kv_lens")
         if q_lens is None:
             status = lib.mha_hd64_launch_grouped_lens(descs, kp, len(calls), DT[in_dtype], DT[out_dtype], None, 0, stream)
         else:
-            status = lib.mha_hd64_launch_grouped_qkv_lens(descs, table(q_lens, "q_lens"), kp, len(calls), DT[in_dtype],
+            status = lib.mha_hd64_launch_grouped_qkv_lens(descs, _lens_table(q_lens, calls, "q_lens"), kp, len(calls), DT[in_dtype],
                                                           DT[out_dtype], None, 0, stream)
         _check(status, "mha_hd64_launch_grouped_lens")
         return outs
@@ -422,6 +408,57 @@ def mha_hd64_grouped(calls, out_dtype=None, outs=None, kv_lens=None, q_lens=None
                                          ws.data_ptr() if ws is not None else None, nbytes, stream)
     _check(status, "mha_hd64_launch_grouped")
     return outs
+
+
+def _lens_table(lens, calls, what):
+    """The pointer array of one lens argument: per call an int32 tensor [B] on its device, or None."""
+    lens = list(lens)
+    if len(lens) != len(calls):
+        raise PluginError(f"{what}: one entry per call")
+    ptrs = (ctypes.c_void_p * len(calls))()
+    for i, (t, (q, _, _)) in enumerate(zip(lens, calls)):
+        if t is None:
+            continue
+        if t.dtype != torch.int32 or t.device != q.device or not t.is_contiguous() or tuple(t.shape) != (q.shape[0],):
+            raise PluginError(f"{what}[i]: a contiguous int32 tensor [B] on the call's device, or None")
+        ptrs[i] = t.data_ptr()
+    return ptrs
+
+
+def mha_hd64_backward_grouped(calls, outs, douts, kv_lens=None, q_lens=None):
+    """The backward of mha_hd64_grouped on the current stream (mha_hd64_backward_grouped_lens): calls [(q, k, v), ...]
+    as the forward took them, its outputs and their gradients, float16 -> [(dq, dk, dv), ...]. Up to 4 calls share one
+    rows, one cols and at most one reduce launch. kv_lens / q_lens as the forward's: item b of call i has
+    q_lens[i][b] real query rows and kv_lens[i][b] real keys (None: all); rows past the counts are never read, and
+    their gradients are zeros. Deterministic (no atomics), no host synchronisation, capturable."""
+    calls, outs, douts = list(calls), list(outs), list(douts)
+    if not calls:
+        return []
+    if len(outs) != len(calls) or len(douts) != len(calls):
+        raise PluginError("grouped backward: one output and one gradient per call")
+    descs = (_lib.BwdCallDesc * len(calls))()
+    grads = []
+    for i, ((q, k, v), o, do) in enumerate(zip(calls, outs, douts)):
+        _require_gpu(q, k, v, o, do)
+        for t in (q, k, v, o, do):
+            if not t.is_contiguous() or t.dim() != 4 or t.shape[-1] != 64 or t.dtype != torch.float16:
+                raise PluginError("expected contiguous float16 [B, H, N, 64] tensors")
+        if k.shape != v.shape or k.shape[:2] != q.shape[:2] or o.shape != q.shape or do.shape != q.shape:
+            raise PluginError("shape mismatch in grouped backward call")
+        g = (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
+        grads.append(g)
+        descs[i] = _lib.BwdCallDesc(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), g[0].data_ptr(),
+                                    g[1].data_ptr(), g[2].data_ptr(), q.shape[0], q.shape[1], q.shape[2], k.shape[2])
+    lib = _lib.load()
+    stream = stream_of(calls[0][0])
+    qp = _lens_table(q_lens, calls, "q_lens") if q_lens is not None else None
+    kp = _lens_table(kv_lens, calls, "kv_lens") if kv_lens is not None else None
+    nbytes = lib.mha_hd64_backward_grouped_workspace_bytes(descs, len(calls), DT[torch.float16])
+    ws = _workspace(calls[0][0].device, stream, nbytes) if nbytes else None
+    status = lib.mha_hd64_backward_grouped_lens(descs, qp, kp, len(calls), DT[torch.float16],
+                                                ws.data_ptr() if ws is not None else None, nbytes, stream)
+    _check(status, "mha_hd64_backward_grouped_lens")
+    return grads
 
 
 class MHAHeadDim64(torch.autograd.Function):

@@ -7,7 +7,14 @@ Arms, alternated in one process, medians of 9 replays after warm-up, each replay
 and, with --splits, ours once per forced query split of the column kernel (MHA_HD64_BWD_SPLITS), each next
 to the default, for the split decision in DESIGN.md. Appends one JSON line per shape to --out.
 
+--grouped: a matcher layer's backward instead, its four attention calls (self0, self1, cross 0->1, cross 1->0) of
+P x 4 x n x n at P = 1, 4, 16, n = 1024, as autograd issues them (the self pair, then the cross pair), per replay:
+  grouped         two mha_hd64_backward_grouped calls of two calls each, every count n
+  single          four mha_hd64_backward calls (the code before the grouped call existed)
+  grouped_ragged  the grouped calls with per-pair counts drawn in [n/2, n]
+
     python tools/attention_backward_ab.py [--shapes 1x4x1024x1024,...] [--splits 1,2,4,8,16] [--out ...]
+    python tools/attention_backward_ab.py --grouped [--out profiles/attention_backward/grouped_ab.jsonl]
 """
 import argparse
 import json
@@ -84,12 +91,60 @@ def measure(shape, splits):
     return rec
 
 
+def timed(arms):
+    """{arm: min / median / max ms} of 9 replays after 3 warm-up rounds, the arms alternating."""
+    times = {name: [] for name in arms}
+    for rep in range(3 + 9):
+        for name, graph in arms.items():
+            t = replay_ms(graph)
+            if rep >= 3:
+                times[name].append(t)
+    return {name + "_ms": {"min": round(min(t), 4), "median": round(statistics.median(t), 4), "max": round(max(t), 4)}
+            for name, t in times.items()}
+
+
+def measure_grouped(pairs, n):
+    g = torch.Generator(device="cuda").manual_seed(pairs)
+    rand = lambda: torch.randn(pairs, 4, n, 64, generator=g, device="cuda", dtype=torch.float16)  # noqa: E731
+    full = [torch.full((pairs,), n, dtype=torch.int32, device="cuda") for _ in range(2)]
+    some = [torch.randint(n // 2, n + 1, (pairs,), generator=g, device="cuda", dtype=torch.int32) for _ in range(2)]
+    calls = [tuple(rand() for _ in range(3)) for _ in range(4)]
+    douts = [rand() for _ in range(4)]
+    outs = lightglue_amd.mha_hd64_grouped(calls)
+
+    def grouped(c):
+        for at, lens in ((0, (c[0], c[1])), (2, (c[1], c[0]))):  # self: own counts; cross i -> j: rows i, keys j
+            lightglue_amd.mha_hd64_backward_grouped(calls[at:at + 2], outs[at:at + 2], douts[at:at + 2], kv_lens=list(lens),
+                                                    q_lens=[c[0], c[1]])
+
+    def single():
+        for (q, k, v), o, do in zip(calls, outs, douts):
+            lightglue_amd.mha_hd64_backward(q, k, v, o, do)
+
+    rec = {"pairs": pairs, "n": n, "calls_per_replay": CALLS, "counts": [t.tolist() for t in some]}
+    rec.update(timed({"grouped": captured(lambda: grouped(full)), "single": captured(single),
+                      "grouped_ragged": captured(lambda: grouped(some))}))
+    rec["grouped_over_single"] = round(rec["grouped_ms"]["median"] / rec["single_ms"]["median"], 3)
+    rec["ragged_over_grouped"] = round(rec["grouped_ragged_ms"]["median"] / rec["grouped_ms"]["median"], 3)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="1x4x1024x1024,1x4x2048x2048,16x4x1024x1024")
     ap.add_argument("--splits", default="", help="forced splits to time as well, on the first and last shape")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "attention_backward", "ab.jsonl"))
+    ap.add_argument("--grouped", action="store_true", help="time a layer's four calls: grouped against four single calls")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(REPO, "profiles", "attention_backward", "grouped_ab.jsonl" if args.grouped else "ab.jsonl")
+    if args.grouped:
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        for pairs in (1, 4, 16):
+            rec = measure_grouped(pairs, 1024)
+            print(json.dumps(rec))
+            with open(args.out, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+        return
     shapes = [tuple(int(x) for x in s.split("x")) for s in args.shapes.split(",")]
     splits = [int(s) for s in args.splits.split(",") if s]
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
